@@ -25,9 +25,17 @@ layer) when it reproduces the separate form bit for bit at start-up on every ran
 (the one-shot peer kernel when IT reproduces RCCL, else RCCL's all_gather_into_tensor); the other forms and the shard
 kernels alone are timed beside it ("sharded_chain"). N > 1 was never run on real links by the builder.
 
+A plain run sets up, warms up, times --steps steps and prints the JSON line; its "roofline" carries only what the timed
+region's own clocks give (frac, frac_wall). Everything else below takes runs of its own and is measured with --full only.
+
+--dump-outputs DIR (after the timed steps): what the timed path returned in its last step, as DIR/<name>.npy in float32 - "y",
+the outputs of the step's LAYERS launches stacked (LAYERS x M x N; with --gpus N > 1 the last layer's gathered output). The
+inputs are seeded, so two builds run with the same arguments can be compared output for output. An output above
+DUMP_LIMIT_BYTES is written as a fixed, seeded sample of its elements (dump_outputs()).
+
 Extra objects on the JSON line:
   "roofline"      dominant kernel; achieved = algorithmic bytes / kernel_us, frac = achieved / 8 TB/s. FOUR clocks are
-                  taken and all stay on the line:
+                  taken (frac_span and frac_rocprof with --full only) and all stay on the line:
                     frac         (the figure of record) kernel_us = HIP events - recorded on the stream the kernels are launched
                                  on - around the timed region / launches: the product binary, kernel + launch boundary;
                     frac_wall    the same region on the host's wall clock (perf_counter around synchronize: what `value` and
@@ -41,6 +49,7 @@ Extra objects on the JSON line:
                                  cross-check the rules name; the CSV is copied to --profile-out when given);
                   "method" says which clock each key uses; the HIP-event launch-to-launch time of a separate 10-replay region is
                   kept as a secondary key; "traffic" from two rocprofv3 PMC passes.
+With --full also:
   "cpu_baseline"  (N = 1, rank 0) the reference's own AVX512-BF16 fused CPU gemv from oracle/_ref when the host
                   supports it, else the scalar port from oracle/.
   "headline_sweep_N4096_K4096"  M = 1..64 (the other half of BASELINE.json's metric; --no-sweep skips it): every entry carries the
@@ -49,6 +58,7 @@ Extra objects on the JSON line:
                   HBM traffic per call from the PMC counters (--no-config3 skips it).
   "grouped"       the same 128 layers launched as 32 groups of 4 through matmul_4bit_grouped (one launch per group):
                   what the boundary costs, reported beside the headline, never instead of it; "sweep": the same at M = 1 ... 32.
+  "sharded_chain" (--gpus N > 1) the chain's other forms timed beside `value`; a plain run carries only its geometry.
 """
 import argparse
 import json
@@ -132,6 +142,28 @@ def capture(fn):
     g.replay()
     torch.cuda.synchronize()
     return g
+
+
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every tensor of `arrays` ({name: tensor}) as out_dir/<name>.npy in float32. When they would exceed DUMP_LIMIT_BYTES
+    in all, each is replaced by the same fixed sample of its flattened elements every run: positions drawn by a CPU generator
+    seeded with 0, in ascending order."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        flat = t.detach().float().cpu().reshape(-1)
+        if total > DUMP_LIMIT_BYTES:
+            keep = min(flat.numel(), DUMP_LIMIT_BYTES // 4 // len(arrays))
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            arr = flat[idx].numpy()
+        else:
+            arr = flat.reshape(t.shape).numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def cpu_baseline(M, N, K, blocksize, quant_type):
@@ -429,13 +461,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (CPU baseline, M sweep, grouped launches, config3, rocprofv3 kernel "
+                         "trace and PMC passes, kernel span, the sharded chain's other forms); the --no-* options skip parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32)")
     ap.add_argument("--m", type=int, default=1, help="activation rows (headline: 1)")
     ap.add_argument("--n", type=int, default=4096)
     ap.add_argument("--k", type=int, default=4096)
     ap.add_argument("--blocksize", type=int, default=64)
     ap.add_argument("--quant-type", default="nf4")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sweep", action="store_true", help="(default at N = 1) also time M = 1..64 at N = K = 4096: the headline sweep of BASELINE.json's metric")
+    ap.add_argument("--sweep", action="store_true", help="(part of --full at N = 1) also time M = 1..64 at N = K = 4096: the headline sweep of BASELINE.json's metric")
     ap.add_argument("--no-sweep", action="store_true", help="skip the M = 1..64 sweep")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC passes that fill roofline.traffic")
     ap.add_argument("--no-rocprof", action="store_true", help="skip the rocprofv3 kernel-trace pass (roofline then falls back to HIP events)")
@@ -452,6 +489,8 @@ def main():
     ap.add_argument("--prof-eager", action="store_true", help=argparse.SUPPRESS)  # ... enqueued eagerly (PMC passes serialise dispatches)
     ap.add_argument("--layers", type=int, default=LAYERS, help=argparse.SUPPRESS)  # child passes of the config3 leg: a shorter rotation
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.span_child:
         kernel_span_child(args.m, args.n, args.k, args.blocksize, args.quant_type)
         return
@@ -495,10 +534,17 @@ def main():
         nbytes_step = LAYERS * nbytes_layer
         flops_step = LAYERS * 2 * M * N * K
 
-        # ---- one step = the 128 layers, each its own launch through the public op
+        # ---- one step = the 128 layers, each its own launch through the public op. With --dump-outputs, outs holds what the last
+        # step returned; otherwise every output is dropped at once, as a caller's would be, and the next launch reuses its memory
+        # (holding all 128 costs a plain run ~0.3 % on the step).
+        outs = [None] * len(layers)
+
         def step_fn():
-            for q, st in layers:
-                bnb.matmul_4bit(x, q, st)
+            for i, (q, st) in enumerate(layers):
+                if args.dump_outputs:
+                    outs[i] = bnb.matmul_4bit(x, q, st)
+                else:
+                    bnb.matmul_4bit(x, q, st)
     else:
         # ---- N-sharded decode chain (bitsandbytes_amd.parallel semantics: rows sharded, x replicated, no reduction). The model
         # is an MLP stack, up (H -> F) / down (F -> H), every layer sharded by output features over the ranks and every layer's
@@ -614,11 +660,10 @@ def main():
                                 ("separate one-shot peer kernel per layer (peer.PeerAllGather)" if peer is not None else "RCCL all_gather_into_tensor per layer"),
                       "fused_chain_not_used_because": why_chain}
 
+        outs = [None]
+
         def step_fn():
-            if fused_mod is not None:
-                fused_mod(x)
-            else:
-                separate_fn()
+            outs[0] = fused_mod(x) if fused_mod is not None else separate_fn()
 
     if args.prof_child:
         if args.prof_eager:
@@ -678,7 +723,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, elapsed_events = float(t[0].item()), float(t[1].item())
 
-    # ---- secondary timings (outside the timed region)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"y": torch.stack(outs) if not multi else outs[0]})
+
+    # ---- secondary timings (outside the timed region; --full only)
     def graph_us_per_launch(fn, launches, reps=10):
         g = capture(fn)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -697,10 +745,10 @@ def main():
                 bnb.matmul_4bit(xm, q, st)
         return graph_us_per_launch(fn, LAYERS, reps)
 
-    side_forms = None
-    if not multi:
+    side_forms = kernel_us_events = None
+    if args.full and not multi:
         kernel_us_events = per_launch_us(M)
-    else:
+    elif args.full:
         # the same chain in its other forms, beside `value` (every rank enqueues the same work; MAX over ranks):
         #   kernels alone: the shard kernels of the chain on resident inputs, no exchange at all - what a layer costs without the gather
         #   separate gather: shard kernel, then a collective per layer (round 3's form)
@@ -727,7 +775,7 @@ def main():
                       "us_per_layer_timed_region": round(elapsed / args.steps / LAYERS * 1e6, 3)}
 
     sweep = grouped = None
-    if not multi and (args.sweep or not args.no_sweep) and rank == 0:
+    if not multi and (args.sweep or (args.full and not args.no_sweep)) and rank == 0:
         sweep = []
         for m_rows in (1, 2, 4, 8, 16, 32, 64):
             t_us = per_launch_us(m_rows, reps=5)
@@ -760,7 +808,7 @@ def main():
         grouped["sweep"] = gsweep
 
     config3 = None
-    if not multi and not args.no_config3 and rank == 0 and (M, N, K) == (1, 4096, 4096):
+    if args.full and not multi and not args.no_config3 and rank == 0 and (M, N, K) == (1, 4096, 4096):
         try:
             config3 = config3_leg(device, with_pmc=not args.no_pmc)
         except Exception as exc:  # informational: never lose the headline over it
@@ -770,11 +818,11 @@ def main():
         total_steps = args.steps * world
         value = nbytes_step * total_steps / elapsed / 1e9
         extra = ["--m", str(M), "--n", str(N), "--k", str(K), "--blocksize", str(bs), "--quant-type", qt]
-        avg_ns, kt_detail = (None, {"skipped": "--no-rocprof or multi-GPU run"})
-        if not multi and not args.no_rocprof:
+        avg_ns, kt_detail = (None, {"skipped": "no --full, --no-rocprof or multi-GPU run"})
+        if args.full and not multi and not args.no_rocprof:
             avg_ns, kt_detail = rocprof_kernel_stats(extra, args.profile_out)
-        span_us, span_detail = (None, {"skipped": "--no-span or multi-GPU run"})
-        if not multi and not args.no_span:
+        span_us, span_detail = (None, {"skipped": "no --full, --no-span or multi-GPU run"})
+        if args.full and not multi and not args.no_span:
             span_us, span_detail = kernel_span(extra, args.span_out)
         # Round 5: the figure of record is the one the PRODUCT binary's own clock gives - HIP events around the timed region divided by
         # the launches in it (kernel + the boundary to the next dependent launch): what the contract prescribes and what the driver's
@@ -832,7 +880,7 @@ def main():
                 "frac_rocprof": None if avg_ns is None else round(nbytes_layer / (avg_ns * 1e-9) / 1e9 / HBM_PEAK_GBS, 4),
                 "traffic": None,
                 "kernel_us": round(kernel_us, 3),
-                "kernel_us_launch_to_launch_events": round(kernel_us_events, 3),
+                "kernel_us_launch_to_launch_events": None if kernel_us_events is None else round(kernel_us_events, 3),
                 "kernel_us_rocprof_stats": None if avg_ns is None else round(avg_ns / 1e3, 3),
                 "kernel_span": span_detail,
                 "kernel_us_span": None if span_us is None else round(span_us, 3),
@@ -842,19 +890,19 @@ def main():
                 "kernel_trace": kt_detail,
             },
         }
-        if not multi and not args.no_pmc:
+        if args.full and not multi and not args.no_pmc:
             traffic, detail = pmc_traffic(extra)
             line["roofline"]["traffic"] = None if traffic is None else round(traffic)
             line["roofline"]["traffic_detail"] = detail
-        if side_forms is not None:
-            line["sharded_chain"] = {**chain_info, **side_forms}
+        if multi:
+            line["sharded_chain"] = {**chain_info, **(side_forms or {})}
         if sweep is not None:
             line["headline_sweep_N4096_K4096"] = sweep
         if grouped is not None:
             line["grouped"] = grouped
         if config3 is not None:
             line["config3"] = config3
-        if not multi and not args.no_cpu_baseline:
+        if args.full and not multi and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(M, N, K, bs, qt)
             except Exception as exc:  # baseline is informational; never lose the GPU line over it

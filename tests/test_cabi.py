@@ -442,8 +442,28 @@ def test_bench_contract_flags_and_algorithmic_bytes():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
                          timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in out.stdout
+
+
+def test_bench_dump_outputs_full_and_sampled(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 .npy files of the given shape under the byte limit; above it, the same seeded sample of the
+    flattened elements (ascending positions) on every call."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    y = torch.arange(3000, dtype=torch.float32).reshape(3, 1, 1000)
+    bench.dump_outputs(str(tmp_path / "a"), {"y": y})
+    a = np.load(tmp_path / "a" / "y.npy")
+    assert a.dtype == np.float32 and a.shape == (3, 1, 1000) and np.array_equal(a, y.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 500)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"y": y})
+    b, c = np.load(tmp_path / "b" / "y.npy"), np.load(tmp_path / "c" / "y.npy")
+    assert b.dtype == np.float32 and b.shape == (500,) and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and np.all(np.isin(b, y.float().numpy()))
 
 
 def test_native_dispatch_routing_constants_match_python():

@@ -2434,7 +2434,7 @@ def test_bench_multi_gpu_code_path_at_world_size_one():
 
     from conftest import ROOT
 
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--sharded-path", "--steps", "6", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--sharded-path", "--full", "--steps", "6", "--warmup", "2"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -2448,6 +2448,34 @@ def test_bench_multi_gpu_code_path_at_world_size_one():
     # the gather is fused into the gemv launches wherever the peer chain constructs and reproduces the separate form (it must, here)
     assert "fused into the gemv launches" in sc["gather"] and sc["fused_chain_not_used_because"] is None, (sc, r.stderr[-2000:])
     assert "sharded x1" in line["config"]["parallelism"]
+
+
+def test_bench_plain_run_dumps_what_the_timed_path_returned(tmp_path):
+    """A plain bench.py run reports the --steps it timed, prints the headline keys and none of --full's legs, and --dump-outputs
+    writes what the last timed step returned: the 128 layers' outputs, equal to the public op called eagerly on the same
+    seeded layers."""
+    import json
+    import subprocess
+    import sys
+
+    import bench
+    import bitsandbytes_amd as bnb
+    from conftest import ROOT
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0
+    for key in ("cpu_baseline", "headline_sweep_N4096_K4096", "grouped", "config3"):
+        assert key not in line, key
+    y = np.load(tmp_path / "y.npy")
+    assert y.dtype == np.float32 and y.shape == (bench.LAYERS, 1, 4096)
+    layers, x = bench.build_layers(torch.device(DEV), bench.LAYERS, 4096, 4096, 1, 64, "nf4", seed=1234)
+    want = torch.stack([bnb.matmul_4bit(x, q, st) for q, st in layers]).float().cpu().numpy()
+    assert np.array_equal(y, want)
 
 
 def test_sharded_linear4bit_over_rccl_two_ranks():

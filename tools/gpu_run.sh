@@ -12,7 +12,7 @@ if [[ "$WHAT" == *" tests "* ]]; then
   echo "=== pytest gpu"; timeout 1500 python -m pytest tests -m gpu -q --maxfail=40 -p no:cacheprovider > $OUT/pytest_gpu.log 2>&1; tail -12 $OUT/pytest_gpu.log
 fi
 if [[ "$WHAT" == *" bench "* ]]; then
-  echo "=== bench"; timeout 600 python bench.py --steps 6400 --warmup 640 --sweep 2>&1 | grep -v amdgpu.ids | tail -2 | tee $OUT/bench_n1.json
+  echo "=== bench"; timeout 600 python bench.py --steps 6400 --warmup 640 --full 2>&1 | grep -v amdgpu.ids | tail -2 | tee $OUT/bench_n1.json
 fi
 if [[ "$WHAT" == *" sweep "* ]]; then
   echo "=== sweep"; timeout 1200 python tools/sweep.py --mfma-only > $OUT/sweep.txt 2>&1; grep -v amdgpu.ids $OUT/sweep.txt | tail -120
@@ -22,7 +22,7 @@ if [[ "$WHAT" == *" sweepquick "* ]]; then
 fi
 if [[ "$WHAT" == *" prof "* ]]; then
   echo "=== rocprof"; R=$PWD; cd /tmp
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_bench -o bench -- python $R/bench.py --steps 640 --warmup 64 --no-cpu-baseline --no-pmc > $R/$OUT/rocprof_bench.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_bench -o bench -- python $R/bench.py --steps 640 --warmup 64 --full --no-cpu-baseline --no-pmc > $R/$OUT/rocprof_bench.log 2>&1
   cd $R; f=$(find $OUT/prof_bench -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -8 "$f" | cut -c1-220
 fi
 if [[ "$WHAT" == *" stream "* ]]; then
