@@ -347,3 +347,66 @@ def _(grad_out, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: st
     torch._check(len(shapeB) == 2, lambda: "shapeB must be [N, K]")
     torch._check(grad_out.shape[-1] == shapeB[0], lambda: f"grad_out inner dim ({grad_out.shape[-1]}) must equal N ({shapeB[0]})")
     return torch.empty((*grad_out.shape[:-1], shapeB[1]), dtype=grad_out.dtype, device=grad_out.device)
+
+
+# ---------------------------------------------------------------------------------------------- gemm_4bit_experts
+# Not a reference op: the expert-indexed fused matmul of a mixture-of-experts decode step,
+#   out[t, s, :] = x_row(t, s) @ dequantize_4bit(B)[ids[t, s]].T (+ bias[ids[t, s]])
+# B is ONE quantize_4bit result over a contiguous [E, N, K] tensor (shapeB), ids [T, S] (or flat [P]) int32 / int64 on the device and
+# read there only (no host synchronisation: the call can be captured in a hipGraph), A [T, K] (the slots of a token share its
+# activations) or [T, S, K] (one row per slot). An id outside [0, E) gives a row of zeros. Inference only: no autograd formula.
+# Statistics arguments as in bitsandbytes::gemm_4bit; with nested statistics the groups of 256 blocks run over the flat tensor.
+torch.library.define(
+    "bitsandbytes_amd::gemm_4bit_experts",
+    "(Tensor A, Tensor B, int[] shapeB, Tensor absmax, Tensor ids, int blocksize, str quant_type, Tensor? bias=None, "
+    "Tensor? absmax_8bit=None, Tensor? absmax_code=None, Tensor? absmax_offset=None) -> Tensor",
+)
+
+
+def _check_gemm_4bit_experts(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code, absmax_offset):
+    """Argument checks shared by the fake kernel and the device kernels; returns (E, N, K, per_slot)."""
+    torch._check(is_pow2_blocksize(blocksize), lambda: f"blocksize must be a power of two >= 32, got {blocksize}")
+    torch._check(quant_type in ("nf4", "fp4"), lambda: f"quant_type must be 'nf4' or 'fp4', got {quant_type!r}")
+    torch._check(len(shapeB) == 3, lambda: f"shapeB must be [E, N, K] (one quantize_4bit over the expert stack), got {list(shapeB)}")
+    E, N, K = (int(v) for v in shapeB)
+    torch._check(E > 0 and N > 0 and K > 0, lambda: f"shapeB must be positive, got {list(shapeB)}")
+    torch._check(A.dtype in _FLOAT_DTYPES, lambda: f"A must be a 16/32-bit float tensor, got {A.dtype}")
+    torch._check(ids.dtype in (torch.int32, torch.int64), lambda: f"ids must be int32 or int64, got {ids.dtype}")
+    torch._check(ids.dim() in (1, 2), lambda: f"ids must be [T, S] or flat [P], got {ids.dim()} dims")
+    torch._check(A.dim() in (2, 3), lambda: f"A must be [T, K] or [T, S, K], got {A.dim()} dims")
+    torch._check(
+        A.shape[-1] == K,
+        lambda: f"A inner dim ({A.shape[-1]}) must equal K = shapeB[2] ({K}); the [E, K, N] orientation (contraction over "
+                "the unpacked dimension) is not supported",
+    )
+    torch._check(K % blocksize == 0, lambda: f"K ({K}) must be a multiple of blocksize ({blocksize})")
+    torch._check(A.shape[0] == ids.shape[0], lambda: f"A has {A.shape[0]} tokens, ids {ids.shape[0]}")
+    per_slot = A.dim() == 3
+    if per_slot:
+        torch._check(ids.dim() == 2 and A.shape[1] == ids.shape[1], lambda: "A [T, S, K] needs ids [T, S] with the same S")
+    torch._check(ids.device == A.device and B.device == A.device, lambda: "A, B and ids must live on one device")
+    torch._check(B.numel() * B.element_size() * 2 == E * N * K, lambda: f"B holds {B.numel() * B.element_size() * 2} 4-bit values, shapeB {E * N * K}")
+    torch._check(absmax.dtype == torch.float32, lambda: f"absmax must be float32, got {absmax.dtype}")
+    blocks = E * N * K // blocksize
+    if absmax_8bit is None:
+        torch._check(absmax.numel() == blocks, lambda: f"absmax must hold {blocks} values, got {absmax.numel()}")
+    else:
+        torch._check(absmax_8bit.dtype == torch.uint8 and absmax_8bit.numel() == blocks, lambda: f"absmax_8bit must hold {blocks} uint8 codes")
+        torch._check(absmax.numel() == -(blocks // -256), lambda: f"nested absmax must hold {-(blocks // -256)} values (groups of 256 blocks)")
+        torch._check(absmax_code is not None and absmax_code.numel() == 256, lambda: "nested statistics need a 256-entry absmax_code")
+        torch._check(absmax_offset is not None and absmax_offset.numel() == 1, lambda: "nested statistics need absmax_offset")
+    if bias is not None:
+        torch._check(tuple(bias.shape) == (E, N), lambda: f"bias must be [E, N] = [{E}, {N}], got {tuple(bias.shape)}")
+        torch._check(bias.dtype == A.dtype, lambda: f"bias dtype ({bias.dtype}) must equal A's ({A.dtype})")
+    return E, N, K, per_slot
+
+
+def is_pow2_blocksize(blocksize: int) -> bool:
+    return isinstance(blocksize, int) and blocksize >= 32 and (blocksize & (blocksize - 1)) == 0
+
+
+@register_fake("bitsandbytes_amd::gemm_4bit_experts")
+def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str, bias=None, absmax_8bit=None, absmax_code=None,
+      absmax_offset=None):
+    _, N, _, _ = _check_gemm_4bit_experts(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code, absmax_offset)
+    return torch.empty((*ids.shape, N), dtype=A.dtype, device=A.device)

@@ -156,6 +156,42 @@ def matmul_4bit(
     return result
 
 
+def matmul_4bit_experts(
+    x: torch.Tensor,
+    packed: torch.Tensor,
+    quant_state: F.QuantState,
+    expert_ids: torch.Tensor,
+    bias: Optional[torch.Tensor] = None,
+):
+    """``y[t, s] = x_row(t, s) @ dequant(packed)[expert_ids[t, s]].T (+ bias[expert_ids[t, s]])`` in one launch - the expert
+    projections of a mixture-of-experts decode step. ``packed`` / ``quant_state``: ONE ``quantize_4bit`` over the fused
+    ``[E, N, K]`` expert tensor; ``expert_ids``: ``[T, S]`` (or flat ``[P]``) int32 / int64 ON THE DEVICE - their values are read
+    by the kernel only, so the call needs no host synchronisation and can be captured in a graph and replayed with other ids in
+    the same buffer; an id outside ``[0, E)`` gives a row of zeros. ``x``: ``[T, K]`` (the slots of a token share its
+    activations: gate / up) or ``[T, S, K]`` (one row per slot: down). ``bias``: optional ``[E, N]``. Returns ``[T, S, N]``
+    (``[P, N]`` for flat ids). Inference only: there is no autograd formula."""
+    if quant_state is None:
+        raise ValueError("quant_state is required")
+    if len(quant_state.shape) != 3:
+        raise ValueError(f"matmul_4bit_experts: quant_state.shape must be 3D [E, N, K], got {list(quant_state.shape)}")
+    if torch.is_grad_enabled() and (x.requires_grad or (bias is not None and bias.requires_grad)):
+        raise RuntimeError("matmul_4bit_experts is inference only (no autograd formula): call it under torch.no_grad() "
+                           "or with detached inputs")
+    if x.shape[-1] != quant_state.shape[2]:
+        raise ValueError(
+            f"matmul_4bit_experts: x inner dim ({x.shape[-1]}) must equal quant_state.shape[2] ({quant_state.shape[2]}); "
+            "expert tensors in [E, K, N] orientation (contraction over the unpacked dimension) are not supported")
+    packed = packed.view(-1, 1)
+    op = torch.ops.bitsandbytes_amd.gemm_4bit_experts.default
+    if not quant_state.nested:
+        return op(x, packed, quant_state.shape, quant_state.absmax, expert_ids, quant_state.blocksize, quant_state.quant_type,
+                  bias=bias)
+    if quant_state.state2.blocksize != 256:
+        raise NotImplementedError("nested quantization with state2.blocksize != 256 is not supported")
+    return op(x, packed, quant_state.shape, quant_state.state2.absmax, expert_ids, quant_state.blocksize, quant_state.quant_type,
+              bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code, absmax_offset=quant_state.offset)
+
+
 def matmul_4bit_grouped(A: torch.Tensor, weights, quant_states, biases=None, outs=None):
     """``[matmul_4bit(A, B_i, state_i, bias=bias_i) for i]`` for 4-bit weights that share their input - the Q/K/V
     projections of an attention block, the gate/up projections of an MLP. On MI355X a decode-sized batch (M <= 4) is

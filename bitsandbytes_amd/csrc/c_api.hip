@@ -70,6 +70,12 @@ void gemm_4bit_grad_input(int dtype, const void* G, const uint8_t* B, const floa
                           const float* absmax_code, const float* absmax_offset, void* out, int M, int N, int K, int blocksize,
                           int quant_type, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+// gemm4_experts.hip
+bool gemm_4bit_experts_supported(int dtype, long E, long N, long K, int blocksize);
+void gemm_4bit_experts(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
+                       const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes,
+                       void* out, long P, int S, int E, int N, int K, int blocksize, int quant_type, hipStream_t stream);
+
 namespace {
 
 // M at or below which the streaming dot kernel is used (its activations live in registers: 32 fp32 per row and
@@ -380,6 +386,18 @@ size_t bnb_mi355x_gemm_4bit_workspace_bytes(int kernel, int dtype, int M, int N,
 }
 int bnb_mi355x_last_gemm_kernel(void) { return g_last_gemm_kernel; }
 
+// ------------------------------------------------------------------ expert-indexed gemm_4bit (MoE decode)
+void bnb_mi355x_gemm_4bit_experts(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax,
+                                  const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, const void* bias,
+                                  const void* ids, int index_bytes, void* out, long P, int slots, int E, int N, int K, int blocksize,
+                                  int quant_type, bnb_stream_t s) {
+    gemm_4bit_experts(dtype, A, a_slot_stride, B, absmax, absmax_8bit, absmax_code, absmax_offset, bias, ids, index_bytes, out, P, slots,
+                      E, N, K, blocksize, quant_type, S(s));
+}
+int bnb_mi355x_gemm_4bit_experts_supported(int dtype, int E, int N, int K, int blocksize) {
+    return gemm_4bit_experts_supported(dtype, E, N, K, blocksize) ? 1 : 0;
+}
+
 // ------------------------------------------------------------------ peer chain (the all-gather fused into the gemv launches)
 static uint32_t peer_chain_spin_bound() {
     // a re-fetch is s_sleep 4 (256 cycles) + a system-scope load round trip: ~1 us. BNB_MI355X_PEER_WAIT_POLLS as in peer_gather.hip
@@ -484,7 +502,7 @@ void bnb_mi355x_set_stamp_buffer(void* device_u64_buffer) {
     (void)device_u64_buffer; // the product library carries no stamp code: the call is accepted and ignored
 #endif
 }
-const char* bnb_mi355x_version(void) { return "bitsandbytes_amd 0.1.0 gfx950"; }
+const char* bnb_mi355x_version(void) { return "bitsandbytes_amd 0.1.1 gfx950"; }
 
 #pragma GCC visibility pop
 } // extern "C"

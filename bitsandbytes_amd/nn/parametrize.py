@@ -15,6 +15,7 @@ import torch.nn as nn
 import torch.nn.utils.parametrize as P
 
 from .. import functional as F
+from ..autograd._functions import matmul_4bit_experts as _matmul_4bit_experts
 
 
 class Bnb4bitParametrization(nn.Module):
@@ -87,6 +88,47 @@ def _disable_parametrization_cache(module: nn.Module, inputs: tuple[Any, ...], o
     P._cache_enabled = max(0, P._cache_enabled - 1)
     if not P._cache_enabled:
         P._cache = {}
+
+
+def matmul_4bit_experts(module: nn.Module, param_name: str, x: torch.Tensor, expert_ids: torch.Tensor,
+                        bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The expert projections of a decode step on a parametrized ``[E, N, K]`` expert tensor WITHOUT the dequantizing read of the
+    attribute: ``y[t, s] = x_row(t, s) @ W[expert_ids[t, s]].T (+ bias[expert_ids[t, s]])`` from the packed bytes, one launch
+    (:func:`bitsandbytes_amd.matmul_4bit_experts`; ``x`` is ``[T, K]`` or ``[T, S, K]``, ``expert_ids`` ``[T, S]`` on the device,
+    an id outside ``[0, E)`` gives a row of zeros). Where the kernel does not serve the geometry the dequantized attribute is
+    indexed and multiplied instead - also without looking at the ids on the host. Inference only."""
+    if not P.is_parametrized(module, param_name):
+        raise ValueError(f"'{param_name}' is not a parametrized parameter of the module")
+    plist = module.parametrizations[param_name]
+    hook = next((h for h in plist if isinstance(h, Bnb4bitParametrization)), None)
+    if hook is None or hook.quant_state is None:
+        raise ValueError(f"'{param_name}' carries no 4-bit parametrization")
+    state = hook.quant_state
+    if len(state.shape) != 3:
+        raise ValueError(f"matmul_4bit_experts: '{param_name}' must be a 3D [E, N, K] expert tensor, got {list(state.shape)}")
+    E, N, K = (int(v) for v in state.shape)
+    if x.shape[-1] != K:
+        raise ValueError(f"matmul_4bit_experts: x inner dim ({x.shape[-1]}) must equal K ({K}); expert tensors in [E, K, N] "
+                         "orientation are not supported")
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("matmul_4bit_experts is inference only (no autograd formula): call it under torch.no_grad()")
+    from ..backends.hip import gemm_4bit_experts_supported
+
+    packed = plist.original
+    served = (x.is_cuda and gemm_4bit_experts_supported(x.dtype, E, N, K, state.blocksize)
+              and (not state.nested or state.state2.blocksize == 256) and packed.data_ptr() % 16 == 0)
+    if served:
+        return _matmul_4bit_experts(x, packed.data, state, expert_ids, bias=bias)
+    # unfused: the dequantized stack, gathered per pair (ids clamped for the gather, masked rows zeroed afterwards)
+    with torch.no_grad():
+        W = getattr(module, param_name).to(x.dtype)
+        valid = (expert_ids >= 0) & (expert_ids < E)
+        safe = expert_ids.clamp(0, E - 1).long()
+        xs = x if x.dim() == expert_ids.dim() + 1 else x.unsqueeze(-2).expand(*expert_ids.shape, K)
+        y = torch.matmul(W[safe], xs.unsqueeze(-1)).squeeze(-1)
+        if bias is not None:
+            y = y + bias[safe]
+        return y * valid.unsqueeze(-1).to(y.dtype)
 
 
 class _StateDictHook:

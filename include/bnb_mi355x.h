@@ -142,10 +142,28 @@ int bnb_mi355x_gemm_4bit_route(int kernel, int dtype, int M, int N, int K, int b
 /* Which kernel family the calling thread's LAST gemm_4bit / gemv_4bit call (any entry point) launched: 0 none yet, 1 streaming
  * kernel (gemv4_stream_kernel), 2 generic scalar kernel (odd shapes), 3 register-transposed MFMA kernel (gemm4_mfma_rt_kernel),
  * 4 producer/consumer MFMA kernel (gemm4_mfma_pc_kernel), 6 K-quarter MFMA kernel (gemm4_mfma_kq_kernel),
- * 7 streaming MFMA kernel (gemm4_mfma_sm_kernel: 2 ... 16 rows, one persistent workgroup per CU). Debug / test query:
+ * 7 streaming MFMA kernel (gemm4_mfma_sm_kernel: 2 ... 16 rows, one persistent workgroup per CU), 9 expert-indexed kernel
+ * (gemm4_experts_kernel: bnb_mi355x_gemm_4bit_experts). Debug / test query:
  * a test that forces a kernel with bnb_mi355x_set_tuning asserts here that it ran (a geometry the forced kernel does not
  * serve falls back to another family by design). */
 int bnb_mi355x_last_gemm_kernel(void);
+
+/* Expert-indexed gemm_4bit for mixture-of-experts decode, ONE launch for any id pattern:
+ *   out[p, 0:N] = x_row(p) * dequant(B[ids[p]])^T (+ bias[ids[p], 0:N])        p = 0 .. P-1, P = T * S (token, slot) pairs
+ * B / absmax (/ absmax_8bit, absmax_code, absmax_offset: nested statistics, as in cgemm_4bit_*) are the result of ONE quantize_4bit
+ * over a contiguous [E, N, K] tensor: expert e is rows e * N .. (e + 1) * N - 1 of the flat [E * N, K] matrix, and the second-level
+ * groups of 256 blocks run over the flat tensor (they may straddle experts). ids: P values on the DEVICE, int32 (index_bytes 4) or
+ * int64 (8), read by the kernel only - the host never looks at them, so the call needs no synchronisation and can be captured in a
+ * hipGraph and replayed with other ids in the same buffer. An id outside [0, E) gives a row of zeros (no bias) and reads no weight.
+ * x_row(p) = A + p * K when a_slot_stride == K (A is [P, K]: one activation row per pair) and A + (p / S) * K when a_slot_stride == 0
+ * (A is [P / S, K]: the S slots of a token share its row). bias: NULL or [E, N] of A's dtype. dtype: 0 = fp32, 1 = fp16, 2 = bf16;
+ * fp32 accumulation, one rounding. Workgroups of experts nobody selected leave after reading the id list; an expert's weights are
+ * streamed once per four pairs that select it; every output element is summed in a fixed order that does not depend on the other
+ * pairs of the call (no atomics). A, B and out must be 16-byte aligned. P <= 0 returns without a launch. A geometry for which
+ * bnb_mi355x_gemm_4bit_experts_supported (pure host logic, no device needed) answers 0 - K not a multiple of blocksize, blocksize not
+ * a power of two >= 32, K > 131072, E > 65535 - terminates like every failed launch of this ABI: ask first. */
+void bnb_mi355x_gemm_4bit_experts(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes, void* out, long P, int S, int E, int N, int K, int blocksize, int quant_type, bnb_stream_t stream);
+int bnb_mi355x_gemm_4bit_experts_supported(int dtype, int E, int N, int K, int blocksize);
 
 /* Grouped gemm_4bit: `count` weight matrices applied to the SAME activations A[M, K] in one launch -
  *   out[i][M, N[i]] = A * dequant(B[i])^T (+ bias[i])        i = 0 .. count-1
