@@ -106,6 +106,7 @@ def _declare(dll: ct.CDLL) -> None:
     # (bufs[], epoch_word, world, rank, dtype, out, nvalues, max_values, epoch_offset, stream)
     sig(["bnb_mi355x_peer_chain_read"], [_VOID_P, _VOID_P, _I32, _I32, _I32, _VOID_P, _I32, ct.c_long, _I32, _VOID_P])
     sig(["bnb_mi355x_set_stream_tuning"], [_I32] * 5)
+    sig(["bnb_mi355x_gemv_4bit_stream_exact"], [_I32] * 6, _I32)
     sig(["bnb_mi355x_set_tuning"], [_I32] * 4)
     sig(["bnb_mi355x_set_stamp_buffer"], [_VOID_P])
     sig(["bnb_mi355x_version"], [], ct.c_char_p)
@@ -142,5 +143,5 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_peer_close", "bnb_mi355x_peer_allgather", "bnb_mi355x_peer_status",
        "bnb_mi355x_peer_chain_buffer_bytes", "bnb_mi355x_peer_chain_alloc", "bnb_mi355x_gemv_4bit_peer_serves", "bnb_mi355x_gemv_4bit_peer",
        "bnb_mi355x_peer_chain_read",
-       "bnb_mi355x_set_stream_tuning", "bnb_mi355x_set_tuning", "bnb_mi355x_set_stamp_buffer", "bnb_mi355x_version"]
+       "bnb_mi355x_set_stream_tuning", "bnb_mi355x_gemv_4bit_stream_exact", "bnb_mi355x_set_tuning", "bnb_mi355x_set_stamp_buffer", "bnb_mi355x_version"]
 )

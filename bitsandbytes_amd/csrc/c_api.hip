@@ -32,6 +32,7 @@ bool gemv_4bit_grouped(int dtype, const void* A, int count, const uint8_t* const
                        void* const* out, const void* const* bias, const int* N, int M, int K, int blocksize, int quant_type,
                        hipStream_t stream);
 void gemv_4bit_stream_tuning(int ns, int sw, int rows_per_wg, int nt, int waves);
+bool gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, bool nested);
 bool gemv_4bit_peer(void* const* bufs, void* epoch_word, int world, int rank, int dtype, const void* A, const uint8_t* B, const float* absmax,
                     const uint8_t* absmax8, const float* absmax_code, const float* absmax_offset, const void* bias, void* out_local,
                     int ns, int K, int blocksize, int quant_type, int mode, long max_values, int wg_limit, uint32_t epoch_offset,
@@ -494,6 +495,9 @@ void bnb_mi355x_set_tuning(int reserved0, int reserved1, int mfma_knob0, int mfm
 }
 void bnb_mi355x_set_stream_tuning(int ring_depth, int segments, int rows_per_workgroup, int nontemporal, int waves) {
     gemv_4bit_stream_tuning(ring_depth, segments, rows_per_workgroup, nontemporal, waves);
+}
+int bnb_mi355x_gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, int nested) {
+    return gemv_4bit_stream_exact(dtype, M, N, K, blocksize, nested != 0) ? 1 : 0;
 }
 void bnb_mi355x_set_stamp_buffer(void* device_u64_buffer) {
 #ifdef BNB_PROFILING

@@ -377,6 +377,11 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
     // barrier - then behind the wait for the fragments - held every wavefront until then) delays only itself. The ring's second
     // stage is requested behind the barrier: 32 KiB of weight requests per CU up front fill the memory pipeline, 64 KiB only
     // congest the address pipeline in front of the late wavefronts' first requests.
+    // The epilogue's pointers come from the kernarg segment beyond the preloaded dwords: a cold scalar load. Left to the compiler it
+    // sat behind the LAST barrier, where nothing hides it - the storing wavefronts are all that is left of the kernel. Pinned in
+    // SGPRs here, it returns under the first weight bytes. (Grouped launches select a member's pointers by block: left as they are.)
+    if constexpr (!GROUPED)
+        asm volatile("" : "+s"(g_out), "+s"(g_bias));
     __syncthreads();
     BNB_SM_STAMP(5)
     if constexpr (!SINGLE) {

@@ -60,7 +60,9 @@ enum StreamFlags : int {
     kNT = 8,      // non-temporal weight loads
     kGrouped = 16, // several matrices over one concatenated row space
     kMulti = 32,   // rows longer than the workgroup's segment columns: several phases (a loop around the whole body)
-    kPeer = 64     // "peer chain" form (M = 1): x taken from / y delivered to the ranks' exchange buffers - see PeerChain
+    kPeer = 64,    // "peer chain" form (M = 1): x taken from / y delivered to the ranks' exchange buffers - see PeerChain
+    kExact = 128,  // exact geometry (M = 1, K = 4096: SW = 2, G = 8, every row, lane and ring position valid): see launch_one
+    kLateArgs = 256 // sweep-only: the epilogue's out / bias pointers loaded where they are used (the form up to round 6; A/B runs)
 };
 
 // One weight matrix of a launch.
@@ -213,6 +215,16 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     constexpr bool MULTI = FLAGS & kMulti;
     constexpr bool PEER = (FLAGS & kPeer) != 0;
     static_assert(!PEER || (MB == 1 && !MULTI && !GROUPED && WAVES == 16), "the peer-chain form is the M = 1, single-phase kernel");
+    // Exact geometry: the host selects this instance only when K = kExactSW * 2048, M = 1 and the rows divide evenly over workgroups
+    // and row groups with at least one ring position each (exact_geometry()). Everything the general instance decides at run time in
+    // front of its first weight request - bounds of the row list, of the row, of the segment, the division of the wavefront id - is a
+    // constant here: the scalar unit is shared by 16 wavefronts, and every instruction in front of the ring delays the whole stream.
+    constexpr bool EXACT = (FLAGS & kExact) != 0;
+    constexpr int kExactSW = 2;
+    static_assert(!EXACT || (MB == 1 && !MULTI && !GROUPED && !PEER && !CODEPTR && WAVES == 16 && TypeInfo<T>::bytes == 2),
+                  "the exact-geometry form is the M = 1, single-phase kernel for 16-bit activations");
+    // the epilogue's pointers are requested in the prologue (see there); kLateArgs keeps the old form for A/B runs
+    constexpr bool EARLY_ARGS = !GROUPED && !(FLAGS & kLateArgs);
     constexpr int THREADS = WAVES * 64;
     constexpr int TB = TypeInfo<T>::bytes;
     constexpr int CH = 2 * TB;  // 16-byte chunks of activations per lane and segment (= 1-KiB DMA pieces per segment)
@@ -229,21 +241,23 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int K = hot_K;
+    const int K = EXACT ? kExactSW * kSegK : hot_K;
     // Single-phase instances have no loop around the body: in the looped form LLVM hoists every phase-invariant
     // address computation in front of the loop - i.e. in front of the first loads.
-    const int M = hot_packed & 0x3FFFF, bs_shift = (hot_packed >> 18) & 31, P = MULTI ? (hot_packed >> 23) & 511 : 1;
-    const int R = hot_geom & 0xFFFF, SW = (hot_geom >> 16) & 31, G = (hot_geom >> 21) & 31;
-    const int S = (K + kSegK - 1) >> 11;
+    const int M = EXACT ? 1 : hot_packed & 0x3FFFF, bs_shift = (hot_packed >> 18) & 31, P = MULTI ? (hot_packed >> 23) & 511 : 1;
+    const int R = hot_geom & 0xFFFF, SW = EXACT ? kExactSW : (hot_geom >> 16) & 31, G = EXACT ? WAVES / kExactSW : (hot_geom >> 21) & 31;
+    const int S = EXACT ? kExactSW : (K + kSegK - 1) >> 11;
     const int rows_total = GROUPED ? p.rows_total : hot_N;
     const int row_begin = blockIdx.x * R;
-    if (row_begin >= rows_total)
-        return;
-    const int nrows = (rows_total - row_begin < R) ? rows_total - row_begin : R;
-    const int m0 = blockIdx.y * MB;
+    if constexpr (!EXACT) {
+        if (row_begin >= rows_total)
+            return;
+    }
+    const int nrows = (EXACT || rows_total - row_begin >= R) ? R : rows_total - row_begin;
+    const int m0 = EXACT ? 0 : blockIdx.y * MB;
     // wave -> (segment column sw, row group g): g = wave / SW by a host-made reciprocal (exact for wave < 16 <= 256 / SW)
-    const int g = (wave * hot_inv) >> 8;
-    const int sw = wave - g * SW;
+    const int g = EXACT ? wave / kExactSW : (wave * hot_inv) >> 8;
+    const int sw = EXACT ? wave % kExactSW : wave - g * SW;
 #ifdef BNB_PROFILING
     if (p.dbg && lane == 0)
         BNB_ST_DBG_BASE[(static_cast<long>(blockIdx.x) * WAVES + wave) * 16 + 13] = __builtin_amdgcn_s_memrealtime();
@@ -291,6 +305,17 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     auto issue_x = [&](int ph) {
         if (wave >= BUILDERS)
             return;
+        if constexpr (EXACT) {
+            // SW * CH = 8 pieces of 1 KiB, one per builder wavefront: piece w = bytes [1024 w, 1024 w + 1024) of x, and - slot
+            // s = 64 pc + lane, chunk = s ^ f(s >> 2) with f(l') = (l' >> 2) & 3 - lane l copies chunk 64 pc + (l ^ ((l >> 4) & 3)):
+            // the general loop's addresses, with the piece in the scalar base and the swizzle in a 32-bit lane offset
+            static_assert(kExactSW * CH == BUILDERS && CH == 4, "one piece per builder wavefront");
+            const unsigned char* const src = reinterpret_cast<const unsigned char*>(A) + wave * 1024;
+            const uint32_t voff = static_cast<uint32_t>(lane ^ ((lane >> 4) & 3)) * 16u;
+            const uint32_t dst = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_ptr)ximg)) + static_cast<uint32_t>(wave * 1024);
+            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(src), "s"(dst) : "memory", "m0");
+            return;
+        }
         const int segs = (S - ph * SW < SW) ? S - ph * SW : SW;
         const int pieces = MB * segs * CH;
         for (int piece = wave; piece < pieces; piece += BUILDERS) {
@@ -347,8 +372,9 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     // wave-uniform mask that is all-ones-ish for an item past the end of the list - branch-free (written as selects,
     // hipcc turned the predicate into two exec-masked copies of every load).
     uint32_t lane_mask = kOob; // 0 for lanes inside the row, kOob otherwise
-    auto issue = [&](Stage& s, int i) {
-        const bool valid = g + i * G < rl_end; // wave-uniform
+    auto issue = [&](Stage& s, int i, auto first) {
+        // (exact geometry: the NS ring positions of the prologue exist on every wavefront)
+        const bool valid = (EXACT && decltype(first)::value) || g + i * G < rl_end; // wave-uniform
         const int grow = valid ? row_begin + g + i * G : 0;
         const uint32_t inval = (valid ? 0u : kOob) | lane_mask;
         const uint8_t* Bp = hot_B;
@@ -377,7 +403,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
             uint32_t k_last = static_cast<uint32_t>(seg * kSegK + kSegK - 1);
             k_last = k_last < static_cast<uint32_t>(K) ? k_last : static_cast<uint32_t>(K - 1);
             const uint32_t e1 = static_cast<uint32_t>(row) * static_cast<uint32_t>(K) + k_last;
-            const uint32_t ga = valid && seg < S ? (e0 >> bs_shift) >> 8 : 0u, gb = valid && seg < S ? (e1 >> bs_shift) >> 8 : 0u;
+            const uint32_t ga = valid && (EXACT || seg < S) ? (e0 >> bs_shift) >> 8 : 0u, gb = valid && (EXACT || seg < S) ? (e1 >> bs_shift) >> 8 : 0u;
             s.grp = ga;
             // (constant address space: the statistics are read-only for the kernel, a uniform index then compiles to s_load_dword;
             // through the generic pointer hipcc emits a vector load per lane)
@@ -410,7 +436,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
             }
             // lanes past the end of the row hold zeros (their weight loads are out of range, their scale is forced to 0);
             // only the last segment of a row whose length is not a multiple of 2048 has such lanes
-            if ((seg + 1) * kSegK > K) {
+            if (!EXACT && (seg + 1) * kSegK > K) {
 #pragma unroll
                 for (int e = 0; e < 32; ++e)
                     xs[e] = k_ok ? xs[e] : 0.0f;
@@ -481,7 +507,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
             } else {
                 scale = s.s;
             }
-            scale_u[u] = k_ok ? scale : 0.0f;
+            scale_u[u] = (EXACT || k_ok) ? scale : 0.0f;
             if constexpr (PRESCALE) {
                 const f32x2 sc2 = {scale_u[u], scale_u[u]};
 #pragma unroll
@@ -517,7 +543,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
 #pragma unroll
         for (int u = 0; u < IL; ++u) {
             const int rl = g + (i0 + u) * G;
-            if (lane == 0 && rl < rl_end) {
+            if (lane == 0 && (EXACT || rl < rl_end)) {
 #pragma unroll
                 for (int m = 0; m < MB; ++m)
                     part[(rl * S + seg) * MB + m] = v[u * MB + m];
@@ -525,6 +551,12 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
         }
     };
 
+    // The epilogue's pointers (out, bias of the one matrix): their kernarg load is this kernel's first touch of the kernarg segment
+    // beyond the preloaded dwords - a cold miss of several hundred cycles. Left to the compiler it sat behind the FINAL barrier, where
+    // nothing hides it: every other wavefront has ended and the kernel cannot end before the storing wavefront has loaded, summed and
+    // stored. Requested here behind the ring issue and pinned in SGPRs in front of the first barrier, it runs under the latency of
+    // the first weight bytes. (Grouped launches pick the matrix per row: left as they are.)
+    [[maybe_unused]] uintptr_t ep_out = 0, ep_bias = 0;
     uint32_t epoch = 0;     // (peer chain) the exchange this launch consumes
     uint32_t epoch_raw = 0; // ... the epoch word as loaded
     for (int ph = 0; ph < P; ++ph) {
@@ -558,13 +590,13 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
         if (ph == 0)
             BNB_ST_STAMP(10)
         seg = ph * SW + sw;
-        rl_end = (g < G && seg < S) ? nrows : 0;
+        rl_end = (EXACT || (g < G && seg < S)) ? nrows : 0;
         k0 = static_cast<uint32_t>(seg * kSegK + lane * 32);
-        k_ok = (seg < S) && (k0 < static_cast<uint32_t>(K));
+        k_ok = EXACT || ((seg < S) && (k0 < static_cast<uint32_t>(K)));
         lane_mask = k_ok ? 0u : kOob;
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
-            issue(st[j], j);
+            issue(st[j], j, std::true_type{});
             __builtin_amdgcn_sched_barrier(0); // keep the queue in stage order: (weights, scale) of stage 0, of stage 1, ...
         }
         if constexpr (PEER) {
@@ -581,6 +613,11 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
             // everything below is written AFTER the first loads in program order and fenced there: the scalar unit
             // is shared by the CU's 16 wavefronts, so nothing that is not needed for the loads may run before them
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (EARLY_ARGS) {
+                ep_out = reinterpret_cast<uintptr_t>(p.mat[0].out);
+                ep_bias = reinterpret_cast<uintptr_t>(p.mat[0].bias);
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
         // (peer chain, x from the exchange: the wavefronts that start FIRST fetch x - it is the longest pole in front of the barrier -
         // and the table is built by the second half of the workgroup, tid_b = the builder's index among the builders)
@@ -679,6 +716,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
                 }
             }
         }
+        if constexpr (EARLY_ARGS) {
+            if (ph == 0)
+                asm volatile("" : "+s"(ep_out), "+s"(ep_bias)); // (opaque: the values live in SGPRs from here - not re-loaded behind the last barrier)
+        }
         __syncthreads();
         if (ph == 0)
             BNB_ST_STAMP(3)
@@ -697,7 +738,8 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
         // (4) rounds of NS items, IL at a time. While another round follows, the refill of a stage is issued right
         // after the stage was consumed - valid or not, see above; the last round (peeled) consumes without refilling.
         int base = 0;
-        for (; g + (base + NS) * G < rl_end; base += NS) {
+        // (exact geometry: R is a multiple of G - every wavefront has R / G items, one trip count for the workgroup)
+        for (; EXACT ? (base + NS) * G < R : g + (base + NS) * G < rl_end; base += NS) {
 #pragma unroll
             for (int j = 0; j < NS; j += IL) {
                 compute(j, base + j);
@@ -705,12 +747,12 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
                     BNB_ST_STAMP(5)
 #pragma unroll
                 for (int u = 0; u < IL; ++u)
-                    issue(st[j + u], base + j + u + NS);
+                    issue(st[j + u], base + j + u + NS, std::false_type{});
             }
         }
 #pragma unroll
         for (int j = 0; j < NS; j += IL) {
-            if (g + (base + j) * G < rl_end)
+            if (EXACT ? (base + j) * G < R : g + (base + j) * G < rl_end)
                 compute(j, base + j);
             if (ph == 0 && base == 0 && j == 0)
                 BNB_ST_STAMP(5)
@@ -741,12 +783,14 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
             mi = mat_of(grow);
             row = grow - p.mat[mi].row_start;
         }
-        const T* bias = static_cast<const T*>(p.mat[mi].bias);
+        const T* bias = EARLY_ARGS ? reinterpret_cast<const T*>(ep_bias) : static_cast<const T*>(p.mat[mi].bias);
+        T* const out = EARLY_ARGS ? reinterpret_cast<T*>(ep_out) : static_cast<T*>(p.mat[mi].out);
+        const int out_n = GROUPED ? p.mat[mi].N : hot_N; // (one matrix: its N is the preloaded row count)
         const float b = bias ? static_cast<float>(bias[row]) : 0.0f;
         const T tv = static_cast<T>(v + b);
         if constexpr (PEER) {
-            if (p.mat[mi].out != nullptr)
-                static_cast<T*>(p.mat[mi].out)[row] = tv;
+            if (out != nullptr)
+                out[row] = tv;
             if (p.peer.mode & 2) {
                 // (rows come in pairs: the host keeps ns and the rows per workgroup even, so a thread and its neighbour are in the
                 // loop together and the even one stores both values)
@@ -808,7 +852,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
                 }
             }
         } else {
-            static_cast<T*>(p.mat[mi].out)[static_cast<long>(m0 + m) * p.mat[mi].N + row] = tv;
+            out[static_cast<long>(m0 + m) * out_n + row] = tv;
         }
     }
     BNB_ST_STAMP(8)
@@ -941,21 +985,54 @@ thread_local StreamTuning g_tune;
 constexpr int kRing = 2;
 constexpr int ring_depth(int mb, int waves) { return (mb == 1 && waves == 8) ? 4 : kRing; }
 
+// The exact-geometry instance (kExact) serves a launch whose geometry has nothing to decide at run time: one activation row, one
+// phase, K = 2 x 2048 in two segment columns (SW = 2, G = 8), every workgroup full (rows_total % R == 0), every row group with
+// the same number of rows (R % G == 0) and at least one ring of them (R >= NS x G: the prologue's NS requests are all real).
+// 4096 x 4096 (R = 16) and 14336 x 4096 (R = 56) on 256 CUs; 11008 x 4096 (R = 43) and every other K keep the general instance.
+constexpr int kExactSegments = 2;
+bool exact_geometry(const Geometry& ge, int M, int rows_total, int K, int ns) {
+    return M == 1 && ge.P == 1 && K == kExactSegments * kSegK && ge.SW == kExactSegments && ge.G == 16 / kExactSegments &&
+           rows_total % ge.R == 0 && ge.R % ge.G == 0 && ge.R >= ns * ge.G;
+}
+// instances that have an exact-geometry twin: 16-bit activations, MB = 1, 16 wavefronts, the production ring, literal tables, fp32
+// absmax. (Nested statistics: the exact form was built and measured BEHIND the general one at 4096^2 - FP4 bs 128 nested 4.50 against
+// 4.36 us - and is not instantiated: DESIGN 6b.)
+template <typename T, int MB, int WAVES, int NS, int FLAGS> constexpr bool has_exact_twin() {
+    return TypeInfo<T>::bytes == 2 && MB == 1 && WAVES == 16 && NS == kRing && (FLAGS & ~kFp4) == kNT;
+}
+// stream tuning knob `nt`, values above 1 (A/B of the fixed-cost levers, tools/stream_fixed_cost_ab.py): 2 = the general instance where
+// the exact one would be selected, 3 = the general instance with the epilogue's pointers loaded late (bf16, NF4 fp32-absmax and
+// FP4 nested only: the two sweep instances)
+constexpr int kTuneGeneral = 2, kTuneLateArgs = 3;
+
 template <typename T, int MB, int WAVES, int NS, int FLAGS> void launch_one(const StreamArgs& a, hipStream_t stream) {
     const Geometry ge = make_geometry(a.rows_total, a.K, MB, WAVES, TypeInfo<T>::bytes, (FLAGS & kGrouped) != 0, g_tune.sw.load(std::memory_order_relaxed),
                                       g_tune.rows.load(std::memory_order_relaxed));
     dim3 grid(ge.grid_x, (a.M + MB - 1) / MB);
     const StreamMat& m0 = a.mat[0];
-    if constexpr (!(FLAGS & kGrouped) && NS == ring_depth(MB, WAVES) && !(MB == 2 && WAVES == 16)) {
-        if (ge.P > 1) {
-            auto kern = gemv4_stream_kernel<T, MB, WAVES, NS, FLAGS | kMulti>;
-            static LdsLimit lds_limit;
-            ensure_dynamic_lds(lds_limit, reinterpret_cast<const void*>(kern), ge.lds);
-            hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), ge.lds, stream, a.A, m0.B, m0.absmax, m0.absmax8, m0.N, a.K,
-                               (a.M & 0x3FFFF) | (a.bs_shift << 18) | (ge.P << 23),
-                               ge.R | (ge.SW << 16) | (ge.G << 21), (256 + ge.SW - 1) / ge.SW, a);
-            return;
+    // the one launch of this function: every instance takes the same arguments
+    auto go = [&](auto kern) {
+        static LdsLimit lds_limit; // (one per kernel instance: the lambda's call operator is instantiated per `kern` type)
+        ensure_dynamic_lds(lds_limit, reinterpret_cast<const void*>(kern), ge.lds);
+        hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), ge.lds, stream, a.A, m0.B, m0.absmax, m0.absmax8, m0.N, a.K,
+                           (a.M & 0x3FFFF) | (a.bs_shift << 18) | (ge.P << 23),
+                           ge.R | (ge.SW << 16) | (ge.G << 21), (256 + ge.SW - 1) / ge.SW, a);
+    };
+    constexpr bool kLateTwin = std::is_same<T, bf16>::value && MB == 1 && WAVES == 16 && NS == kRing && (FLAGS == kNT || FLAGS == (kNT | kFp4 | kNested));
+    if constexpr (has_exact_twin<T, MB, WAVES, NS, FLAGS>() || kLateTwin) {
+        const int knob = g_tune.nt.load(std::memory_order_relaxed);
+        if constexpr (kLateTwin) {
+            if (knob == kTuneLateArgs && ge.P == 1)
+                return go(gemv4_stream_kernel<T, MB, WAVES, NS, FLAGS | kLateArgs>);
         }
+        if constexpr (has_exact_twin<T, MB, WAVES, NS, FLAGS>()) {
+            if (knob != kTuneGeneral && knob != kTuneLateArgs && exact_geometry(ge, a.M, a.rows_total, a.K, NS))
+                return go(gemv4_stream_kernel<T, MB, WAVES, NS, FLAGS | kExact>);
+        }
+    }
+    if constexpr (!(FLAGS & kGrouped) && NS == ring_depth(MB, WAVES) && !(MB == 2 && WAVES == 16)) {
+        if (ge.P > 1)
+            return go(gemv4_stream_kernel<T, MB, WAVES, NS, FLAGS | kMulti>);
     }
     if (ge.P > 1) {
         // sweep-only instances exist single-phase only; grouped launches are refused earlier (grouped_fits)
@@ -964,12 +1041,7 @@ template <typename T, int MB, int WAVES, int NS, int FLAGS> void launch_one(cons
         fprintf(stderr, "bitsandbytes_amd: gemv_4bit: internal error, multi-phase geometry on a single-phase instance\n");
         exit(1);
     }
-    auto kern = gemv4_stream_kernel<T, MB, WAVES, NS, FLAGS>;
-    static LdsLimit lds_limit;
-    ensure_dynamic_lds(lds_limit, reinterpret_cast<const void*>(kern), ge.lds);
-    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), ge.lds, stream, a.A, m0.B, m0.absmax, m0.absmax8, m0.N, a.K,
-                       (a.M & 0x3FFFF) | (a.bs_shift << 18) | (ge.P << 23),
-                       ge.R | (ge.SW << 16) | (ge.G << 21), (256 + ge.SW - 1) / ge.SW, a);
+    go(gemv4_stream_kernel<T, MB, WAVES, NS, FLAGS>);
 }
 
 // The sweep-only variants (other ring depths, default cache policy) exist for ONE configuration - bf16, one activation
@@ -1258,6 +1330,18 @@ void peer_chain_read(void* const* bufs, void* epoch_word, int world, int rank, i
 
 // Sweep-only overrides (0 / -1 = built-in choice). Atomics: a sweep thread can never corrupt a concurrent launch,
 // it can only change which (always correct) geometry that launch uses.
+// 1 when a single-matrix M-row call of this shape launches the exact-geometry instance under the calling thread's tuning, else 0
+// (pure host logic: the geometry and the selection rule of launch_one)
+bool gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, bool nested) {
+    const int knob = g_tune.nt.load(std::memory_order_relaxed);
+    if (nested || (dtype != 1 && dtype != 2) || M != 1 || N <= 0 || K <= 0 || K % 32 != 0 || blocksize < 32 || !is_pow2(blocksize) ||
+        g_tune.waves.load(std::memory_order_relaxed) == 8 || g_tune.ns.load(std::memory_order_relaxed) != 0 || knob == 0 || knob == kTuneGeneral ||
+        knob == kTuneLateArgs)
+        return false;
+    const Geometry ge = make_geometry(N, K, 1, 16, 2, false, g_tune.sw.load(std::memory_order_relaxed), g_tune.rows.load(std::memory_order_relaxed));
+    return exact_geometry(ge, M, N, K, kRing);
+}
+
 void gemv_4bit_stream_tuning(int ns, int sw, int rows_per_wg, int nt, int waves) {
     g_tune.ns.store(ns, std::memory_order_relaxed);
     g_tune.sw.store(sw, std::memory_order_relaxed);

@@ -264,6 +264,13 @@ void bnb_mi355x_set_tuning(int reserved0, int reserved1, int mfma_knob0, int mfm
  * like bnb_mi355x_set_tuning. */
 void bnb_mi355x_set_stream_tuning(int ring_depth, int segments, int rows_per_workgroup, int nontemporal, int waves);
 
+/* Which instance of the streaming kernel a single-matrix call of this shape launches under the calling thread's stream tuning:
+ * 1 = the exact-geometry instance (M = 1, 16-bit activations, fp32 absmax (nested = 0), K = 4096, rows that divide evenly over
+ * workgroups and row groups: csrc/gemv4_stream.hip exact_geometry), 0 = the general one. Host logic only (the launcher's own
+ * geometry and rule, no launch). Stream tuning `nontemporal` = 2 forces the general instance, 3 the general instance with the
+ * epilogue's pointers loaded late (A/B runs: tools/stream_fixed_cost_ab.py). */
+int bnb_mi355x_gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, int nested);
+
 /* Profiling builds only (libbitsandbytes_mi355x_prof.so, -DBNB_PROFILING): when non-NULL the kernels write s_memtime
  * stamps per wavefront (u64) into this device buffer (tools/timeline_*.py). The product library contains no stamp or
  * ablation code; there the call is accepted and ignored. */

@@ -62,6 +62,7 @@ for b in range(nwg):  # s_memtime domains are not chip-wide: normalise every wav
         base = t[sel, 0].min()
         t[sel, :13] = torch.where(t[sel, :13] > 0, t[sel, :13] - base + 1, t[sel, :13])
         t[sel, 15] = torch.where(t[sel, 15] > 0, t[sel, 15] - base + 1, t[sel, 15])
+wave_in_wg = (torch.arange(NW) % waves_per_wg)[live]
 rt = rt[live]
 t = t[live]
 r0 = rt[:, 0].min()
@@ -92,3 +93,12 @@ for i in order:
         d = f"{(t[both, i] - t[both, prev]).median().item():8.0f}"
     print(f"{nme:20s} {rel.min().item():8.0f} {rel.median().item():8.0f} {rel.quantile(0.9).item():8.0f} {rel.max().item():8.0f}   {d}")
     prev = i
+# the kernel's fixed cost in two spans: a wavefront's start -> its ring issued (first / second half of the workgroup: the first half
+# copies the activations in front of its ring), and the tail of the kernel behind the final barrier
+for label, sel in (("first half", wave_in_wg < waves_per_wg // 2), ("second half", wave_in_wg >= waves_per_wg // 2)):
+    ok = sel & (t[:, 0] > 0) & (t[:, 1] > 0)
+    if ok.any():
+        print(f"# start -> ring issued, wavefronts of the {label} of the workgroup: median {(t[ok, 1] - t[ok, 0]).median().item():.0f} ticks")
+if (t[:, 7] > 0).any() and (t[:, 8] > 0).any():
+    print(f"# max(end) - max(past final barrier): {(t[:, 8].max() - t[:, 7].max()).item():.0f} ticks; median wavefront past final barrier -> end: "
+          f"{(t[:, 8] - t[:, 7])[(t[:, 7] > 0) & (t[:, 8] > 0)].median().item():.0f}")
