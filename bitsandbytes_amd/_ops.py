@@ -410,3 +410,44 @@ def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str,
       absmax_offset=None):
     _, N, _, _ = _check_gemm_4bit_experts(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code, absmax_offset)
     return torch.empty((*ids.shape, N), dtype=A.dtype, device=A.device)
+
+
+# ---------------------------------------------------------------------------------------------- gemm_4bit_experts_ffn
+# gemm_4bit_experts with one of two epilogues - the two projections of a gated-SiLU expert FFN:
+#   gated = "chunked" / "interleaved": B is [E, 2 I, K] (gate rows [0, I) and up rows [I, 2 I), or gate row 2 i and up row 2 i + 1),
+#     out[t, s, :] = silu(g) * u of the plain call's (g, u) - [T, S, I], bit for bit torch's F.silu(g) * u on that output;
+#   row_scale [T, S] (fp32 or A's dtype, on the device): out[t, s, :] = (acc + bias) * row_scale[t, s], rounded once.
+# The two exclude each other; with neither, the op equals gemm_4bit_experts. An id outside [0, E) gives zeros whatever its scale.
+GATED_CODES = {"none": 0, "chunked": 1, "interleaved": 2}
+
+torch.library.define(
+    "bitsandbytes_amd::gemm_4bit_experts_ffn",
+    "(Tensor A, Tensor B, int[] shapeB, Tensor absmax, Tensor ids, int blocksize, str quant_type, Tensor? bias=None, "
+    "Tensor? absmax_8bit=None, Tensor? absmax_code=None, Tensor? absmax_offset=None, Tensor? row_scale=None, "
+    "str gated=\"none\") -> Tensor",
+)
+
+
+def _check_gemm_4bit_experts_ffn(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code, absmax_offset,
+                                 row_scale, gated):
+    """The checks of gemm_4bit_experts and those of the two epilogues; returns (E, N, K, per_slot, output width)."""
+    E, N, K, per_slot = _check_gemm_4bit_experts(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code,
+                                                 absmax_offset)
+    torch._check(gated in GATED_CODES, lambda: f"gated must be one of {sorted(GATED_CODES)}, got {gated!r}")
+    if gated != "none":
+        torch._check(N % 2 == 0, lambda: f"a gated call needs an even number of weight rows per expert (gate + up), got N = {N}")
+        torch._check(row_scale is None, lambda: "gated and row_scale cannot be given together")
+    if row_scale is not None:
+        torch._check(tuple(row_scale.shape) == tuple(ids.shape),
+                     lambda: f"row_scale must have the shape of ids {tuple(ids.shape)}, got {tuple(row_scale.shape)}")
+        torch._check(row_scale.dtype in (torch.float32, A.dtype), lambda: f"row_scale must be float32 or {A.dtype}, got {row_scale.dtype}")
+        torch._check(row_scale.device == A.device, lambda: "row_scale must live on A's device")
+    return E, N, K, per_slot, (N // 2 if gated != "none" else N)
+
+
+@register_fake("bitsandbytes_amd::gemm_4bit_experts_ffn")
+def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str, bias=None, absmax_8bit=None, absmax_code=None,
+      absmax_offset=None, row_scale=None, gated: str = "none"):
+    width = _check_gemm_4bit_experts_ffn(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code, absmax_offset,
+                                         row_scale, gated)[4]
+    return torch.empty((*ids.shape, width), dtype=A.dtype, device=A.device)

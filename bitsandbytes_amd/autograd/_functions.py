@@ -162,6 +162,9 @@ def matmul_4bit_experts(
     quant_state: F.QuantState,
     expert_ids: torch.Tensor,
     bias: Optional[torch.Tensor] = None,
+    *,
+    row_scale: Optional[torch.Tensor] = None,
+    gated: str = "none",
 ):
     """``y[t, s] = x_row(t, s) @ dequant(packed)[expert_ids[t, s]].T (+ bias[expert_ids[t, s]])`` in one launch - the expert
     projections of a mixture-of-experts decode step. ``packed`` / ``quant_state``: ONE ``quantize_4bit`` over the fused
@@ -169,7 +172,13 @@ def matmul_4bit_experts(
     by the kernel only, so the call needs no host synchronisation and can be captured in a graph and replayed with other ids in
     the same buffer; an id outside ``[0, E)`` gives a row of zeros. ``x``: ``[T, K]`` (the slots of a token share its
     activations: gate / up) or ``[T, S, K]`` (one row per slot: down). ``bias``: optional ``[E, N]``. Returns ``[T, S, N]``
-    (``[P, N]`` for flat ids). Inference only: there is no autograd formula."""
+    (``[P, N]`` for flat ids). Inference only: there is no autograd formula.
+
+    Two epilogues for the projections of a gated-SiLU expert FFN (they exclude each other; :func:`moe_ffn_4bit` is the block):
+    ``gated="chunked"`` / ``"interleaved"``: the stack is ``[E, 2 I, K]`` (gate rows ``[0, I)`` and up rows ``[I, 2 I)``, or gate row
+    ``2 i`` and up row ``2 i + 1``) and the result ``[T, S, I]`` is ``F.silu(g) * u`` of the plain call's two halves, bit for bit;
+    ``row_scale``: ``[T, S]`` (the shape of ``expert_ids``), fp32 or ``x``'s dtype, on the device - ``y[t, s]`` is multiplied by it
+    in fp32 in front of the single rounding."""
     if quant_state is None:
         raise ValueError("quant_state is required")
     if len(quant_state.shape) != 3:
@@ -182,14 +191,52 @@ def matmul_4bit_experts(
             f"matmul_4bit_experts: x inner dim ({x.shape[-1]}) must equal quant_state.shape[2] ({quant_state.shape[2]}); "
             "expert tensors in [E, K, N] orientation (contraction over the unpacked dimension) are not supported")
     packed = packed.view(-1, 1)
-    op = torch.ops.bitsandbytes_amd.gemm_4bit_experts.default
+    if row_scale is None and gated == "none":
+        op, extra = torch.ops.bitsandbytes_amd.gemm_4bit_experts.default, {}
+    else:
+        if torch.is_grad_enabled() and row_scale is not None and row_scale.requires_grad:
+            raise RuntimeError("matmul_4bit_experts is inference only (no autograd formula): call it under torch.no_grad() "
+                               "or with detached inputs")
+        op, extra = torch.ops.bitsandbytes_amd.gemm_4bit_experts_ffn.default, {"row_scale": row_scale, "gated": gated}
     if not quant_state.nested:
         return op(x, packed, quant_state.shape, quant_state.absmax, expert_ids, quant_state.blocksize, quant_state.quant_type,
-                  bias=bias)
+                  bias=bias, **extra)
     if quant_state.state2.blocksize != 256:
         raise NotImplementedError("nested quantization with state2.blocksize != 256 is not supported")
     return op(x, packed, quant_state.shape, quant_state.state2.absmax, expert_ids, quant_state.blocksize, quant_state.quant_type,
-              bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code, absmax_offset=quant_state.offset)
+              bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code, absmax_offset=quant_state.offset, **extra)
+
+
+def moe_ffn_4bit(
+    x: torch.Tensor,
+    gate_up: torch.Tensor,
+    gate_up_state: F.QuantState,
+    down: torch.Tensor,
+    down_state: F.QuantState,
+    expert_ids: torch.Tensor,
+    routing_weights: torch.Tensor,
+    gate_up_bias: Optional[torch.Tensor] = None,
+    down_bias: Optional[torch.Tensor] = None,
+    gated: str = "chunked",
+):
+    """The expert FFN block of a mixture-of-experts decode step, two launches and one slot sum::
+
+        h[t, s] = silu(g) * u,  (g, u) = x[t] @ dequant(gate_up)[expert_ids[t, s]].T (+ gate_up_bias)      [T, S, I]
+        y[t]    = sum_s routing_weights[t, s] * (h[t, s] @ dequant(down)[expert_ids[t, s]].T (+ down_bias))  [T, H]
+
+    ``gate_up`` / ``gate_up_state``: one ``quantize_4bit`` over the ``[E, 2 I, H]`` stack, (gate, up) rows ``gated="chunked"`` or
+    ``"interleaved"`` (:func:`matmul_4bit_experts`); ``down`` / ``down_state``: the same over ``[E, H, I]``. ``x``: ``[T, H]`` (or
+    ``[T, S, H]``); ``expert_ids`` and ``routing_weights``: ``[T, S]`` on the device, the weights fp32 or of ``x``'s dtype. Neither is
+    read on the host, so the block can be captured in a graph and replayed with other ids and weights in the same buffers. A slot
+    whose id is outside ``[0, E)`` contributes zeros whatever its weight. Inference only."""
+    if gated not in ("chunked", "interleaved"):
+        raise ValueError(f"moe_ffn_4bit: gated must be 'chunked' or 'interleaved', got {gated!r}")
+    if expert_ids.dim() != 2 or tuple(routing_weights.shape) != tuple(expert_ids.shape):
+        raise ValueError(f"moe_ffn_4bit: expert_ids and routing_weights must both be [T, S], got {tuple(expert_ids.shape)} and "
+                         f"{tuple(routing_weights.shape)}")
+    h = matmul_4bit_experts(x, gate_up, gate_up_state, expert_ids, bias=gate_up_bias, gated=gated)
+    y = matmul_4bit_experts(h, down, down_state, expert_ids, bias=down_bias, row_scale=routing_weights)
+    return y[:, 0] if y.shape[1] == 1 else y.sum(dim=1)
 
 
 def matmul_4bit_grouped(A: torch.Tensor, weights, quant_states, biases=None, outs=None):

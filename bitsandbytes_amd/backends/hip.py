@@ -20,7 +20,7 @@ from warnings import warn
 
 import torch
 
-from .._ops import _check_gemm_4bit_experts, register_kernel
+from .._ops import GATED_CODES, _check_gemm_4bit_experts, _check_gemm_4bit_experts_ffn, register_kernel
 from ..cextension import lib
 
 _DT_NAME = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}
@@ -531,6 +531,48 @@ def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str,
             _DT_CODE[A.dtype], A.data_ptr(), K if (per_slot or ids.dim() == 1) else 0, B.data_ptr(), absmax.contiguous().data_ptr(),
             _ptr(absmax_8bit if absmax_8bit is None else absmax_8bit.contiguous()), _ptr(code32), _ptr(offset32),
             _ptr(bias if bias is None else bias.contiguous()), ids.data_ptr(), ids.element_size(), out.data_ptr(),
+            P, S, E, N, K, blocksize, _QT_CODE[quant_type], _stream(A),
+        )
+    return out
+
+
+def gemm_4bit_experts_ffn_supported(dtype: torch.dtype, E: int, N: int, K: int, blocksize: int, gated: str = "none") -> bool:
+    """Whether the expert-indexed kernel serves this geometry with this epilogue (N: weight rows per expert; pure host logic)."""
+    if dtype not in _DT_CODE or gated not in GATED_CODES or max(E, N, K) >= 2**31:
+        return False
+    return bool(lib.bnb_mi355x_gemm_4bit_experts_ffn_supported(_DT_CODE[dtype], E, N, K, blocksize, GATED_CODES[gated]))
+
+
+@register_kernel("bitsandbytes_amd::gemm_4bit_experts_ffn", "cuda")
+def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str, bias=None, absmax_8bit=None, absmax_code=None,
+      absmax_offset=None, row_scale=None, gated: str = "none"):
+    """One launch of gemm4_experts_kernel with the gated or the row-scale epilogue; ids and scales stay on the device."""
+    E, N, K, per_slot, width = _check_gemm_4bit_experts_ffn(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit,
+                                                            absmax_code, absmax_offset, row_scale, gated)
+    if not gemm_4bit_experts_ffn_supported(A.dtype, E, N, K, blocksize, gated):
+        raise ValueError(f"gemm_4bit_experts_ffn: no kernel for E={E}, N={N}, K={K}, blocksize={blocksize}, dtype={A.dtype}, gated={gated}")
+    P = ids.numel()
+    S = ids.shape[1] if ids.dim() == 2 else 1
+    out = torch.empty((*ids.shape, width), dtype=A.dtype, device=A.device)
+    if P == 0:
+        return out
+    A = A.contiguous()
+    B = B.contiguous()
+    ids = ids.contiguous()
+    if A.data_ptr() % 16 or B.data_ptr() % 16:
+        raise ValueError("gemm_4bit_experts_ffn: A and B must be 16-byte aligned")
+    for t in (absmax, bias, absmax_8bit, absmax_code, absmax_offset):
+        if t is not None and t.device != A.device:
+            raise ValueError("gemm_4bit_experts_ffn: statistics and bias must live on A's device")
+    code32 = absmax_code.to(dtype=torch.float32).contiguous() if absmax_code is not None else None
+    offset32 = absmax_offset.to(dtype=torch.float32) if absmax_offset is not None else None
+    scale = None if row_scale is None else row_scale.contiguous()  # (read in its own dtype: no conversion launch)
+    with _device_of(A):
+        lib.bnb_mi355x_gemm_4bit_experts_ffn(
+            _DT_CODE[A.dtype], A.data_ptr(), K if (per_slot or ids.dim() == 1) else 0, B.data_ptr(), absmax.contiguous().data_ptr(),
+            _ptr(absmax_8bit if absmax_8bit is None else absmax_8bit.contiguous()), _ptr(code32), _ptr(offset32),
+            _ptr(bias if bias is None else bias.contiguous()), ids.data_ptr(), ids.element_size(),
+            _ptr(scale), 0 if scale is None else _DT_CODE[scale.dtype], GATED_CODES[gated], out.data_ptr(),
             P, S, E, N, K, blocksize, _QT_CODE[quant_type], _stream(A),
         )
     return out

@@ -76,6 +76,11 @@ bool gemm_4bit_experts_supported(int dtype, long E, long N, long K, int blocksiz
 void gemm_4bit_experts(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
                        const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes,
                        void* out, long P, int S, int E, int N, int K, int blocksize, int quant_type, hipStream_t stream);
+bool gemm_4bit_experts_ffn_supported(int dtype, long E, long N, long K, int blocksize, int gated);
+void gemm_4bit_experts_ffn(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
+                           const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes,
+                           const void* row_scale, int row_scale_dtype, int gated, void* out, long P, int S, int E, int N, int K,
+                           int blocksize, int quant_type, hipStream_t stream);
 
 namespace {
 
@@ -397,6 +402,16 @@ void bnb_mi355x_gemm_4bit_experts(int dtype, const void* A, long a_slot_stride, 
 }
 int bnb_mi355x_gemm_4bit_experts_supported(int dtype, int E, int N, int K, int blocksize) {
     return gemm_4bit_experts_supported(dtype, E, N, K, blocksize) ? 1 : 0;
+}
+void bnb_mi355x_gemm_4bit_experts_ffn(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax,
+                                      const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, const void* bias,
+                                      const void* ids, int index_bytes, const void* row_scale, int row_scale_dtype, int gated, void* out,
+                                      long P, int slots, int E, int N, int K, int blocksize, int quant_type, bnb_stream_t s) {
+    gemm_4bit_experts_ffn(dtype, A, a_slot_stride, B, absmax, absmax_8bit, absmax_code, absmax_offset, bias, ids, index_bytes, row_scale,
+                          row_scale_dtype, gated, out, P, slots, E, N, K, blocksize, quant_type, S(s));
+}
+int bnb_mi355x_gemm_4bit_experts_ffn_supported(int dtype, int E, int N, int K, int blocksize, int gated) {
+    return gemm_4bit_experts_ffn_supported(dtype, E, N, K, blocksize, gated) ? 1 : 0;
 }
 
 // ------------------------------------------------------------------ peer chain (the all-gather fused into the gemv launches)

@@ -19,6 +19,14 @@
 // lands in: deterministic, order-free, no atomics.
 //
 // Ids outside [0, E) (a router's "dropped" slot) select nothing; the expert-0 workgroups write zeros to those rows.
+//
+// Two more epilogues, compile-time variants (EPI) of the same kernel - the plain form's code is what it was:
+//   * gated: an expert's matrix is [2 I, K], (gate, up) rows chunked (gate [0, I), up [I, 2 I)) or interleaved (gate 2 i, up 2 i + 1);
+//     the output is [P, I], out = T(float(T(silu(g))) * float(u)) with g = T(acc_g + bias_g), u = T(acc_u + bias_u) - the bits of
+//     torch's `F.silu(g) * u` on the plain call's T-valued output. A workgroup keeps its TN (even) WEIGHT rows: local row 2 c is
+//     the gate row and 2 c + 1 the up row of the tile's output column c, so only the local -> global row map (wave-uniform
+//     scalars) and the epilogue differ; every row's sum is formed exactly as in the plain form.
+//   * row scale: out[p, n] = T((acc + bias) * w[p]), w fp32 or T as it is in memory (the routing weight of the down projection).
 #include "bnb_common.h"
 
 namespace bnb {
@@ -37,6 +45,7 @@ constexpr int kThreads = kWaves * 64;
 constexpr int kPassRows = 4; // pairs of one expert served by one pass over its weights
 constexpr int kMaxSegs = 64; // K <= 131072
 constexpr size_t kPartBudget = 12 * 1024;
+constexpr int kEpiPlain = 0, kEpiGated = 1, kEpiScale = 2;
 
 struct ExpertArgs {
     const void* A;
@@ -48,6 +57,10 @@ struct ExpertArgs {
     const void* bias;
     const void* ids;
     void* out;
+    const void* row_scale; // kEpiScale: [P] fp32 (scale_f32) or T
+    int scale_f32;
+    int up_delta, col_step, n0_shift; // kEpiGated: up row = gate row + up_delta, next column's gate row + col_step (chunked: N / 2, 1;
+                            // interleaved: 1, 2); the tile's first gate row is n0 >> n0_shift (chunked: n0 / 2, interleaved: n0)
     int P, S, E, N, K, bs_shift;
     int a_per_slot; // 1: one activation row per pair, 0: one per token (pair / S)
     int idx64;
@@ -101,6 +114,13 @@ __device__ __forceinline__ float code_literal_rt(bool fp4, int i) {
     return v;
 }
 
+// An fp32 intermediate that is rounded to fp32 BEFORE it is converted to T: without it the compiler folds `T(a * b)` of fp16
+// instances into v_fma_mixlo_f16, which rounds the exact product once - not what two torch kernels (and the plain form) compute.
+__device__ __forceinline__ float rounded_f32(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
 __device__ __forceinline__ long long load_id(const void* ids, int idx64, int i) {
     return idx64 ? static_cast<const long long*>(ids)[i] : static_cast<long long>(static_cast<const int*>(ids)[i]);
 }
@@ -143,7 +163,7 @@ struct Stage {
 };
 
 // One pass: MB pairs of expert e against the workgroup's tile, all K.
-template <typename T, bool NESTED, int MB>
+template <typename T, bool NESTED, int MB, int EPI>
 __device__ __forceinline__ void run_pass(const ExpertArgs& p, unsigned char* smem, const int (&pr)[kPassRows], int e, int n0, int rows, int tid) {
     // weight rows in flight per wavefront (and as many again prefetched): fewer beside the 96 ... 128 activation registers of 3 / 4 rows
     constexpr int kDepth = MB >= 3 ? 2 : 4;
@@ -157,6 +177,16 @@ __device__ __forceinline__ void run_pass(const ExpertArgs& p, unsigned char* sme
     const float offset = NESTED ? p.absmax_offset[0] : 0.0f;
     const long row_base = static_cast<long>(e) * p.N + n0; // first row of the tile in the flat [E * N, K] matrix
     const int items = (wave_active && g < rows) ? (rows - g + p.G - 1) / p.G : 0;
+    // gated: local row rl = 2 c + h is the gate (h = 0) or up (h = 1) row of the tile's output column c (n0 and rows are even)
+    // chunked: gate row (n0 >> 1) + c, up row N / 2 + that; interleaved: gate row n0 + 2 c, up row that + 1. One base beside the
+    // launch's two constants (up_delta, col_step): nothing more stays live across the item loop than in the plain form
+    const long gate_base = static_cast<long>(e) * p.N + (n0 >> p.n0_shift);
+    auto global_row = [&](int rl) -> long {
+        if constexpr (EPI == kEpiGated)
+            return gate_base + (rl & 1) * p.up_delta + (rl >> 1) * p.col_step;
+        else
+            return row_base + rl;
+    };
 
     for (int ph = 0; ph < p.PH; ++ph) {
         const int seg = ph * p.SW + sw;
@@ -182,7 +212,7 @@ __device__ __forceinline__ void run_pass(const ExpertArgs& p, unsigned char* sme
         auto load_stage = [&](int item) -> Stage {
             const int it = item < items ? item : items - 1; // (clamped: the prefetch behind the last row re-reads it)
             const int rl = g + it * p.G;
-            const long elem = (row_base + rl) * p.K + k0c;
+            const long elem = global_row(rl) * p.K + k0c;
             Stage st;
             st.w = *reinterpret_cast<const u32x4*>(p.B + (elem >> 1));
             const long blk = elem >> p.bs_shift;
@@ -256,21 +286,51 @@ __device__ __forceinline__ void run_pass(const ExpertArgs& p, unsigned char* sme
     }
     __syncthreads();
     // a row's segment sums in ascending segment order, bias, one rounding
+    if constexpr (EPI == kEpiGated) {
+#pragma unroll
+        for (int m = 0; m < MB; ++m) {
+            T* const orow = static_cast<T*>(p.out) + static_cast<long>(pr[m]) * (p.N >> 1) + (n0 >> 1);
+            for (int c = tid; c < (rows >> 1); c += kThreads) {
+                float ag = 0.0f, au = 0.0f;
+                for (int s = 0; s < p.SEGS; ++s)
+                    ag += part[((2 * c) * p.SEGS + s) * kPassRows + m];
+                for (int s = 0; s < p.SEGS; ++s)
+                    au += part[((2 * c + 1) * p.SEGS + s) * kPassRows + m];
+                const long rg = gate_base + c * p.col_step, ru = rg + p.up_delta;
+                const float bg = p.bias ? static_cast<float>(static_cast<const T*>(p.bias)[rg]) : 0.0f;
+                const float bu = p.bias ? static_cast<float>(static_cast<const T*>(p.bias)[ru]) : 0.0f;
+                // torch's `F.silu(g) * u` on T-valued g, u: silu in fp32 (exact expf, IEEE division) rounded to T, the product
+                // in fp32 rounded to T (csrc/gemv4_stream.hip, gated production)
+                const float gf = static_cast<float>(static_cast<T>(rounded_f32(ag + bg)));
+                const float uf = static_cast<float>(static_cast<T>(rounded_f32(au + bu)));
+                const T st = static_cast<T>(rounded_f32(gf / (1.0f + expf(-gf))));
+                orow[c] = static_cast<T>(rounded_f32(__fmul_rn(static_cast<float>(st), uf)));
+            }
+        }
+        __syncthreads();
+        return;
+    }
 #pragma unroll
     for (int m = 0; m < MB; ++m) {
         T* const orow = static_cast<T*>(p.out) + static_cast<long>(pr[m]) * p.N + n0;
+        [[maybe_unused]] float w = 1.0f; // the pair's routing weight: one fp32 multiply in front of the single rounding
+        if constexpr (EPI == kEpiScale)
+            w = p.scale_f32 ? static_cast<const float*>(p.row_scale)[pr[m]] : static_cast<float>(static_cast<const T*>(p.row_scale)[pr[m]]);
         for (int rl = tid; rl < rows; rl += kThreads) {
             float acc = 0.0f;
             for (int s = 0; s < p.SEGS; ++s)
                 acc += part[(rl * p.SEGS + s) * kPassRows + m];
             const float b = p.bias ? static_cast<float>(static_cast<const T*>(p.bias)[row_base + rl]) : 0.0f;
-            orow[rl] = static_cast<T>(acc + b);
+            if constexpr (EPI == kEpiScale)
+                orow[rl] = static_cast<T>(rounded_f32(__fmul_rn(__fadd_rn(acc, b), w)));
+            else
+                orow[rl] = static_cast<T>(acc + b);
         }
     }
     __syncthreads();
 }
 
-template <typename T, bool NESTED> __global__ __launch_bounds__(kThreads) void gemm4_experts_kernel(const ExpertArgs p) {
+template <typename T, bool NESTED, int EPI = kEpiPlain> __global__ __launch_bounds__(kThreads) void gemm4_experts_kernel(const ExpertArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -279,13 +339,14 @@ template <typename T, bool NESTED> __global__ __launch_bounds__(kThreads) void g
     const int rows = (p.N - n0) < p.TN ? (p.N - n0) : p.TN;
 
     if (e == 0) {
-        // rows of ids that name no expert: zeros, no weight read, no bias
+        // rows of ids that name no expert: zeros, no weight read, no bias, no scale (gated: the tile's rows / 2 output columns)
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        constexpr int kSh = EPI == kEpiGated ? 1 : 0;
         for (int q = wave; q < p.P; q += kWaves) {
             const long long id = load_id(p.ids, p.idx64, q);
             if (id < 0 || id >= p.E) {
-                T* const orow = static_cast<T*>(p.out) + static_cast<long>(q) * p.N + n0;
-                for (int c = lane; c < rows; c += 64)
+                T* const orow = static_cast<T*>(p.out) + static_cast<long>(q) * (p.N >> kSh) + (n0 >> kSh);
+                for (int c = lane; c < (rows >> kSh); c += 64)
                     orow[c] = static_cast<T>(0.0f);
             }
         }
@@ -318,22 +379,31 @@ template <typename T, bool NESTED> __global__ __launch_bounds__(kThreads) void g
             table_built = true;
         }
         if (cnt == 1)
-            run_pass<T, NESTED, 1>(p, smem, pr, e, n0, rows, tid);
+            run_pass<T, NESTED, 1, EPI>(p, smem, pr, e, n0, rows, tid);
         else if (cnt == 2)
-            run_pass<T, NESTED, 2>(p, smem, pr, e, n0, rows, tid);
+            run_pass<T, NESTED, 2, EPI>(p, smem, pr, e, n0, rows, tid);
         else if (cnt == 3)
-            run_pass<T, NESTED, 3>(p, smem, pr, e, n0, rows, tid);
+            run_pass<T, NESTED, 3, EPI>(p, smem, pr, e, n0, rows, tid);
         else
-            run_pass<T, NESTED, 4>(p, smem, pr, e, n0, rows, tid);
+            run_pass<T, NESTED, 4, EPI>(p, smem, pr, e, n0, rows, tid);
     }
 }
 
-LdsLimit g_lds[3][2];
+LdsLimit g_lds[3][2][3];
 
-template <typename T, bool NESTED> void launch(const ExpertArgs& a, dim3 grid, size_t lds, int di, hipStream_t stream) {
-    ensure_dynamic_lds(g_lds[di][NESTED ? 1 : 0], reinterpret_cast<const void*>(&gemm4_experts_kernel<T, NESTED>), lds);
-    hipLaunchKernelGGL((gemm4_experts_kernel<T, NESTED>), grid, dim3(kThreads), lds, stream, a);
+template <typename T, bool NESTED, int EPI> void launch_epi(const ExpertArgs& a, dim3 grid, size_t lds, int di, hipStream_t stream) {
+    ensure_dynamic_lds(g_lds[di][NESTED ? 1 : 0][EPI], reinterpret_cast<const void*>(&gemm4_experts_kernel<T, NESTED, EPI>), lds);
+    hipLaunchKernelGGL((gemm4_experts_kernel<T, NESTED, EPI>), grid, dim3(kThreads), lds, stream, a);
     BNB_CHECK_LAUNCH();
+}
+
+template <typename T, bool NESTED> void launch(const ExpertArgs& a, dim3 grid, size_t lds, int di, int epi, hipStream_t stream) {
+    if (epi == kEpiGated)
+        launch_epi<T, NESTED, kEpiGated>(a, grid, lds, di, stream);
+    else if (epi == kEpiScale)
+        launch_epi<T, NESTED, kEpiScale>(a, grid, lds, di, stream);
+    else
+        launch_epi<T, NESTED, kEpiPlain>(a, grid, lds, di, stream);
 }
 
 } // namespace
@@ -349,18 +419,31 @@ bool gemm_4bit_experts_supported(int dtype, long E, long N, long K, int blocksiz
     return E * N < (1L << 31);
 }
 
-void gemm_4bit_experts(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
-                       const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes,
-                       void* out, long P, int S, int E, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
+// The geometries of the FFN entry point: the plain predicate, and an even number of weight rows (gate + up) in a gated call.
+bool gemm_4bit_experts_ffn_supported(int dtype, long E, long N, long K, int blocksize, int gated) {
+    if (gated < 0 || gated > 2 || (gated != 0 && N % 2 != 0))
+        return false;
+    return gemm_4bit_experts_supported(dtype, E, N, K, blocksize);
+}
+
+// gated: 0 none, 1 chunked, 2 interleaved (N = 2 I weight rows per expert, out [P, I]); row_scale: [P] fp32 (row_scale_dtype 0) or
+// of the activations' dtype (row_scale_dtype == dtype), or null. Not both.
+void gemm_4bit_experts_ffn(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
+                           const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes,
+                           const void* row_scale, int row_scale_dtype, int gated, void* out, long P, int S, int E, int N, int K,
+                           int blocksize, int quant_type, hipStream_t stream) {
     if (P <= 0)
         return;
-    if (!gemm_4bit_experts_supported(dtype, E, N, K, blocksize) || (quant_type != kFP4 && quant_type != kNF4) || S <= 0 ||
+    if (!gemm_4bit_experts_ffn_supported(dtype, E, N, K, blocksize, gated) || (gated != 0 && row_scale != nullptr) ||
+        (row_scale != nullptr && row_scale_dtype != 0 && row_scale_dtype != dtype) ||
+        (quant_type != kFP4 && quant_type != kNF4) || S <= 0 ||
         (a_slot_stride != 0 && a_slot_stride != K) || (index_bytes != 4 && index_bytes != 8) || P > (1L << 30) ||
         !aligned_to(A, 16) || !aligned_to(B, 16)) {
         fprintf(stderr,
                 "bitsandbytes_amd: gemm_4bit_experts: unsupported call (dtype %d, E %d, N %d, K %d, blocksize %d, quant_type %d, "
-                "a_slot_stride %ld, index_bytes %d; A and B must be 16-byte aligned)\n",
-                dtype, E, N, K, blocksize, quant_type, a_slot_stride, index_bytes);
+                "a_slot_stride %ld, index_bytes %d, gated %d, row_scale %s of dtype %d; A and B must be 16-byte aligned, gated and "
+                "row_scale exclude each other)\n",
+                dtype, E, N, K, blocksize, quant_type, a_slot_stride, index_bytes, gated, row_scale ? "given" : "null", row_scale_dtype);
         exit(1);
     }
     ExpertArgs a{};
@@ -373,6 +456,11 @@ void gemm_4bit_experts(int dtype, const void* A, long a_slot_stride, const uint8
     a.bias = bias;
     a.ids = ids;
     a.out = out;
+    a.row_scale = row_scale;
+    a.scale_f32 = row_scale_dtype == 0;
+    a.up_delta = gated == 2 ? 1 : N / 2;
+    a.col_step = gated == 2 ? 2 : 1;
+    a.n0_shift = gated == 2 ? 0 : 1;
     a.P = static_cast<int>(P);
     a.S = S;
     a.E = E;
@@ -394,17 +482,27 @@ void gemm_4bit_experts(int dtype, const void* A, long a_slot_stride, const uint8
     const int tn_cap = static_cast<int>(kPartBudget / (static_cast<size_t>(a.SEGS) * kPassRows * sizeof(float)));
     if (tn > tn_cap)
         tn = tn_cap;
+    if (gated != 0)
+        tn &= ~1; // (gate, up) row pairs: TN / 2 output columns (tn >= 12 here)
     a.TN = tn;
     const size_t lds = kLutBytes + kCode2Bytes + static_cast<size_t>(tn) * a.SEGS * kPassRows * sizeof(float);
     const dim3 grid((N + tn - 1) / tn, E);
     const bool nested = absmax8 != nullptr;
+    const int epi = gated != 0 ? kEpiGated : (row_scale != nullptr ? kEpiScale : kEpiPlain);
     if (dtype == 0)
-        nested ? launch<float, true>(a, grid, lds, 0, stream) : launch<float, false>(a, grid, lds, 0, stream);
+        nested ? launch<float, true>(a, grid, lds, 0, epi, stream) : launch<float, false>(a, grid, lds, 0, epi, stream);
     else if (dtype == 1)
-        nested ? launch<f16, true>(a, grid, lds, 1, stream) : launch<f16, false>(a, grid, lds, 1, stream);
+        nested ? launch<f16, true>(a, grid, lds, 1, epi, stream) : launch<f16, false>(a, grid, lds, 1, epi, stream);
     else
-        nested ? launch<bf16, true>(a, grid, lds, 2, stream) : launch<bf16, false>(a, grid, lds, 2, stream);
+        nested ? launch<bf16, true>(a, grid, lds, 2, epi, stream) : launch<bf16, false>(a, grid, lds, 2, epi, stream);
     g_last_gemm_kernel = kKernelExperts;
+}
+
+void gemm_4bit_experts(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
+                       const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes,
+                       void* out, long P, int S, int E, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
+    gemm_4bit_experts_ffn(dtype, A, a_slot_stride, B, absmax, absmax8, absmax_code, absmax_offset, bias, ids, index_bytes, nullptr, 0, 0,
+                          out, P, S, E, N, K, blocksize, quant_type, stream);
 }
 
 } // namespace bnb

@@ -16,6 +16,7 @@ import torch.nn.utils.parametrize as P
 
 from .. import functional as F
 from ..autograd._functions import matmul_4bit_experts as _matmul_4bit_experts
+from ..autograd._functions import moe_ffn_4bit as _moe_ffn_4bit
 
 
 class Bnb4bitParametrization(nn.Module):
@@ -90,6 +91,19 @@ def _disable_parametrization_cache(module: nn.Module, inputs: tuple[Any, ...], o
         P._cache = {}
 
 
+def _expert_state(module: nn.Module, param_name: str, what: str):
+    """(packed parameter, QuantState) of a parametrized 3D expert tensor."""
+    if not P.is_parametrized(module, param_name):
+        raise ValueError(f"'{param_name}' is not a parametrized parameter of the module")
+    plist = module.parametrizations[param_name]
+    hook = next((h for h in plist if isinstance(h, Bnb4bitParametrization)), None)
+    if hook is None or hook.quant_state is None:
+        raise ValueError(f"'{param_name}' carries no 4-bit parametrization")
+    if len(hook.quant_state.shape) != 3:
+        raise ValueError(f"{what}: '{param_name}' must be a 3D [E, N, K] expert tensor, got {list(hook.quant_state.shape)}")
+    return plist.original, hook.quant_state
+
+
 def matmul_4bit_experts(module: nn.Module, param_name: str, x: torch.Tensor, expert_ids: torch.Tensor,
                         bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The expert projections of a decode step on a parametrized ``[E, N, K]`` expert tensor WITHOUT the dequantizing read of the
@@ -97,15 +111,7 @@ def matmul_4bit_experts(module: nn.Module, param_name: str, x: torch.Tensor, exp
     (:func:`bitsandbytes_amd.matmul_4bit_experts`; ``x`` is ``[T, K]`` or ``[T, S, K]``, ``expert_ids`` ``[T, S]`` on the device,
     an id outside ``[0, E)`` gives a row of zeros). Where the kernel does not serve the geometry the dequantized attribute is
     indexed and multiplied instead - also without looking at the ids on the host. Inference only."""
-    if not P.is_parametrized(module, param_name):
-        raise ValueError(f"'{param_name}' is not a parametrized parameter of the module")
-    plist = module.parametrizations[param_name]
-    hook = next((h for h in plist if isinstance(h, Bnb4bitParametrization)), None)
-    if hook is None or hook.quant_state is None:
-        raise ValueError(f"'{param_name}' carries no 4-bit parametrization")
-    state = hook.quant_state
-    if len(state.shape) != 3:
-        raise ValueError(f"matmul_4bit_experts: '{param_name}' must be a 3D [E, N, K] expert tensor, got {list(state.shape)}")
+    packed, state = _expert_state(module, param_name, "matmul_4bit_experts")
     E, N, K = (int(v) for v in state.shape)
     if x.shape[-1] != K:
         raise ValueError(f"matmul_4bit_experts: x inner dim ({x.shape[-1]}) must equal K ({K}); expert tensors in [E, K, N] "
@@ -114,7 +120,6 @@ def matmul_4bit_experts(module: nn.Module, param_name: str, x: torch.Tensor, exp
         raise RuntimeError("matmul_4bit_experts is inference only (no autograd formula): call it under torch.no_grad()")
     from ..backends.hip import gemm_4bit_experts_supported
 
-    packed = plist.original
     served = (x.is_cuda and gemm_4bit_experts_supported(x.dtype, E, N, K, state.blocksize)
               and (not state.nested or state.state2.blocksize == 256) and packed.data_ptr() % 16 == 0)
     if served:
@@ -129,6 +134,44 @@ def matmul_4bit_experts(module: nn.Module, param_name: str, x: torch.Tensor, exp
         if bias is not None:
             y = y + bias[safe]
         return y * valid.unsqueeze(-1).to(y.dtype)
+
+
+def moe_ffn_4bit(module: nn.Module, gate_up_name: str, down_name: str, x: torch.Tensor, expert_ids: torch.Tensor,
+                 routing_weights: torch.Tensor, gate_up_bias: Optional[torch.Tensor] = None,
+                 down_bias: Optional[torch.Tensor] = None, gated: str = "chunked") -> torch.Tensor:
+    """The gated-SiLU expert FFN block of a decode step on parametrized ``[E, 2 I, H]`` / ``[E, H, I]`` expert tensors, from the
+    packed bytes: two launches and one slot sum (:func:`bitsandbytes_amd.moe_ffn_4bit`; ``x`` ``[T, H]``, ``expert_ids`` and
+    ``routing_weights`` ``[T, S]`` on the device; returns ``[T, H]``). Where the kernel does not serve one of the two geometries the
+    block is composed of :func:`matmul_4bit_experts` of this module and torch's ``silu``, ``*`` and ``sum`` - also without looking at
+    the ids or the weights on the host. Inference only."""
+    if gated not in ("chunked", "interleaved"):
+        raise ValueError(f"moe_ffn_4bit: gated must be 'chunked' or 'interleaved', got {gated!r}")
+    gu_packed, gu_state = _expert_state(module, gate_up_name, "moe_ffn_4bit")
+    dn_packed, dn_state = _expert_state(module, down_name, "moe_ffn_4bit")
+    if expert_ids.dim() != 2 or tuple(routing_weights.shape) != tuple(expert_ids.shape):
+        raise ValueError(f"moe_ffn_4bit: expert_ids and routing_weights must both be [T, S], got {tuple(expert_ids.shape)} and "
+                         f"{tuple(routing_weights.shape)}")
+    if torch.is_grad_enabled() and (x.requires_grad or routing_weights.requires_grad):
+        raise RuntimeError("moe_ffn_4bit is inference only (no autograd formula): call it under torch.no_grad()")
+    from ..backends.hip import gemm_4bit_experts_ffn_supported
+
+    def served(packed, state, mode):
+        E, N, K = (int(v) for v in state.shape)
+        return (gemm_4bit_experts_ffn_supported(x.dtype, E, N, K, state.blocksize, mode)
+                and (not state.nested or state.state2.blocksize == 256) and packed.data_ptr() % 16 == 0)
+
+    if (x.is_cuda and routing_weights.dtype in (torch.float32, x.dtype) and served(gu_packed, gu_state, gated)
+            and served(dn_packed, dn_state, "none")):
+        return _moe_ffn_4bit(x, gu_packed.data, gu_state, dn_packed.data, dn_state, expert_ids, routing_weights,
+                             gate_up_bias=gate_up_bias, down_bias=down_bias, gated=gated)
+    with torch.no_grad():
+        h = matmul_4bit_experts(module, gate_up_name, x, expert_ids, bias=gate_up_bias)
+        g, u = (h[..., 0::2], h[..., 1::2]) if gated == "interleaved" else h.chunk(2, dim=-1)
+        y = matmul_4bit_experts(module, down_name, torch.nn.functional.silu(g) * u, expert_ids, bias=down_bias)
+        # (a dropped slot contributes zeros whatever its weight, as in the fused form)
+        E = int(gu_state.shape[0])
+        w = torch.where((expert_ids >= 0) & (expert_ids < E), routing_weights, torch.zeros_like(routing_weights))
+        return (y * w.unsqueeze(-1).to(y.dtype)).sum(dim=1)
 
 
 class _StateDictHook:

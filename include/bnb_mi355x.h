@@ -164,6 +164,19 @@ int bnb_mi355x_last_gemm_kernel(void);
  * a power of two >= 32, K > 131072, E > 65535 - terminates like every failed launch of this ABI: ask first. */
 void bnb_mi355x_gemm_4bit_experts(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes, void* out, long P, int S, int E, int N, int K, int blocksize, int quant_type, bnb_stream_t stream);
 int bnb_mi355x_gemm_4bit_experts_supported(int dtype, int E, int N, int K, int blocksize);
+/* The same launch with one of two epilogues - the two expert projections of a gated-SiLU MoE FFN block (family 9 as well):
+ *   gated = 1 (chunked) / 2 (interleaved): an expert's matrix is [N = 2 I, K] with gate rows 0 .. I-1 and up rows I .. 2 I - 1
+ *     (chunked: torch.chunk(2, -1) of the fused projection's output) or gate row 2 i and up row 2 i + 1 (interleaved); bias, if given,
+ *     [E, 2 I] in the same layout. out is [P, I]:  g = T(acc_g + bias_g), u = T(acc_u + bias_u), out = T(float(T(silu(g))) * float(u))
+ *     with silu(g) = g / (1 + expf(-g)) in fp32 - bit for bit what `F.silu(g) * u` gives on the T-valued output of the plain call.
+ *   row_scale != NULL: out[p, n] = T((acc + bias) * w[p]), w[P] on the device, fp32 (row_scale_dtype 0) or of A's dtype
+ *     (row_scale_dtype == dtype), read as it is: the routing weights of the down projection, one fp32 multiply in front of the
+ *     single rounding.
+ * The two exclude each other; with gated = 0 and row_scale = NULL this is bnb_mi355x_gemm_4bit_experts. A pair whose id is outside
+ * [0, E) stays a row of zeros (I wide when gated) and its scale is never read into the result. N is the number of WEIGHT rows per
+ * expert. bnb_mi355x_gemm_4bit_experts_ffn_supported: the predicate above, and N even when gated != 0 (pure host logic). */
+void bnb_mi355x_gemm_4bit_experts_ffn(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes, const void* row_scale, int row_scale_dtype, int gated, void* out, long P, int S, int E, int N, int K, int blocksize, int quant_type, bnb_stream_t stream);
+int bnb_mi355x_gemm_4bit_experts_ffn_supported(int dtype, int E, int N, int K, int blocksize, int gated);
 
 /* Grouped gemm_4bit: `count` weight matrices applied to the SAME activations A[M, K] in one launch -
  *   out[i][M, N[i]] = A * dequant(B[i])^T (+ bias[i])        i = 0 .. count-1
