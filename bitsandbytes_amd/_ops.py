@@ -451,3 +451,42 @@ def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str,
     width = _check_gemm_4bit_experts_ffn(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code, absmax_offset,
                                          row_scale, gated)[4]
     return torch.empty((*ids.shape, width), dtype=A.dtype, device=A.device)
+
+
+# ---------------------------------------------------------------------------------------------- gemm_4bit_gated
+# Not a reference op: the gate / up projections of a dense gated-SiLU FFN (Llama, Mistral, Qwen, Phi-3) with the activation as the
+# matmul's epilogue. B is the quantize_4bit result of ONE interleaved [2 F, K] matrix - gate row i at row 2 i, up row i at row 2 i + 1
+# (functional.interleave_gate_up_4bit builds it from quantized members) -, bias [2 F] in the same layout, absmax fp32 (nested
+# statistics un-nested). A [*, K] -> [*, F]:  F.silu(y[..., 0::2]) * y[..., 1::2] of the plain gemm_4bit's output y, bit for bit.
+# Served for 1 ... 16 rows where the plain call runs the streaming or the streaming MFMA kernel (backends/hip.py:
+# gemm_4bit_gated_supported); anything else raises. Inference only: no autograd formula.
+torch.library.define(
+    "bitsandbytes_amd::gemm_4bit_gated",
+    "(Tensor A, Tensor B, int[] shapeB, Tensor absmax, int blocksize, str quant_type, Tensor? bias=None) -> Tensor",
+)
+
+
+def _check_gemm_4bit_gated(A, B, shapeB, absmax, blocksize, quant_type, bias):
+    """Argument checks shared by the fake kernel and the device kernel; returns (N = 2 F, K)."""
+    torch._check(is_pow2_blocksize(blocksize), lambda: f"blocksize must be a power of two >= 32, got {blocksize}")
+    torch._check(quant_type in ("nf4", "fp4"), lambda: f"quant_type must be 'nf4' or 'fp4', got {quant_type!r}")
+    torch._check(len(shapeB) == 2, lambda: f"shapeB must be [2 F, K] (the interleaved gate / up matrix), got {list(shapeB)}")
+    N, K = (int(v) for v in shapeB)
+    torch._check(N > 0 and K > 0 and N % 2 == 0, lambda: f"shapeB must be [2 F, K] with an even, positive row count, got {list(shapeB)}")
+    torch._check(A.dtype in _FLOAT_DTYPES, lambda: f"A must be a 16/32-bit float tensor, got {A.dtype}")
+    torch._check(A.dim() >= 1 and A.shape[-1] == K, lambda: f"A inner dim ({A.shape[-1] if A.dim() else None}) must equal K = shapeB[1] ({K})")
+    torch._check(B.device == A.device and absmax.device == A.device, lambda: "A, B and absmax must live on one device")
+    torch._check(B.numel() * B.element_size() * 2 == N * K, lambda: f"B holds {B.numel() * B.element_size() * 2} 4-bit values, shapeB {N * K}")
+    torch._check(absmax.dtype == torch.float32, lambda: f"absmax must be float32, got {absmax.dtype}")
+    torch._check(K % blocksize == 0, lambda: f"K ({K}) must be a multiple of blocksize ({blocksize})")
+    torch._check(absmax.numel() == N * K // blocksize, lambda: f"absmax must hold {N * K // blocksize} values, got {absmax.numel()}")
+    if bias is not None:
+        torch._check(tuple(bias.shape) == (N,), lambda: f"bias must be [2 F] = [{N}] (interleaved like the rows), got {tuple(bias.shape)}")
+        torch._check(bias.dtype == A.dtype and bias.device == A.device, lambda: f"bias must be a {A.dtype} tensor on A's device")
+    return N, K
+
+
+@register_fake("bitsandbytes_amd::gemm_4bit_gated")
+def _(A, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: str, bias=None):
+    N, _ = _check_gemm_4bit_gated(A, B, shapeB, absmax, blocksize, quant_type, bias)
+    return torch.empty((*A.shape[:-1], N // 2), dtype=A.dtype, device=A.device)

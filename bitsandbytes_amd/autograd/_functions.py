@@ -239,6 +239,65 @@ def moe_ffn_4bit(
     return y[:, 0] if y.shape[1] == 1 else y.sum(dim=1)
 
 
+def _gated_fused(x: torch.Tensor, quant_state: F.QuantState) -> bool:
+    """Whether the gated launch serves this call - decided from shapes, dtypes and alignment only (nothing is read on the host)."""
+    if x.device.type != "cuda" or quant_state.nested or _is_compiling():
+        return False
+    from ..backends import hip
+
+    N, K = int(quant_state.shape[0]), int(quant_state.shape[1])
+    M = x.numel() // K if K else 0
+    with torch.cuda.device(x.device):  # (the route depends on the current device's CU count)
+        return hip.gemm_4bit_gated_supported(x.dtype, M, N, K, quant_state.blocksize)
+
+
+def matmul_4bit_gated(x: torch.Tensor, gate_up: torch.Tensor, gate_up_state: F.QuantState, bias: Optional[torch.Tensor] = None):
+    """``silu(g) * u`` with ``(g, u) = x @ dequant(gate_up).T (+ bias)`` - the first stage of a dense gated-SiLU FFN (Llama, Mistral,
+    Qwen, Phi-3) - as ONE launch: the activation is the matmul's epilogue. ``gate_up`` / ``gate_up_state``: the packed INTERLEAVED
+    ``[2 F, K]`` matrix, gate row ``i`` at row ``2 i`` and up row ``i`` at row ``2 i + 1``
+    (:func:`bitsandbytes_amd.functional.interleave_gate_up_4bit`), ``bias`` ``[2 F]`` in the same layout. ``x``: ``[*, K]``; returns
+    ``[*, F]``.
+
+    The fused launch exists for 1 ... 16 rows of 16-bit activations where the plain call runs the streaming or the streaming MFMA
+    kernel (``backends.hip.gemm_4bit_gated_supported``) and plain fp32 absmax. Every other call composes
+    ``y = matmul_4bit(x, gate_up, ...)`` with ``F.silu(y[..., 0::2]) * y[..., 1::2]``: the same bits, three or four launches. Neither
+    path reads data on the host, so both can be captured in a graph. Inference only: there is no autograd formula."""
+    if gate_up_state is None:
+        raise ValueError("quant_state is required")
+    if len(gate_up_state.shape) != 2 or int(gate_up_state.shape[0]) % 2:
+        raise ValueError(f"matmul_4bit_gated: quant_state.shape must be [2 F, K], got {list(gate_up_state.shape)}")
+    if torch.is_grad_enabled() and (x.requires_grad or (bias is not None and bias.requires_grad)):
+        raise RuntimeError("matmul_4bit_gated is inference only (no autograd formula): call it under torch.no_grad() "
+                           "or with detached inputs")
+    if x.shape[-1] != gate_up_state.shape[1]:
+        raise ValueError(f"matmul_4bit_gated: x inner dim ({x.shape[-1]}) must equal quant_state.shape[1] ({gate_up_state.shape[1]})")
+    if x.numel() > 0 and gate_up.data_ptr() % 16 == 0 and _gated_fused(x, gate_up_state):
+        xc = x.contiguous()
+        if xc.data_ptr() % 16 == 0 and (bias is None or bias.dtype == x.dtype):
+            return torch.ops.bitsandbytes_amd.gemm_4bit_gated.default(xc, gate_up.view(-1, 1), gate_up_state.shape, gate_up_state.absmax,
+                                                                      gate_up_state.blocksize, gate_up_state.quant_type, bias=bias)
+    y = matmul_4bit(x, gate_up, gate_up_state, bias=bias)
+    return torch.nn.functional.silu(y[..., 0::2]) * y[..., 1::2]
+
+
+def ffn_4bit(
+    x: torch.Tensor,
+    gate_up: torch.Tensor,
+    gate_up_state: F.QuantState,
+    down: torch.Tensor,
+    down_state: F.QuantState,
+    gate_up_bias: Optional[torch.Tensor] = None,
+    down_bias: Optional[torch.Tensor] = None,
+):
+    """One dense gated-SiLU FFN block, ``down(silu(gate(x)) * up(x))``, in two launches where the gated launch serves the call
+    (:func:`matmul_4bit_gated`; its composition otherwise - the same bits): ``gate_up`` is the interleaved ``[2 F, H]`` matrix,
+    ``down`` the ``[H, F]`` one. Bit-identical to the three ``Linear4bit`` layers and torch's ``F.silu(g) * u``. Inference only."""
+    if torch.is_grad_enabled() and down_bias is not None and down_bias.requires_grad:
+        raise RuntimeError("ffn_4bit is inference only (no autograd formula): call it under torch.no_grad() or with detached inputs")
+    h = matmul_4bit_gated(x, gate_up, gate_up_state, bias=gate_up_bias)
+    return matmul_4bit(h, down, down_state, bias=down_bias)
+
+
 def matmul_4bit_grouped(A: torch.Tensor, weights, quant_states, biases=None, outs=None):
     """``[matmul_4bit(A, B_i, state_i, bias=bias_i) for i]`` for 4-bit weights that share their input - the Q/K/V
     projections of an attention block, the gate/up projections of an MLP. On MI355X a decode-sized batch (M <= 4) is

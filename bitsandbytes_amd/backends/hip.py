@@ -20,7 +20,7 @@ from warnings import warn
 
 import torch
 
-from .._ops import GATED_CODES, _check_gemm_4bit_experts, _check_gemm_4bit_experts_ffn, register_kernel
+from .._ops import GATED_CODES, _check_gemm_4bit_experts, _check_gemm_4bit_experts_ffn, _check_gemm_4bit_gated, register_kernel
 from ..cextension import lib
 
 _DT_NAME = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}
@@ -574,6 +574,39 @@ def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str,
             _ptr(bias if bias is None else bias.contiguous()), ids.data_ptr(), ids.element_size(),
             _ptr(scale), 0 if scale is None else _DT_CODE[scale.dtype], GATED_CODES[gated], out.data_ptr(),
             P, S, E, N, K, blocksize, _QT_CODE[quant_type], _stream(A),
+        )
+    return out
+
+
+# ------------------------------------------------------------------------------------------ gemm_4bit_gated
+def gemm_4bit_gated_supported(dtype: torch.dtype, M: int, N: int, K: int, blocksize: int) -> bool:
+    """Whether ``bitsandbytes_amd::gemm_4bit_gated`` has a kernel for ``M`` rows on the interleaved ``[N = 2 F, K]`` matrix: the
+    plain call of that shape runs the streaming or the streaming MFMA kernel, 16-bit activations, ``M <= 16``, blocksize >= 64
+    (pure host logic of the library plus the CU count of the current device, as the route queries)."""
+    if dtype not in (torch.float16, torch.bfloat16) or max(M, N, K) >= 2**31 or min(M, N, K) < 1:
+        return False
+    return bool(lib.bnb_mi355x_gemm_4bit_gated_supported(_DT_CODE[dtype], M, N, K, blocksize))
+
+
+@register_kernel("bitsandbytes_amd::gemm_4bit_gated", "cuda")
+def _(A, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: str, bias=None):
+    """One launch of the streaming kernel's or the streaming MFMA kernel's gated instance - the family the plain call runs."""
+    N, K = _check_gemm_4bit_gated(A, B, shapeB, absmax, blocksize, quant_type, bias)
+    M = A.numel() // K
+    out = torch.empty((*A.shape[:-1], N // 2), dtype=A.dtype, device=A.device)
+    if M == 0:
+        return out
+    A = A.contiguous()
+    B = B.contiguous()
+    absmax = absmax.contiguous()
+    with _device_of(A):
+        # (inside the guard: the route depends on the current device's CU count)
+        if not gemm_4bit_gated_supported(A.dtype, M, N, K, blocksize) or A.data_ptr() % 16 or B.data_ptr() % 16 or absmax.data_ptr() % 4:
+            raise ValueError(f"gemm_4bit_gated: no kernel for M={M}, N={N}, K={K}, blocksize={blocksize}, dtype={A.dtype} "
+                             "(A and B 16-byte aligned); compose gemm_4bit with silu and a multiply - matmul_4bit_gated does")
+        lib.bnb_mi355x_gemm_4bit_gated(
+            _DT_CODE[A.dtype], A.data_ptr(), B.data_ptr(), absmax.data_ptr(), out.data_ptr(),
+            _ptr(bias if bias is None else bias.contiguous()), M, N, K, blocksize, _QT_CODE[quant_type], _stream(A),
         )
     return out
 

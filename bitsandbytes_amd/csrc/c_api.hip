@@ -33,6 +33,9 @@ bool gemv_4bit_grouped(int dtype, const void* A, int count, const uint8_t* const
                        hipStream_t stream);
 void gemv_4bit_stream_tuning(int ns, int sw, int rows_per_wg, int nt, int waves);
 bool gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, bool nested);
+bool gemv_4bit_stream_gated_supported(int dtype, int M, int N, int K, int blocksize);
+bool gemv_4bit_stream_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K,
+                            int blocksize, int quant_type, hipStream_t stream);
 bool gemv_4bit_peer(void* const* bufs, void* epoch_word, int world, int rank, int dtype, const void* A, const uint8_t* B, const float* absmax,
                     const uint8_t* absmax8, const float* absmax_code, const float* absmax_offset, const void* bias, void* out_local,
                     int ns, int K, int blocksize, int quant_type, int mode, long max_values, int wg_limit, uint32_t epoch_offset,
@@ -57,6 +60,10 @@ bool gemm_4bit_sm_grouped(int dtype, const void* A, int count, const uint8_t* co
                           const uint8_t* const* absmax8, const float* const* absmax_code, const float* const* absmax_offset,
                           void* const* out, const void* const* bias, const int* N, int M, int K, int blocksize, int quant_type,
                           hipStream_t stream);
+bool gemm_4bit_sm_serves(const float* absmax, const uint8_t* absmax8, int blocksize);
+bool gemm_4bit_sm_gated_supported(int dtype, const void* A, const uint8_t* B, int M, int N, int K, int blocksize);
+bool gemm_4bit_sm_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K,
+                        int blocksize, int quant_type, hipStream_t stream);
 extern thread_local TlsKnob g_mfma_knob0, g_mfma_knob1;
 // gemm4_grad_input.hip
 bool gemm_4bit_grad_input_supported(int dtype, const void* G, const uint8_t* B, int M, int N, int K, int blocksize);
@@ -124,6 +131,26 @@ void gemm_4bit_dispatch(int kernel, int dtype, const void* A, const uint8_t* B, 
     else
         gemv_4bit_stream(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, code16, out, bias, M, N, K, blocksize,
                          quant_type, stream);
+}
+
+// Gated call (bnb_mi355x_gemm_4bit_gated) on the interleaved [N = 2F, K] matrix at M rows: the kernel FAMILY the plain call on the
+// same matrix and M runs - so that the gated result is the plain result's silu(gate) * up bit for bit - when that family has a gated
+// form: kKernelStream or kKernelSm, else 0 (not supported). 16-bit activations, fp32 absmax, 1 <= M <= 16, blocksize >= 64, whole
+// quantization blocks per row, aligned pointers.
+int gated_family(int dtype, const void* A, const uint8_t* B, const float* absmax, int M, int N, int K, int blocksize) {
+    if ((dtype != 1 && dtype != 2) || M < 1 || M > 16 || N < 2 || (N & 1) || K <= 0 || blocksize < 64 || !is_pow2(blocksize) || (K % blocksize) != 0 ||
+        !aligned_to(A, 16) || !aligned_to(B, 16) || !aligned_to(absmax, 4))
+        return kKernelNone;
+    if (route_to_mfma(0, dtype, A, B, nullptr, M, N, K, blocksize, aligned_to(absmax, 16))) {
+        // (gemm_4bit_mfma's order: the tall-tile knob first, then the streaming MFMA kernel; every other MFMA kernel has no gated form)
+        if (g_mfma_knob1.load(std::memory_order_relaxed) / 100 == 60)
+            return kKernelNone;
+        return gemm_4bit_sm_routes(dtype, M, N, K, blocksize) && gemm_4bit_sm_gated_supported(dtype, A, B, M, N, K, blocksize) &&
+                       gemm_4bit_sm_serves(absmax, nullptr, blocksize)
+                   ? kKernelSm
+                   : kKernelNone;
+    }
+    return gemv_4bit_stream_gated_supported(dtype, M, N, K, blocksize) ? kKernelStream : kKernelNone;
 }
 
 } // namespace
@@ -412,6 +439,32 @@ void bnb_mi355x_gemm_4bit_experts_ffn(int dtype, const void* A, long a_slot_stri
 }
 int bnb_mi355x_gemm_4bit_experts_ffn_supported(int dtype, int E, int N, int K, int blocksize, int gated) {
     return gemm_4bit_experts_ffn_supported(dtype, E, N, K, blocksize, gated) ? 1 : 0;
+}
+
+// ------------------------------------------------------------------ gated gemm_4bit (dense FFN: silu(gate) * up as the epilogue)
+void bnb_mi355x_gemm_4bit_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N,
+                                int K, int blocksize, int quant_type, bnb_stream_t s) {
+    if (quant_type != kFP4 && quant_type != kNF4) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_gated: quant_type must be 1 (FP4) or 2 (NF4), got %d\n", quant_type);
+        exit(1);
+    }
+    const int family = gated_family(dtype, A, B, absmax, M, N, K, blocksize);
+    const bool ok = family == kKernelSm       ? gemm_4bit_sm_gated(dtype, A, B, absmax, out, bias, M, N, K, blocksize, quant_type, S(s))
+                    : family == kKernelStream ? gemv_4bit_stream_gated(dtype, A, B, absmax, out, bias, M, N, K, blocksize, quant_type, S(s))
+                                              : false;
+    if (!ok) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_gated: no kernel for dtype %d, M=%d, N=%d, K=%d, blocksize=%d (ask bnb_mi355x_gemm_4bit_gated_supported, align A / B to 16 bytes)\n",
+                dtype, M, N, K, blocksize);
+        exit(1);
+    }
+}
+int bnb_mi355x_gemm_4bit_gated_supported(int dtype, int M, int N, int K, int blocksize) {
+    // (alignment of A / B / absmax is unknown here; the aligned case is assumed, as in the route query)
+    static const int dummy_aligned[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
+    return gated_family(dtype, dummy_aligned, reinterpret_cast<const uint8_t*>(dummy_aligned), reinterpret_cast<const float*>(dummy_aligned), M, N, K,
+                        blocksize) != kKernelNone
+               ? 1
+               : 0;
 }
 
 // ------------------------------------------------------------------ peer chain (the all-gather fused into the gemv launches)

@@ -149,7 +149,10 @@ __device__ __forceinline__ int sm_swz(int m) { return (m & 3) | ((m & 4) << 1); 
 // the ring stage of an item must be a compile-time index); NESTED: double-quantised statistics; SINGLE: no wavefront has more
 // than ONE item (K <= 256 WAVES and one tile - the headline shape): no ring, no refill requests.
 // grid = (ceil(N / R), ceil(M / 16)); hot_geom = R | fp4 << 16 | bs_shift << 20 | members of a grouped launch << 25.
-template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false>
+// GATED (dense FFN, bnb_mi355x_gemm_4bit_gated): the weight rows are (gate, up) pairs of ONE interleaved [2F, K] matrix - row 2 i = gate
+// row i, row 2 i + 1 = up row i - and the epilogue stores out[m, i] = T(T(silu(g)) * u), [M, F]; the host keeps R even (sm_plan), so a
+// pair never straddles two workgroups. Everything in front of the combine step is the plain kernel's.
+template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false, bool GATED = false>
 __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
     // hot arguments as separate scalars: preloaded into SGPRs by the command processor (14 dwords)
     const void* hot_A, const uint8_t* hot_B, const float* hot_absmax, const uint8_t* hot_absmax8, const float* hot_code2, int hot_M,
@@ -179,6 +182,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
     static_assert(ROWS == 4 || ROWS == 8 || ROWS == 16 || ROWS == 32, "staged activation rows");
     static_assert(ROWS != 32 || (!SINGLE && WAVES == 8), "32-row instances: ring, 8 wavefronts");
     static_assert(TT >= 1 && TT <= kSmMaxTiles && (!SINGLE || TT == 1), "tiles per workgroup");
+    static_assert(!GATED || (ROWS != 32 && !GROUPED && !NESTED && ORDER == 0), "gated instances: up to 16 rows, one matrix, fp32 absmax");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -543,6 +547,10 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
     BNB_SM_STAMP(9)
     constexpr int PARTS = 4, WPP = WAVES * V / PARTS; // (virtual wavefront v = set v / WAVES of wavefront v % WAVES)
     const int nout = TT * 16 * ROWS;
+    // (gated) the (gate, up) sums, batch row and gate row this lane finishes behind the loop: see there
+    static_assert(!GATED || TT * ROWS <= 8 * WAVES, "gated: at most eight trips of the combine loop, one kept pair per lane");
+    [[maybe_unused]] float kept_g = 0.0f, kept_u = 0.0f;
+    [[maybe_unused]] int kept_m = M, kept_n = 0, trip = 0;
     for (int idx = tid; idx < nout * PARTS; idx += THREADS) {
         const int o = idx >> 2, part = idx & 3;
         const int col = o & 15, m = (o >> 4) & (ROWS - 1), t = o / (16 * ROWS);
@@ -560,10 +568,38 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
         v = dpp_add<0xB1>(v);
         v = dpp_add<0x4E>(v);
         const int mm = m_base + m, n = row0 + 16 * t + col;
+        if constexpr (GATED) {
+            // the outputs of weight columns col and col ^ 1 sit four lanes apart (lane = 4 col + part; nout * PARTS is a multiple of
+            // 64: whole wavefronts run every trip): one lane permute gives each of the EIGHT lanes of a (gate, up) pair both sums.
+            // The activation - exact expf and an IEEE division, ~150 VALU instructions - is not computed here, by one lane in eight
+            // and once per trip (up to eight trips: 2 us at sixteen rows of a 28672-row matrix), but ONCE behind the loop: lane j of
+            // the eight keeps the pair of trip j.
+            const float vo = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ 4) << 2, __builtin_bit_cast(int, v)));
+            const bool odd = (col & 1) != 0;
+            if ((((col & 1) << 2) | part) == trip) {
+                kept_g = odd ? vo : v;
+                kept_u = odd ? v : vo;
+                kept_m = mm;
+                kept_n = n & ~1;
+            }
+            ++trip;
+        } else
         if (part == 0 && mm < M && n < row_end) {
             const T* bias = static_cast<const T*>(g_bias);
             const float b = bias ? static_cast<float>(bias[n]) : 0.0f;
             static_cast<T*>(g_out)[static_cast<long>(mm) * N + n] = static_cast<T>(v + b);
+        }
+    }
+    if constexpr (GATED) {
+        // the arithmetic of the streaming kernel's gated epilogue: torch's `F.silu(g) * u` on the plain call's output, bit for bit
+        if (kept_m < M && kept_n + 1 < row_end) {
+            const T* bias = static_cast<const T*>(g_bias);
+            const float bg = bias ? static_cast<float>(bias[kept_n]) : 0.0f;
+            const float bu = bias ? static_cast<float>(bias[kept_n + 1]) : 0.0f;
+            const float gf = static_cast<float>(static_cast<T>(rounded_f32(kept_g + bg)));
+            const float uf = static_cast<float>(static_cast<T>(rounded_f32(kept_u + bu)));
+            const T st = static_cast<T>(rounded_f32(gf / (1.0f + expf(-gf))));
+            static_cast<T*>(g_out)[static_cast<long>(kept_m) * (N >> 1) + (kept_n >> 1)] = static_cast<T>(rounded_f32(__fmul_rn(static_cast<float>(st), uf)));
         }
     }
 #ifdef BNB_PROFILING
@@ -583,16 +619,20 @@ struct SmPlan {
     int R, tt, grid_x, rows;
     int variant = 0; // experiment bits (bnb_mi355x_set_tuning knob0)
     bool grouped = false;
+    bool gated = false; // (gate, up) row pairs: R even
 };
 
 // rows per workgroup: one workgroup per CU when 64 rows are enough, else whole rounds of workgroups
-SmPlan sm_plan(int M, int N) {
+SmPlan sm_plan(int M, int N, bool gated = false) {
     SmPlan pl;
     const int cus = sm_cu_count();
     const long per_round = static_cast<long>(cus) * 16 * kSmMaxTiles;
     const int rounds = static_cast<int>((N + per_round - 1) / per_round);
     int R = (N + cus * rounds - 1) / (cus * rounds);
     R = R < 16 ? 16 : R;
+    if (gated)
+        R += R & 1; // (R <= 16 kSmMaxTiles by construction, an even bound: 4352 rows on 256 CUs give 17 -> 18)
+    pl.gated = gated;
     pl.R = R;
     pl.tt = (R + 15) / 16;
     pl.grid_x = (N + R - 1) / R;
@@ -602,14 +642,14 @@ SmPlan sm_plan(int M, int N) {
     return pl;
 }
 
-template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false>
+template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false, bool GATED = false>
 void sm_launch_one(const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* code2, int M, int N, int K, int geom,
                    const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
     constexpr int V = (ROWS < 16 && WAVES == 8) ? 2 : 1; // (accumulator sets per tile: the kernel's V)
     constexpr int RB = ROWS == 32 ? 2 : 1, SROWS = ROWS == 32 ? 16 : ROWS;
     constexpr size_t region = (SROWS * 512 + kSmScratch) > V * TT * RB * 1024 ? (SROWS * 512 + kSmScratch) : V * TT * RB * 1024;
     constexpr size_t lds = kSmLut + kSmCode2 + static_cast<size_t>(WAVES) * region;
-    auto kern = gemm4_mfma_sm_kernel<T, ROWS, WAVES, TT, NESTED, SINGLE, ORDER, GROUPED>;
+    auto kern = gemm4_mfma_sm_kernel<T, ROWS, WAVES, TT, NESTED, SINGLE, ORDER, GROUPED, GATED>;
     static LdsLimit lim;
     ensure_dynamic_lds(lim, reinterpret_cast<const void*>(kern), lds);
     hipLaunchKernelGGL(kern, dim3(pl.grid_x, (M + 16 * RB - 1) / (16 * RB)), dim3(WAVES * 64), lds, stream, A, B, absmax, absmax8, code2, M, N, K, geom, a);
@@ -619,6 +659,15 @@ template <typename T, int ROWS, int WAVES, int TT>
 void sm_launch_kind(const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* code2, int M, int N, int K, int geom,
                     const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
     const bool nested = absmax8 != nullptr;
+    if constexpr (ROWS != 32) {
+        if (pl.gated) { // (fp32 absmax, one matrix: gemm_4bit_sm_gated checks)
+            if constexpr (TT == 1) {
+                if ((K + kSmChunk - 1) / kSmChunk <= WAVES)
+                    return sm_launch_one<T, ROWS, WAVES, 1, false, true, 0, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+            }
+            return sm_launch_one<T, ROWS, WAVES, TT, false, false, 0, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+        }
+    }
     if (pl.grouped) { // (ring instances only)
         if (nested)
             return sm_launch_one<T, ROWS, WAVES, TT, true, false, 0, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
@@ -702,6 +751,35 @@ void gemm_4bit_sm(int dtype, const void* A, const uint8_t* B, const float* absma
     else
         sm_launch_rows<f16>(A, B, absmax, absmax8, absmax_code, M, N, K, geom, pl, a, stream);
     BNB_CHECK_LAUNCH();
+}
+
+// Gated form (see the kernel's GATED): B [N = 2 F, K] interleaved, bias [N], out [M, F]. 2 <= ... M <= 16 (the 4-, 8- and 16-row
+// instances), fp32 absmax. false - nothing launched - outside these preconditions.
+bool gemm_4bit_sm_gated_supported(int dtype, const void* A, const uint8_t* B, int M, int N, int K, int blocksize) {
+    return M <= 16 && N >= 2 && !(N & 1) && gemm_4bit_sm_supported(dtype, A, B, nullptr, M, N, K, blocksize);
+}
+bool gemm_4bit_sm_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K,
+                        int blocksize, int quant_type, hipStream_t stream) {
+    if (!gemm_4bit_sm_gated_supported(dtype, A, B, M, N, K, blocksize) || !gemm_4bit_sm_serves(absmax, nullptr, blocksize))
+        return false;
+    const SmPlan pl = sm_plan(M, N, true);
+    if (pl.rows > 16 || (pl.R & 1) || pl.tt > kSmMaxTiles)
+        return false;
+    SmArgs a{};
+#ifdef BNB_PROFILING
+    a.dbg = nullptr;
+#endif
+    a.absmax_offset = nullptr;
+    a.out = out;
+    a.bias = bias;
+    const int geom = pl.R | ((quant_type == kFP4) ? (1 << 16) : 0) | (ilog2(blocksize) << 20);
+    if (dtype == 2)
+        sm_launch_rows<bf16>(A, B, absmax, nullptr, nullptr, M, N, K, geom, pl, a, stream);
+    else
+        sm_launch_rows<f16>(A, B, absmax, nullptr, nullptr, M, N, K, geom, pl, a, stream);
+    BNB_CHECK_LAUNCH();
+    g_last_gemm_kernel = kKernelSm;
+    return true;
 }
 
 // Several weight matrices that share the activations (Q/K/V, gate/up; reference: one gemm_4bit per Linear4bit, nn/modules.py:609-637)

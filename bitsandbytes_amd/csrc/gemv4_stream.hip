@@ -62,7 +62,8 @@ enum StreamFlags : int {
     kMulti = 32,   // rows longer than the workgroup's segment columns: several phases (a loop around the whole body)
     kPeer = 64,    // "peer chain" form (M = 1): x taken from / y delivered to the ranks' exchange buffers - see PeerChain
     kExact = 128,  // exact geometry (M = 1, K = 4096: SW = 2, G = 8, every row, lane and ring position valid): see launch_one
-    kLateArgs = 256 // sweep-only: the epilogue's out / bias pointers loaded where they are used (the form up to round 6; A/B runs)
+    kLateArgs = 256, // sweep-only: the epilogue's out / bias pointers loaded where they are used (the form up to round 6; A/B runs)
+    kGated = 512     // rows are (gate, up) pairs of ONE interleaved [2F, K] matrix: out[m, i] = silu(row 2 i) * (row 2 i + 1), [M, F]
 };
 
 // One weight matrix of a launch.
@@ -214,6 +215,12 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     constexpr bool NESTED = FLAGS & kNested, CODEPTR = FLAGS & kCodePtr, NT = FLAGS & kNT, GROUPED = FLAGS & kGrouped;
     constexpr bool MULTI = FLAGS & kMulti;
     constexpr bool PEER = (FLAGS & kPeer) != 0;
+    // Gated epilogue (dense FFN on one device, bnb_mi355x_gemm_4bit_gated): everything in front of the epilogue is the plain kernel's;
+    // the host keeps the first row and the row count of every workgroup even (make_geometry, pairs), so a (gate, up) pair never
+    // straddles two workgroups.
+    constexpr bool GATED = (FLAGS & kGated) != 0;
+    static_assert(!GATED || (!PEER && !GROUPED && !NESTED && !CODEPTR && !(FLAGS & kLateArgs) && TypeInfo<T>::bytes == 2),
+                  "the gated form: one matrix, fp32 absmax, literal table, 16-bit activations");
     static_assert(!PEER || (MB == 1 && !MULTI && !GROUPED && WAVES == 16), "the peer-chain form is the M = 1, single-phase kernel");
     // Exact geometry: the host selects this instance only when K = kExactSW * 2048, M = 1 and the rows divide evenly over workgroups
     // and row groups with at least one ring position each (exact_geometry()). Everything the general instance decides at run time in
@@ -770,6 +777,33 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
         epoch_out = epoch + 1u;
     __syncthreads();
     BNB_ST_STAMP(7)
+    if constexpr (GATED) {
+        // the thread of output column c adds the segment partials of local rows 2 c (gate) and 2 c + 1 (up) - each in segment order, as
+        // the plain epilogue does - and stores ONE value: T(T(silu(g)) * u) with g = T(acc_g + bias_g), u = T(acc_u + bias_u); silu in
+        // fp32 (exact expf, IEEE division), each step rounded to T once: torch's `F.silu(g) * u` on the plain call's output, bit for bit
+        // (the arithmetic of the peer chain's gated production above)
+        const int npairs = nrows >> 1;
+        const T* const bias = reinterpret_cast<const T*>(ep_bias);
+        T* const out = reinterpret_cast<T*>(ep_out);
+        const int out_f = hot_N >> 1;
+        for (int idx = tid; idx < npairs * MB; idx += THREADS) {
+            const int m = (MB == 1) ? 0 : idx / npairs, c = idx - m * npairs;
+            if (m0 + m >= M)
+                continue;
+            float vg = 0.0f, vu = 0.0f;
+            for (int sg = 0; sg < S; ++sg) {
+                vg += part[((2 * c) * S + sg) * MB + m];
+                vu += part[((2 * c + 1) * S + sg) * MB + m];
+            }
+            const int row = row_begin + 2 * c;
+            const float bg = bias ? static_cast<float>(bias[row]) : 0.0f;
+            const float bu = bias ? static_cast<float>(bias[row + 1]) : 0.0f;
+            const float gf = static_cast<float>(static_cast<T>(rounded_f32(vg + bg)));
+            const float uf = static_cast<float>(static_cast<T>(rounded_f32(vu + bu)));
+            const T st = static_cast<T>(rounded_f32(gf / (1.0f + expf(-gf))));
+            out[static_cast<long>(m0 + m) * out_f + (row >> 1)] = static_cast<T>(rounded_f32(__fmul_rn(static_cast<float>(st), uf)));
+        }
+    } else
     for (int idx = tid; idx < nrows * MB; idx += THREADS) {
         const int m = (MB == 1) ? 0 : idx / nrows, rl = idx - m * nrows;
         if (m0 + m >= M)
@@ -943,7 +977,7 @@ struct Geometry {
 //       left for the activation image; P = ceil(S / SW) phases re-use the workgroup for longer rows;
 //   G   row groups = WAVES / SW; wavefront (sw, g) walks rows g, g + G, ... of the workgroup;
 //   R   rows per workgroup: one workgroup per CU unless the partial-sum slots of that many rows do not fit.
-Geometry make_geometry(int rows_total, int K, int mb, int waves, int tbytes, bool grouped, int tune_sw, int tune_rows) {
+Geometry make_geometry(int rows_total, int K, int mb, int waves, int tbytes, bool grouped, int tune_sw, int tune_rows, bool pairs = false) {
     Geometry ge;
     const int S = (K + kSegK - 1) / kSegK;
     const int cus = device_cu_count();
@@ -968,6 +1002,10 @@ Geometry make_geometry(int rows_total, int K, int mb, int waves, int tbytes, boo
         R = 0xFFFF;
     if (R < 1)
         R = 1;
+    // (gated launches) rows come in (gate, up) pairs: an even row count per workgroup - so every workgroup starts on a gate row -,
+    // rounded UP where the row split gave an odd one, down where the partial-sum slots clamp it (R = 1 then: the caller refuses)
+    if (pairs && (R & 1))
+        R = (R + 1 <= r_cap && R + 1 <= 0xFFFF) ? R + 1 : R - 1;
     ge.R = R;
     ge.P = (S + sw - 1) / sw;
     ge.grid_x = (rows_total + R - 1) / R;
@@ -995,10 +1033,12 @@ bool exact_geometry(const Geometry& ge, int M, int rows_total, int K, int ns) {
            rows_total % ge.R == 0 && ge.R % ge.G == 0 && ge.R >= ns * ge.G;
 }
 // instances that have an exact-geometry twin: 16-bit activations, MB = 1, 16 wavefronts, the production ring, literal tables, fp32
-// absmax. (Nested statistics: the exact form was built and measured BEHIND the general one at 4096^2 - FP4 bs 128 nested 4.50 against
+// absmax - plain or gated (the gated launch of 8192 x 4096 and 28672 x 4096, the interleaved matrices of 4096- and 14336-wide FFNs, was
+// 0.5 - 0.8 us behind the plain launch while it ran the general instance against the plain call's exact one: DESIGN 3.12).
+// (Nested statistics: the exact form was built and measured BEHIND the general one at 4096^2 - FP4 bs 128 nested 4.50 against
 // 4.36 us - and is not instantiated: DESIGN 6b.)
 template <typename T, int MB, int WAVES, int NS, int FLAGS> constexpr bool has_exact_twin() {
-    return TypeInfo<T>::bytes == 2 && MB == 1 && WAVES == 16 && NS == kRing && (FLAGS & ~kFp4) == kNT;
+    return TypeInfo<T>::bytes == 2 && MB == 1 && WAVES == 16 && NS == kRing && (FLAGS & ~(kFp4 | kGated)) == kNT;
 }
 // stream tuning knob `nt`, values above 1 (A/B of the fixed-cost levers, tools/stream_fixed_cost_ab.py): 2 = the general instance where
 // the exact one would be selected, 3 = the general instance with the epilogue's pointers loaded late (bf16, NF4 fp32-absmax and
@@ -1007,7 +1047,13 @@ constexpr int kTuneGeneral = 2, kTuneLateArgs = 3;
 
 template <typename T, int MB, int WAVES, int NS, int FLAGS> void launch_one(const StreamArgs& a, hipStream_t stream) {
     const Geometry ge = make_geometry(a.rows_total, a.K, MB, WAVES, TypeInfo<T>::bytes, (FLAGS & kGrouped) != 0, g_tune.sw.load(std::memory_order_relaxed),
-                                      g_tune.rows.load(std::memory_order_relaxed));
+                                      g_tune.rows.load(std::memory_order_relaxed), (FLAGS & kGated) != 0);
+    if constexpr ((FLAGS & kGated) != 0) {
+        if (ge.R < 2 || (ge.R & 1) || (a.rows_total & 1)) { // (gemv_4bit_stream_gated_supported asks the same question)
+            fprintf(stderr, "bitsandbytes_amd: gemm_4bit_gated: internal error, odd rows per workgroup\n");
+            exit(1);
+        }
+    }
     dim3 grid(ge.grid_x, (a.M + MB - 1) / MB);
     const StreamMat& m0 = a.mat[0];
     // the one launch of this function: every instance takes the same arguments
@@ -1384,6 +1430,56 @@ void gemv_4bit_stream(int dtype, const void* A, const uint8_t* B, const float* a
     else
         launch_generic<bf16>(p, stream);
     BNB_CHECK_LAUNCH();
+}
+
+// Gated form (dense FFN, bnb_mi355x_gemm_4bit_gated): ONE interleaved matrix B [N = 2 F, K] - row 2 i = gate row i, row 2 i + 1 = up
+// row i -, bias [N] in the same layout, out [M, F] = silu(gate) * up. The instances the plain call of the same shape runs (launch_mb:
+// one row -> 16 wavefronts, two -> 16 or 8, more -> passes of four on 8), production ring, non-temporal loads, with the gated
+// epilogue; 16-bit activations and fp32 absmax only. The shape half of the preconditions, shared with the host layer's query:
+static int gated_mb(int M) { return M == 1 ? 1 : M == 2 ? 2 : 4; }
+static int gated_waves(int M, int N, int K) { return M == 1 ? 16 : (M == 2 && make_geometry(N, K, 2, 16, 2, false, 0, 0, true).P == 1) ? 16 : 8; }
+bool gemv_4bit_stream_gated_supported(int dtype, int M, int N, int K, int blocksize) {
+    if ((dtype != 1 && dtype != 2) || M < 1 || N < 2 || (N & 1) || K <= 0 || (K % 32) != 0 || K > 511 * kSegK || blocksize < 32 || !is_pow2(blocksize))
+        return false;
+    const Geometry ge = make_geometry(N, K, gated_mb(M), gated_waves(M, N, K), 2, false, g_tune.sw.load(std::memory_order_relaxed),
+                                      g_tune.rows.load(std::memory_order_relaxed), true);
+    return ge.R >= 2 && !(ge.R & 1);
+}
+template <typename T, int FLAGS> static void launch_gated(const StreamArgs& a, hipStream_t stream) {
+    if (a.M == 1)
+        return launch_one<T, 1, 16, kRing, FLAGS>(a, stream);
+    if (a.M == 2 && gated_waves(2, a.rows_total, a.K) == 16)
+        return launch_one<T, 2, 16, kRing, FLAGS>(a, stream);
+    if (a.M == 2)
+        return launch_one<T, 2, 8, kRing, FLAGS>(a, stream);
+    launch_one<T, 4, 8, kRing, FLAGS>(a, stream);
+}
+// false - nothing launched - when the call is outside the form's preconditions
+bool gemv_4bit_stream_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K,
+                            int blocksize, int quant_type, hipStream_t stream) {
+    if (!gemv_4bit_stream_gated_supported(dtype, M, N, K, blocksize) || !stream_ok(A, M, K, blocksize) || !aligned_to(B, 16) || !aligned_to(absmax, 4))
+        return false;
+    StreamArgs a;
+#ifdef BNB_PROFILING
+    a.dbg = nullptr;
+#endif
+    a.A = A;
+    a.code16 = nullptr;
+    a.M = M;
+    a.K = K;
+    a.bs_shift = ilog2(blocksize);
+    a.rows_total = N;
+    a.nmat = 1;
+    for (int i = 0; i < kMaxGroup; ++i)
+        a.mat[i] = StreamMat{B, absmax, nullptr, nullptr, nullptr, out, bias, N, i == 0 ? 0 : 0x7FFFFFFF};
+    const bool fp4 = quant_type == kFP4;
+    if (dtype == 2)
+        fp4 ? launch_gated<bf16, kNT | kGated | kFp4>(a, stream) : launch_gated<bf16, kNT | kGated>(a, stream);
+    else
+        fp4 ? launch_gated<f16, kNT | kGated | kFp4>(a, stream) : launch_gated<f16, kNT | kGated>(a, stream);
+    BNB_CHECK_LAUNCH();
+    g_last_gemm_kernel = kKernelStream;
+    return true;
 }
 
 // Grouped launch: `count` weight matrices (same K, blocksize, quant_type, nested-ness) applied to the same

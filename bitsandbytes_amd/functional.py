@@ -526,6 +526,76 @@ def dequantize_nf4(A, quant_state=None, absmax=None, out=None, blocksize=None):
     return dequantize_4bit(A, quant_state, absmax, out, blocksize, "nf4")
 
 
+def plain_absmax_4bit(quant_state: QuantState) -> Tensor:
+    """fp32 absmax of a (possibly double-quantised) 4-bit state: exactly the values the nested kernels reconstruct - two roundings,
+    the product ``code2[q8] * absmax2`` and the sum with the offset, what ``dequantize_blockwise`` and a torch add compute."""
+    if not quant_state.nested:
+        return quant_state.absmax.float()
+    return (dequantize_blockwise(quant_state.absmax, quant_state.state2) + quant_state.offset).float()
+
+
+def interleave_gate_up_4bit(gate: Tensor, gate_state: QuantState, up: Optional[Tensor] = None, up_state: Optional[QuantState] = None):
+    """The interleaved ``[2 F, K]`` matrix of a dense gated FFN's first stage - gate row ``i`` at row ``2 i``, up row ``i`` at row
+    ``2 i + 1`` - from ALREADY quantized weights, for :func:`bitsandbytes_amd.matmul_4bit_gated` / ``ffn_4bit``:
+
+    * two members: ``gate`` / ``gate_state`` and ``up`` / ``up_state``, both ``[F, K]`` (``gate_proj``, ``up_proj``);
+    * one chunked member (``up`` and ``up_state`` omitted): ``gate`` / ``gate_state`` is ``[2 F, K]`` with the gate rows first
+      (``torch.chunk(2, -1)`` of its output: Phi-3's ``gate_up_proj``).
+
+    Packed bytes and absmax are row-major over ``[N, K]``; with whole quantization blocks and whole bytes per row
+    (``K % blocksize == 0``, ``K`` even) permuting the packed rows and the absmax rows IS the quantized form of the permuted matrix:
+    nothing is requantized, and dequantizing the result gives the row-interleave of the members' dequantized weights bit for bit.
+    Nested (double-quantised) statistics are carried un-nested as fp32 - the values the nested kernels reconstruct
+    (:func:`plain_absmax_4bit`); the members keep their own offsets and second-level tables, which one matrix cannot. That costs
+    ``4 / blocksize`` bytes per weight (0.0625 at blocksize 64) against ~``1 / blocksize`` nested.
+
+    Returns ``(packed [F * K, 1] uint8, QuantState)`` with shape ``[2 F, K]`` and plain fp32 absmax. The result is a second copy of
+    the members' packed weights: release theirs if the members are not used on their own (``nn.FFN4bit.from_linears`` does)."""
+    chunked = up is None
+    if chunked != (up_state is None):
+        raise ValueError("interleave_gate_up_4bit: give up and up_state together, or neither (one chunked [2 F, K] weight)")
+    states = (gate_state,) if chunked else (gate_state, up_state)
+    for st in states:
+        if st is None or len(st.shape) != 2:
+            raise ValueError("interleave_gate_up_4bit: quant states with a 2-D shape [N, K] are required")
+        if st.nested and st.state2.blocksize != 256:
+            raise NotImplementedError("nested quantization with state2.blocksize != 256 is not supported")
+    rows, K = int(gate_state.shape[0]), int(gate_state.shape[1])
+    bs = gate_state.blocksize
+    if K % bs != 0 or K % 2 != 0:
+        raise ValueError(f"interleave_gate_up_4bit: rows must be whole quantization blocks and whole bytes (K = {K}, blocksize {bs}); "
+                         "quantize the interleaved fp weight instead")
+    if chunked:
+        if rows % 2:
+            raise ValueError(f"interleave_gate_up_4bit: a chunked weight needs an even row count, got {rows}")
+        F_ = rows // 2
+    else:
+        if tuple(up_state.shape) != (rows, K) or up_state.blocksize != bs or up_state.quant_type != gate_state.quant_type:
+            raise ValueError("interleave_gate_up_4bit: gate and up must have the same shape, blocksize and quant_type")
+        F_ = rows
+
+    def packed_rows(w, n):
+        w = w.reshape(-1)
+        if w.dtype != torch.uint8:
+            w = w.view(torch.uint8)
+        if w.numel() != n * K // 2:
+            raise ValueError(f"interleave_gate_up_4bit: packed weight holds {w.numel()} bytes, its state says {n * K // 2}")
+        return w.view(n, K // 2)
+
+    if chunked:
+        w2 = packed_rows(gate, rows).view(2, F_, K // 2)
+        a2 = plain_absmax_4bit(gate_state).reshape(2, F_, K // bs)
+        wg, wu, ag, au = w2[0], w2[1], a2[0], a2[1]
+    else:
+        wg, wu = packed_rows(gate, F_), packed_rows(up, F_)
+        ag, au = plain_absmax_4bit(gate_state).reshape(F_, K // bs), plain_absmax_4bit(up_state).reshape(F_, K // bs)
+    packed = torch.stack([wg, wu], dim=1).reshape(-1, 1).contiguous()
+    absmax = torch.stack([ag, au], dim=1).reshape(-1).contiguous()
+    state = QuantState(absmax=absmax, shape=torch.Size((2 * F_, K)), code=gate_state.code, blocksize=bs,
+                       quant_type=gate_state.quant_type, dtype=gate_state.dtype)
+    return packed, state
+
+
 def gemv_4bit(A: Tensor, B: Tensor, out: Optional[Tensor] = None, transposed_A=False, transposed_B=False,
               state: Optional[QuantState] = None) -> Tensor:
     """Legacy single-row fused dequant + matvec (reference functional.py:1300-1334): nested absmax is

@@ -3,6 +3,7 @@ from .modules import (
     Embedding4bit,
     EmbeddingFP4,
     EmbeddingNF4,
+    FFN4bit,
     Linear4bit,
     LinearFP4,
     LinearNF4,
@@ -11,4 +12,4 @@ from .modules import (
 )
 
 __all__ = ["Linear4bit", "LinearFP4", "LinearNF4", "Params4bit", "Embedding4bit", "EmbeddingFP4", "EmbeddingNF4",
-           "parametrize", "linear4bit_group_forward"]
+           "parametrize", "linear4bit_group_forward", "FFN4bit"]

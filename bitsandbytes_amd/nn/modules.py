@@ -419,6 +419,83 @@ def linear4bit_group_forward(layers, x: torch.Tensor):
     return [y.to(inp_dtype) for y in ys]
 
 
+class FFN4bit(nn.Module):
+    """One dense gated-SiLU FFN block, ``down(silu(gate(x)) * up(x))`` (Llama, Mistral, Qwen, Phi-3), as TWO launches for a decode
+    step on one GPU: the gate and up rows live in ONE interleaved ``[2 F, H]`` matrix (``functional.interleave_gate_up_4bit``) and
+    the activation is the epilogue of its matmul (:func:`bitsandbytes_amd.ffn_4bit`). Outputs are bit-identical to the three
+    :class:`Linear4bit` layers with torch's ``F.silu(g) * u``, whatever the batch: calls the gated launch does not serve (more than
+    16 rows, fp32, shapes whose plain call runs another kernel family) compose the plain matmul on the interleaved matrix with
+    torch's ``silu`` and ``*``. Inference only.
+
+    Build it with :meth:`from_linears` AFTER the checkpoint is loaded and the layers are quantized on the device. The block is not
+    part of any state dict: its buffers are derived from the members', which keep owning what a checkpoint stores. The interleaved
+    matrix is a second copy of the gate / up packed weights (``F * H`` bytes) plus their statistics as fp32 (``4 / blocksize`` bytes
+    per weight, nested or not); with ``keep_members=False`` the two members' packed buffers are released, so the block does not
+    double its gate / up memory - the two layers cannot be called on their own afterwards."""
+
+    def __init__(self, gate_up: torch.Tensor, gate_up_state, down: "Linear4bit", gate_up_bias: Optional[torch.Tensor] = None,
+                 compute_dtype=None):
+        super().__init__()
+        self.register_buffer("gate_up", gate_up, persistent=False)
+        self.register_buffer("gate_up_absmax", gate_up_state.absmax, persistent=False)
+        self.register_buffer("gate_up_bias", gate_up_bias, persistent=False)
+        self.gate_up_state = gate_up_state
+        self.compute_dtype = compute_dtype
+        # (the members are referenced, not registered: they stay where the model holds them, and state_dict() of the block is empty)
+        object.__setattr__(self, "down", down)
+        object.__setattr__(self, "members", None)
+
+    @classmethod
+    def from_linears(cls, gate: "Linear4bit", up: "Linear4bit", down: "Linear4bit", keep_members: bool = False) -> "FFN4bit":
+        for layer in (gate, up, down):
+            fix_4bit_weight_quant_state_from_module(layer)
+            if getattr(layer.weight, "quant_state", None) is None:
+                raise ValueError("FFN4bit.from_linears: the layers must be quantized (load the checkpoint and move the model to the device first)")
+        if gate.compute_dtype != up.compute_dtype or gate.compute_dtype != down.compute_dtype:
+            raise ValueError("FFN4bit.from_linears: gate, up and down must share one compute dtype")
+        if gate.out_features != up.out_features or gate.out_features != down.in_features or gate.in_features != up.in_features:
+            raise ValueError("FFN4bit.from_linears: gate / up must be [F, H] layers and down must take what they produce")
+        packed, state = F.interleave_gate_up_4bit(gate.weight.data, gate.weight.quant_state, up.weight.data, up.weight.quant_state)
+        bias = None
+        if gate.bias is not None or up.bias is not None:
+            ref = gate.bias if gate.bias is not None else up.bias
+            parts = [b.detach() if b is not None else torch.zeros_like(ref) for b in (gate.bias, up.bias)]
+            bias = torch.stack([parts[0], parts[1].to(parts[0].dtype)], dim=1).reshape(-1).contiguous()  # interleaved like the rows
+        block = cls(packed, state, down, bias, gate.compute_dtype)
+        if keep_members:
+            object.__setattr__(block, "members", (gate, up))
+        else:
+            for layer in (gate, up):
+                layer._prepared_drop()  # (a prepared call keeps the packed weight alive)
+                layer.weight.data = torch.empty(0, dtype=layer.weight.dtype, device=layer.weight.device)
+        return block
+
+    def _apply(self, fn, recurse=True):
+        out = super()._apply(fn, recurse)
+        self.gate_up_state.absmax = self.gate_up_absmax  # (the state's absmax IS the moved buffer)
+        return out
+
+    def forward(self, x: torch.Tensor):
+        from ..autograd import ffn_4bit, matmul_4bit
+
+        down = self.down
+        fix_4bit_weight_quant_state_from_module(down)
+        inp_dtype = x.dtype
+        cd = self.compute_dtype
+        xc = x if cd is None else x.to(cd)
+        gb = self.gate_up_bias
+        if gb is not None and gb.dtype != xc.dtype:
+            gb = gb.to(xc.dtype)
+        if xc.dtype != inp_dtype:
+            # a compute dtype other than the input's: the members round g and u to the input dtype before the activation
+            y = matmul_4bit(xc, self.gate_up, self.gate_up_state, bias=gb).to(inp_dtype)
+            return down(torch.nn.functional.silu(y[..., 0::2]) * y[..., 1::2])
+        db = down.bias
+        if db is not None and db.dtype != xc.dtype:
+            db = db.to(xc.dtype)
+        return ffn_4bit(xc, self.gate_up, self.gate_up_state, down.weight, down.weight.quant_state, gate_up_bias=gb, down_bias=db)
+
+
 class LinearFP4(Linear4bit):
     def __init__(self, input_features, output_features, bias=True, compute_dtype=None, compress_statistics=True,
                  quant_storage=torch.uint8, device=None):

@@ -177,6 +177,18 @@ int bnb_mi355x_gemm_4bit_experts_supported(int dtype, int E, int N, int K, int b
  * expert. bnb_mi355x_gemm_4bit_experts_ffn_supported: the predicate above, and N even when gated != 0 (pure host logic). */
 void bnb_mi355x_gemm_4bit_experts_ffn(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes, const void* row_scale, int row_scale_dtype, int gated, void* out, long P, int S, int E, int N, int K, int blocksize, int quant_type, bnb_stream_t stream);
 int bnb_mi355x_gemm_4bit_experts_ffn_supported(int dtype, int E, int N, int K, int blocksize, int gated);
+/* Dense gated-SiLU FFN: the fused matmul over ONE interleaved matrix B [N = 2 F, K] - gate row i at row 2 i, up row i at row 2 i + 1;
+ * bias, if given, [N] in the same layout - with silu(gate) * up as its epilogue. A is [M, K], out is [M, F]:
+ *     g = T(acc_g + bias_g), u = T(acc_u + bias_u), out[m, i] = T(float(T(silu(g))) * float(u)),  silu(g) = g / (1 + expf(-g)) in fp32
+ * - bit for bit what `F.silu(y[:, 0::2]) * y[:, 1::2]` gives on the output y of bnb_mi355x_gemm_4bit on the same matrix, because the
+ * launch is the kernel family that call runs, and it exists only where that family is the streaming kernel (1) or the streaming MFMA
+ * kernel (7); bnb_mi355x_last_gemm_kernel reports 1 or 7 as for the plain call. dtype 1 / 2 (fp16 / bf16) only, fp32 absmax only
+ * (un-nest double-quantised statistics first), 1 <= M <= 16, N even, blocksize >= 64, K % blocksize == 0, A / B 16-byte aligned.
+ * N is the number of WEIGHT rows (2 F). A call outside these preconditions prints a message and ends the process, like every failed
+ * launch of this ABI: ask bnb_mi355x_gemm_4bit_gated_supported first (pure host logic over the shapes, aligned pointers assumed; it
+ * needs no device beyond the CU count the route queries use) and compose the plain call with silu and a multiply where it says 0. */
+void bnb_mi355x_gemm_4bit_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K, int blocksize, int quant_type, bnb_stream_t stream);
+int bnb_mi355x_gemm_4bit_gated_supported(int dtype, int M, int N, int K, int blocksize);
 
 /* Grouped gemm_4bit: `count` weight matrices applied to the SAME activations A[M, K] in one launch -
  *   out[i][M, N[i]] = A * dequant(B[i])^T (+ bias[i])        i = 0 .. count-1
