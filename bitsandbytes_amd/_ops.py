@@ -490,3 +490,61 @@ def _check_gemm_4bit_gated(A, B, shapeB, absmax, blocksize, quant_type, bias):
 def _(A, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: str, bias=None):
     N, _ = _check_gemm_4bit_gated(A, B, shapeB, absmax, blocksize, quant_type, bias)
     return torch.empty((*A.shape[:-1], N // 2), dtype=A.dtype, device=A.device)
+
+
+# ---------------------------------------------------------------------------------------------- gemm_4bit_lora
+# Not a reference op: a LoRA adapter beside a 4-bit base layer, y = base(x) + scaling * lora_B(lora_A(x)), with the adapter term as the
+# EPILOGUE of the base layer's fused matmul. A [*, K], B / shapeB / absmax / nested statistics / bias as for gemm_4bit; lora_t [*, r] =
+# x @ lora_A^T (the caller's small matmul; same leading dims as A, contiguous), lora_b [N, r] = lora_B.weight as stored; both of A's
+# dtype. out = T((acc + bias) + scaling * (t @ lora_b^T)): the plain call's fp32 sum, the adapter sum in fp32, ONE rounding to T.
+# Served for 1 ... 16 rows where the plain call runs the streaming or the streaming MFMA kernel, r % 8 == 0, 8 <= r <= 128
+# (backends/hip.py: gemm_4bit_lora_supported); anything else raises. Inference only: no autograd formula.
+torch.library.define(
+    "bitsandbytes_amd::gemm_4bit_lora",
+    "(Tensor A, Tensor B, int[] shapeB, Tensor absmax, int blocksize, str quant_type, Tensor lora_t, Tensor lora_b, float scaling, "
+    "Tensor? bias=None, Tensor? absmax_8bit=None, Tensor? absmax_code=None, Tensor? absmax_offset=None) -> Tensor",
+)
+
+
+def _check_gemm_4bit_lora(A, B, shapeB, absmax, blocksize, quant_type, lora_t, lora_b, bias, absmax_8bit, absmax_code, absmax_offset):
+    """Argument checks shared by the fake kernel and the device kernel; returns (N, K, r)."""
+    torch._check(is_pow2_blocksize(blocksize), lambda: f"blocksize must be a power of two >= 32, got {blocksize}")
+    torch._check(quant_type in ("nf4", "fp4"), lambda: f"quant_type must be 'nf4' or 'fp4', got {quant_type!r}")
+    torch._check(len(shapeB) == 2, lambda: f"shapeB must be [N, K], got {list(shapeB)}")
+    N, K = (int(v) for v in shapeB)
+    torch._check(N > 0 and K > 0, lambda: f"shapeB must be [N, K] with positive sizes, got {list(shapeB)}")
+    torch._check(A.dtype in _FLOAT_DTYPES, lambda: f"A must be a 16/32-bit float tensor, got {A.dtype}")
+    torch._check(A.dim() >= 1 and A.shape[-1] == K, lambda: f"A inner dim ({A.shape[-1] if A.dim() else None}) must equal K = shapeB[1] ({K})")
+    torch._check(B.device == A.device and absmax.device == A.device, lambda: "A, B and absmax must live on one device")
+    torch._check(B.numel() * B.element_size() * 2 == N * K, lambda: f"B holds {B.numel() * B.element_size() * 2} 4-bit values, shapeB {N * K}")
+    torch._check(absmax.dtype == torch.float32, lambda: f"absmax must be float32, got {absmax.dtype}")
+    torch._check(K % blocksize == 0, lambda: f"K ({K}) must be a multiple of blocksize ({blocksize})")
+    blocks = N * K // blocksize
+    nested = absmax_8bit is not None
+    if nested:
+        torch._check(absmax_code is not None and absmax_offset is not None, lambda: "nested statistics need absmax_8bit, absmax_code and absmax_offset together")
+        torch._check(absmax_8bit.dtype == torch.uint8 and absmax_8bit.numel() == blocks, lambda: f"absmax_8bit must hold {blocks} uint8 codes")
+        torch._check(absmax_code.dtype == torch.float32 and absmax_code.numel() == 256, lambda: "absmax_code must hold 256 float32 values")
+        torch._check(absmax.numel() == -(blocks // -256), lambda: f"absmax (second level) must hold {-(blocks // -256)} values, got {absmax.numel()}")
+        torch._check(absmax_offset.numel() == 1, lambda: "absmax_offset must hold one value")
+    else:
+        torch._check(absmax_code is None and absmax_offset is None, lambda: "absmax_code / absmax_offset belong to nested statistics (absmax_8bit)")
+        torch._check(absmax.numel() == blocks, lambda: f"absmax must hold {blocks} values, got {absmax.numel()}")
+    torch._check(lora_b.dim() == 2 and lora_b.shape[0] == N, lambda: f"lora_b must be [N, r] = [{N}, r] (lora_B.weight as stored), got {tuple(lora_b.shape)}")
+    r = int(lora_b.shape[1])
+    torch._check(r > 0, lambda: "lora_b must be [N, r] with r > 0")
+    torch._check(tuple(lora_t.shape) == (*A.shape[:-1], r), lambda: f"lora_t must be [*, r] = {(*A.shape[:-1], r)} (A's leading dims), got {tuple(lora_t.shape)}")
+    torch._check(lora_t.dtype == A.dtype and lora_b.dtype == A.dtype, lambda: f"lora_t and lora_b must have A's dtype ({A.dtype}), got {lora_t.dtype} and {lora_b.dtype}")
+    torch._check(lora_t.device == A.device and lora_b.device == A.device, lambda: "lora_t and lora_b must live on A's device")
+    torch._check(lora_t.is_contiguous() and lora_b.is_contiguous(), lambda: "lora_t and lora_b must be contiguous")
+    if bias is not None:
+        torch._check(tuple(bias.shape) == (N,), lambda: f"bias must be [N] = [{N}], got {tuple(bias.shape)}")
+        torch._check(bias.dtype == A.dtype and bias.device == A.device, lambda: f"bias must be a {A.dtype} tensor on A's device")
+    return N, K, r
+
+
+@register_fake("bitsandbytes_amd::gemm_4bit_lora")
+def _(A, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: str, lora_t, lora_b, scaling: float, bias=None, absmax_8bit=None,
+      absmax_code=None, absmax_offset=None):
+    N, _, _ = _check_gemm_4bit_lora(A, B, shapeB, absmax, blocksize, quant_type, lora_t, lora_b, bias, absmax_8bit, absmax_code, absmax_offset)
+    return torch.empty((*A.shape[:-1], N), dtype=A.dtype, device=A.device)

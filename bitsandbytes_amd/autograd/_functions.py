@@ -298,6 +298,61 @@ def ffn_4bit(
     return matmul_4bit(h, down, down_state, bias=down_bias)
 
 
+def _lora_fused(x: torch.Tensor, quant_state: F.QuantState, r: int) -> bool:
+    """Whether the LoRA launch serves this call - decided from shapes, dtypes and alignment only (nothing is read on the host)."""
+    if x.device.type != "cuda" or _is_compiling() or (quant_state.nested and quant_state.state2.blocksize != 256):
+        return False
+    from ..backends import hip
+
+    N, K = int(quant_state.shape[0]), int(quant_state.shape[1])
+    M = x.numel() // K if K else 0
+    with torch.cuda.device(x.device):  # (the route depends on the current device's CU count)
+        return hip.gemm_4bit_lora_supported(x.dtype, M, N, K, quant_state.blocksize, quant_state.nested, r)
+
+
+def matmul_4bit_lora(x: torch.Tensor, weight: torch.Tensor, quant_state: F.QuantState, lora_t: torch.Tensor, lora_b: torch.Tensor,
+                     scaling: float, bias: Optional[torch.Tensor] = None):
+    """``x @ dequant(weight).T (+ bias) + scaling * lora_t @ lora_b.T`` - a 4-bit base layer with its LoRA adapter beside it - as ONE
+    launch: the adapter term is the matmul's epilogue. ``lora_t``: ``[*, r] = F.linear(x, lora_A)`` (the caller's small matmul; layers
+    that share ``x`` can stack their ``lora_A``), ``lora_b``: ``[N, r]``, PEFT's ``lora_B.weight`` as stored. ``x``: ``[*, K]``; returns
+    ``[*, N]``.
+
+    The fused launch exists for 1 ... 16 rows of 16-bit activations where the plain call runs the streaming or the streaming MFMA
+    kernel, ``r % 8 == 0`` and ``8 <= r <= 128`` (``backends.hip.gemm_4bit_lora_supported``), plain or nested statistics; its result
+    is rounded ONCE: ``T((acc + bias) + scaling * lora)`` with both sums in fp32. Every other call composes
+    ``torch.addmm(matmul_4bit(x, ...), lora_t, lora_b.t(), alpha=scaling)`` - two launches, and NOT bit-identical to the fused call: the
+    base result is rounded to the tensor's dtype before the adapter term is added (two roundings). Neither path reads data on the
+    host, so both can be captured in a graph. Inference only: there is no autograd formula."""
+    if quant_state is None:
+        raise ValueError("quant_state is required")
+    if len(quant_state.shape) != 2:
+        raise ValueError(f"matmul_4bit_lora: quant_state.shape must be [N, K], got {list(quant_state.shape)}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, lora_t, lora_b, bias)):
+        raise RuntimeError("matmul_4bit_lora is inference only (no autograd formula): call it under torch.no_grad() "
+                           "or with detached inputs")
+    N, K = int(quant_state.shape[0]), int(quant_state.shape[1])
+    if x.shape[-1] != K:
+        raise ValueError(f"matmul_4bit_lora: x inner dim ({x.shape[-1]}) must equal quant_state.shape[1] ({K})")
+    if lora_b.dim() != 2 or lora_b.shape[0] != N or tuple(lora_t.shape) != (*x.shape[:-1], lora_b.shape[1]):
+        raise ValueError(f"matmul_4bit_lora: lora_b must be [N, r] = [{N}, r] and lora_t [*, r] with x's leading dims, "
+                         f"got {tuple(lora_b.shape)} and {tuple(lora_t.shape)}")
+    r = int(lora_b.shape[1])
+    if (x.numel() > 0 and weight.data_ptr() % 16 == 0 and lora_t.dtype == x.dtype and lora_b.dtype == x.dtype
+            and (bias is None or bias.dtype == x.dtype) and _lora_fused(x, quant_state, r)):
+        xc, tc, bc = x.contiguous(), lora_t.contiguous(), lora_b.contiguous()
+        if xc.data_ptr() % 16 == 0 and tc.data_ptr() % 16 == 0 and bc.data_ptr() % 16 == 0:
+            op = torch.ops.bitsandbytes_amd.gemm_4bit_lora.default
+            if not quant_state.nested:
+                return op(xc, weight.view(-1, 1), quant_state.shape, quant_state.absmax, quant_state.blocksize, quant_state.quant_type, tc, bc,
+                          float(scaling), bias=bias)
+            return op(xc, weight.view(-1, 1), quant_state.shape, quant_state.state2.absmax, quant_state.blocksize, quant_state.quant_type, tc, bc,
+                      float(scaling), bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code,
+                      absmax_offset=quant_state.offset)
+    y = matmul_4bit(x, weight, quant_state, bias=bias)
+    out = torch.addmm(y.reshape(-1, N), lora_t.reshape(-1, r).to(y.dtype), lora_b.to(y.dtype).t(), alpha=float(scaling))
+    return out.view(*x.shape[:-1], N)
+
+
 def matmul_4bit_grouped(A: torch.Tensor, weights, quant_states, biases=None, outs=None):
     """``[matmul_4bit(A, B_i, state_i, bias=bias_i) for i]`` for 4-bit weights that share their input - the Q/K/V
     projections of an attention block, the gate/up projections of an MLP. On MI355X a decode-sized batch (M <= 4) is

@@ -20,7 +20,8 @@ from warnings import warn
 
 import torch
 
-from .._ops import GATED_CODES, _check_gemm_4bit_experts, _check_gemm_4bit_experts_ffn, _check_gemm_4bit_gated, register_kernel
+from .._ops import (GATED_CODES, _check_gemm_4bit_experts, _check_gemm_4bit_experts_ffn, _check_gemm_4bit_gated, _check_gemm_4bit_lora,
+                     register_kernel)
 from ..cextension import lib
 
 _DT_NAME = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}
@@ -607,6 +608,46 @@ def _(A, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: str, bias
         lib.bnb_mi355x_gemm_4bit_gated(
             _DT_CODE[A.dtype], A.data_ptr(), B.data_ptr(), absmax.data_ptr(), out.data_ptr(),
             _ptr(bias if bias is None else bias.contiguous()), M, N, K, blocksize, _QT_CODE[quant_type], _stream(A),
+        )
+    return out
+
+
+# ------------------------------------------------------------------------------------------ gemm_4bit_lora
+def gemm_4bit_lora_supported(dtype: torch.dtype, M: int, N: int, K: int, blocksize: int, nested: bool, r: int) -> bool:
+    """Whether ``bitsandbytes_amd::gemm_4bit_lora`` has a kernel for ``M`` rows on the ``[N, K]`` matrix with a rank-``r`` adapter: the
+    plain call of that shape runs the streaming or the streaming MFMA kernel, 16-bit activations, ``M <= 16``, blocksize >= 64,
+    ``r % 8 == 0``, ``8 <= r <= 128`` (pure host logic of the library plus the CU count of the current device, as the route queries)."""
+    if dtype not in (torch.float16, torch.bfloat16) or max(M, N, K, r) >= 2**31 or min(M, N, K, r) < 1:
+        return False
+    return bool(lib.bnb_mi355x_gemm_4bit_lora_supported(_DT_CODE[dtype], M, N, K, blocksize, 1 if nested else 0, r))
+
+
+@register_kernel("bitsandbytes_amd::gemm_4bit_lora", "cuda")
+def _(A, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: str, lora_t, lora_b, scaling: float, bias=None, absmax_8bit=None,
+      absmax_code=None, absmax_offset=None):
+    """One launch of the streaming kernel's or the streaming MFMA kernel's LoRA instance - the family the plain call runs."""
+    N, K, r = _check_gemm_4bit_lora(A, B, shapeB, absmax, blocksize, quant_type, lora_t, lora_b, bias, absmax_8bit, absmax_code, absmax_offset)
+    M = A.numel() // K
+    out = torch.empty((*A.shape[:-1], N), dtype=A.dtype, device=A.device)
+    if M == 0:
+        return out
+    A = A.contiguous()
+    B = B.contiguous()
+    absmax = absmax.contiguous()
+    nested = absmax_8bit is not None
+    a8 = absmax_8bit.contiguous() if nested else None
+    code = absmax_code.contiguous() if nested else None
+    offset32 = absmax_offset.to(dtype=torch.float32) if nested else None
+    with _device_of(A):
+        # (inside the guard: the route depends on the current device's CU count)
+        if (not gemm_4bit_lora_supported(A.dtype, M, N, K, blocksize, nested, r) or A.data_ptr() % 16 or B.data_ptr() % 16 or absmax.data_ptr() % 4
+                or lora_t.data_ptr() % 16 or lora_b.data_ptr() % 16):
+            raise ValueError(f"gemm_4bit_lora: no kernel for M={M}, N={N}, K={K}, blocksize={blocksize}, r={r}, dtype={A.dtype} "
+                             "(A, B, lora_t and lora_b 16-byte aligned); add the adapter term to gemm_4bit's output - matmul_4bit_lora does")
+        lib.bnb_mi355x_gemm_4bit_lora(
+            _DT_CODE[A.dtype], A.data_ptr(), B.data_ptr(), absmax.data_ptr(), _ptr(a8), _ptr(code), _ptr(offset32), out.data_ptr(),
+            _ptr(bias if bias is None else bias.contiguous()), lora_t.data_ptr(), lora_b.data_ptr(), float(scaling), r, M, N, K, blocksize,
+            _QT_CODE[quant_type], _stream(A),
         )
     return out
 

@@ -36,6 +36,10 @@ bool gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, bool 
 bool gemv_4bit_stream_gated_supported(int dtype, int M, int N, int K, int blocksize);
 bool gemv_4bit_stream_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K,
                             int blocksize, int quant_type, hipStream_t stream);
+bool gemv_4bit_stream_lora_supported(int dtype, int M, int N, int K, int blocksize, int r);
+bool gemv_4bit_stream_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                           const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r,
+                           int M, int N, int K, int blocksize, int quant_type, hipStream_t stream);
 bool gemv_4bit_peer(void* const* bufs, void* epoch_word, int world, int rank, int dtype, const void* A, const uint8_t* B, const float* absmax,
                     const uint8_t* absmax8, const float* absmax_code, const float* absmax_offset, const void* bias, void* out_local,
                     int ns, int K, int blocksize, int quant_type, int mode, long max_values, int wg_limit, uint32_t epoch_offset,
@@ -64,6 +68,10 @@ bool gemm_4bit_sm_serves(const float* absmax, const uint8_t* absmax8, int blocks
 bool gemm_4bit_sm_gated_supported(int dtype, const void* A, const uint8_t* B, int M, int N, int K, int blocksize);
 bool gemm_4bit_sm_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K,
                         int blocksize, int quant_type, hipStream_t stream);
+bool gemm_4bit_sm_lora_supported(int dtype, const void* A, const uint8_t* B, int M, int N, int K, int blocksize, int r);
+bool gemm_4bit_sm_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                       const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r,
+                       int M, int N, int K, int blocksize, int quant_type, hipStream_t stream);
 extern thread_local TlsKnob g_mfma_knob0, g_mfma_knob1;
 // gemm4_grad_input.hip
 bool gemm_4bit_grad_input_supported(int dtype, const void* G, const uint8_t* B, int M, int N, int K, int blocksize);
@@ -151,6 +159,29 @@ int gated_family(int dtype, const void* A, const uint8_t* B, const float* absmax
                    : kKernelNone;
     }
     return gemv_4bit_stream_gated_supported(dtype, M, N, K, blocksize) ? kKernelStream : kKernelNone;
+}
+
+// LoRA call (bnb_mi355x_gemm_4bit_lora) at M rows: the kernel FAMILY the plain bnb_mi355x_gemm_4bit call on the same matrix, M and
+// statistics runs - the adapter term is an epilogue of that launch, everything in front of it the plain instance's - when that family
+// has the epilogue: kKernelStream or kKernelSm, else 0 (not supported). 16-bit activations, 1 <= M <= 16, blocksize >= 64, whole
+// quantization blocks per row, r a multiple of 8 in [8, 128], aligned pointers.
+int lora_family(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const void* lora_t, const void* lora_b, int M,
+                int N, int K, int blocksize, int r) {
+    if ((dtype != 1 && dtype != 2) || M < 1 || M > 16 || N < 1 || K <= 0 || blocksize < 64 || !is_pow2(blocksize) || (K % blocksize) != 0 || r < 8 || r > 128 ||
+        (r % 8) != 0 || !aligned_to(A, 16) || !aligned_to(B, 16) || !aligned_to(absmax, 4) || !aligned_to(lora_t, 16) || !aligned_to(lora_b, 16))
+        return kKernelNone;
+    if (route_to_mfma(0, dtype, A, B, nullptr, M, N, K, blocksize, absmax8 == nullptr && aligned_to(absmax, 16))) {
+        // (gemm_4bit_mfma's order: the tall-tile knob, the streaming MFMA kernel, the streaming kernel for rows that are not whole
+        // 256-k chunks; every other MFMA kernel has no LoRA epilogue)
+        if (g_mfma_knob1.load(std::memory_order_relaxed) / 100 == 60)
+            return kKernelNone;
+        if (gemm_4bit_sm_routes(dtype, M, N, K, blocksize) && gemm_4bit_sm_supported(dtype, A, B, nullptr, M, N, K, blocksize) &&
+            gemm_4bit_sm_serves(absmax, absmax8, blocksize))
+            return gemm_4bit_sm_lora_supported(dtype, A, B, M, N, K, blocksize, r) ? kKernelSm : kKernelNone;
+        if ((K % 256) == 0)
+            return kKernelNone;
+    }
+    return gemv_4bit_stream_lora_supported(dtype, M, N, K, blocksize, r) ? kKernelStream : kKernelNone;
 }
 
 } // namespace
@@ -463,6 +494,36 @@ int bnb_mi355x_gemm_4bit_gated_supported(int dtype, int M, int N, int K, int blo
     static const int dummy_aligned[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
     return gated_family(dtype, dummy_aligned, reinterpret_cast<const uint8_t*>(dummy_aligned), reinterpret_cast<const float*>(dummy_aligned), M, N, K,
                         blocksize) != kKernelNone
+               ? 1
+               : 0;
+}
+
+// ------------------------------------------------------------------ LoRA gemm_4bit (the adapter term as the decode kernels' epilogue)
+void bnb_mi355x_gemm_4bit_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit,
+                               const float* absmax_code, const float* absmax_offset, void* out, const void* bias, const void* lora_t,
+                               const void* lora_b, float scaling, int r, int M, int N, int K, int blocksize, int quant_type, bnb_stream_t s) {
+    if (quant_type != kFP4 && quant_type != kNF4) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_lora: quant_type must be 1 (FP4) or 2 (NF4), got %d\n", quant_type);
+        exit(1);
+    }
+    const int family = lora_family(dtype, A, B, absmax, absmax_8bit, lora_t, lora_b, M, N, K, blocksize, r);
+    const bool ok = family == kKernelSm ? gemm_4bit_sm_lora(dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, lora_t, lora_b, scaling, r,
+                                                            M, N, K, blocksize, quant_type, S(s))
+                    : family == kKernelStream ? gemv_4bit_stream_lora(dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, lora_t, lora_b,
+                                                                      scaling, r, M, N, K, blocksize, quant_type, S(s))
+                                              : false;
+    if (!ok) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_lora: no kernel for dtype %d, M=%d, N=%d, K=%d, blocksize=%d, r=%d (ask bnb_mi355x_gemm_4bit_lora_supported, align A / B / lora_t / lora_b to 16 bytes)\n",
+                dtype, M, N, K, blocksize, r);
+        exit(1);
+    }
+}
+int bnb_mi355x_gemm_4bit_lora_supported(int dtype, int M, int N, int K, int blocksize, int nested, int r) {
+    // (alignment is unknown here; the aligned case is assumed, as in the route query)
+    static const int dummy_aligned[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
+    const uint8_t* const d8 = reinterpret_cast<const uint8_t*>(dummy_aligned);
+    return lora_family(dtype, dummy_aligned, d8, reinterpret_cast<const float*>(dummy_aligned), nested ? d8 : nullptr, dummy_aligned, dummy_aligned, M, N, K,
+                       blocksize, r) != kKernelNone
                ? 1
                : 0;
 }

@@ -101,6 +101,11 @@ struct SmArgs {
     const float* goffset[kSmMaxGroup];
     void* gout[kSmMaxGroup];
     const void* gbias[kSmMaxGroup];
+    // LoRA epilogue (LORA instances; behind everything the other instances read, outside the preloaded dwords)
+    const void* lora_t; // [M, r] of T: the down-projected activations x @ lora_A^T
+    const void* lora_b; // [N, r] of T: lora_B.weight as stored
+    int lora_r;         // 8 <= r <= 128, r % 8 == 0
+    float lora_scaling;
 };
 
 // Time stamps (measurement build): s_memtime values collect in scalar registers and are stored ONCE, at the end of the kernel
@@ -152,7 +157,12 @@ __device__ __forceinline__ int sm_swz(int m) { return (m & 3) | ((m & 4) << 1); 
 // GATED (dense FFN, bnb_mi355x_gemm_4bit_gated): the weight rows are (gate, up) pairs of ONE interleaved [2F, K] matrix - row 2 i = gate
 // row i, row 2 i + 1 = up row i - and the epilogue stores out[m, i] = T(T(silu(g)) * u), [M, F]; the host keeps R even (sm_plan), so a
 // pair never straddles two workgroups. Everything in front of the combine step is the plain kernel's.
-template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false, bool GATED = false>
+// LORA (bnb_mi355x_gemm_4bit_lora): the epilogue stores out[m, n] = T((acc + bias[n]) + scaling * lora[m, n]) with the fp32 tile
+// lora = t [M, r] x B_l[rows of the tile, r]^T from the matrix pipe: wavefront t of the first TT multiplies tile t - v_mfma_f32_16x16x32
+// steps over k = 0, 32, ... < r in ascending order into ONE accumulator that starts at zero (k >= r and rows past M / past the
+// workgroup's rows are out-of-range loads: zeros), behind its last item and in front of the final barrier, and hands the tile to the
+// combine step through TT KiB of LDS behind the wavefronts' regions. Everything in front of that is the plain kernel's.
+template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false, bool GATED = false, bool LORA = false>
 __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
     // hot arguments as separate scalars: preloaded into SGPRs by the command processor (14 dwords)
     const void* hot_A, const uint8_t* hot_B, const float* hot_absmax, const uint8_t* hot_absmax8, const float* hot_code2, int hot_M,
@@ -183,6 +193,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
     static_assert(ROWS != 32 || (!SINGLE && WAVES == 8), "32-row instances: ring, 8 wavefronts");
     static_assert(TT >= 1 && TT <= kSmMaxTiles && (!SINGLE || TT == 1), "tiles per workgroup");
     static_assert(!GATED || (ROWS != 32 && !GROUPED && !NESTED && ORDER == 0), "gated instances: up to 16 rows, one matrix, fp32 absmax");
+    static_assert(!LORA || (ROWS != 32 && !GROUPED && !GATED && ORDER == 0), "LoRA instances: up to 16 rows, one matrix");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -386,6 +397,16 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
     // SGPRs here, it returns under the first weight bytes. (Grouped launches select a member's pointers by block: left as they are.)
     if constexpr (!GROUPED)
         asm volatile("" : "+s"(g_out), "+s"(g_bias));
+    // (LoRA) the adapter's kernarg fields, requested and pinned with them
+    [[maybe_unused]] uintptr_t lo_t = 0, lo_b = 0;
+    [[maybe_unused]] int lo_r = 0, lo_s = 0;
+    if constexpr (LORA) {
+        lo_t = reinterpret_cast<uintptr_t>(p.lora_t);
+        lo_b = reinterpret_cast<uintptr_t>(p.lora_b);
+        lo_r = p.lora_r;
+        lo_s = __builtin_bit_cast(int, p.lora_scaling);
+        asm volatile("" : "+s"(lo_t), "+s"(lo_b), "+s"(lo_r), "+s"(lo_s));
+    }
     __syncthreads();
     BNB_SM_STAMP(5)
     if constexpr (!SINGLE) {
@@ -543,6 +564,33 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb)
                 *reinterpret_cast<f32x4*>(region + ((z * TT + t) * RB + rb) * 1024 + lane * 16) = acc[z][t][rb];
+    constexpr int kLoraLds = kRegions + WAVES * REGION; // (LoRA) TT tiles of 1 KiB, in the accumulators' lane layout
+    if constexpr (LORA) {
+        static_assert(TT <= WAVES, "one wavefront per tile");
+        if (wave < TT) {
+            // operand shape of v_mfma_f32_16x16x32: lane (ln, lg) holds 8 consecutive k of row ln - batch row ln of t, weight row ln of the
+            // tile - from k = 32 s + 8 lg; both operands use the same k, which is all the product needs
+            const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(lo_t), 0, 0x7FFFFFFF, 0x00020000);
+            const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(lo_b), 0, 0x7FFFFFFF, 0x00020000);
+            const int lm = m_base + ln, lnrow = row0 + 16 * wave + ln;
+            u32x4 ta[4], tb[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int k = 32 * s + 8 * lg;
+                const uint32_t inv_k = k < lo_r ? 0u : kOob;
+                ta[s] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                      rs_t, (static_cast<uint32_t>(lm * lo_r + k) * 2u) | inv_k | (lm < M ? 0u : kOob), 0, 0));
+                tb[s] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                      rs_b, (static_cast<uint32_t>(lnrow * lo_r + k) * 2u) | inv_k | (lnrow < row_end ? 0u : kOob), 0, 0));
+            }
+            f32x4 lacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                if (32 * s < lo_r) // (wave-uniform)
+                    lacc = SmMma<T>::run(ta[s], tb[s], lacc);
+            *reinterpret_cast<f32x4*>(smem + kLoraLds + wave * 1024 + lane * 16) = lacc;
+        }
+    }
     __syncthreads();
     BNB_SM_STAMP(9)
     constexpr int PARTS = 4, WPP = WAVES * V / PARTS; // (virtual wavefront v = set v / WAVES of wavefront v % WAVES)
@@ -587,7 +635,14 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
         if (part == 0 && mm < M && n < row_end) {
             const T* bias = static_cast<const T*>(g_bias);
             const float b = bias ? static_cast<float>(bias[n]) : 0.0f;
-            static_cast<T*>(g_out)[static_cast<long>(mm) * N + n] = static_cast<T>(v + b);
+            float vb = v + b;
+            if constexpr (LORA) {
+                // T((acc + bias) + scaling * lora): every intermediate an fp32 VALUE (opaque: no mixed-precision FMA folds the sum
+                // into the conversion), one rounding to T
+                const float lv = reinterpret_cast<const float*>(smem + kLoraLds + t * 1024)[src];
+                vb = rounded_f32(rounded_f32(vb) + rounded_f32(__builtin_bit_cast(float, lo_s) * lv));
+            }
+            static_cast<T*>(g_out)[static_cast<long>(mm) * N + n] = static_cast<T>(vb);
         }
     }
     if constexpr (GATED) {
@@ -620,6 +675,7 @@ struct SmPlan {
     int variant = 0; // experiment bits (bnb_mi355x_set_tuning knob0)
     bool grouped = false;
     bool gated = false; // (gate, up) row pairs: R even
+    bool lora = false;  // the LoRA epilogue's instances
 };
 
 // rows per workgroup: one workgroup per CU when 64 rows are enough, else whole rounds of workgroups
@@ -642,14 +698,14 @@ SmPlan sm_plan(int M, int N, bool gated = false) {
     return pl;
 }
 
-template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false, bool GATED = false>
+template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false, bool GATED = false, bool LORA = false>
 void sm_launch_one(const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* code2, int M, int N, int K, int geom,
                    const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
     constexpr int V = (ROWS < 16 && WAVES == 8) ? 2 : 1; // (accumulator sets per tile: the kernel's V)
     constexpr int RB = ROWS == 32 ? 2 : 1, SROWS = ROWS == 32 ? 16 : ROWS;
     constexpr size_t region = (SROWS * 512 + kSmScratch) > V * TT * RB * 1024 ? (SROWS * 512 + kSmScratch) : V * TT * RB * 1024;
-    constexpr size_t lds = kSmLut + kSmCode2 + static_cast<size_t>(WAVES) * region;
-    auto kern = gemm4_mfma_sm_kernel<T, ROWS, WAVES, TT, NESTED, SINGLE, ORDER, GROUPED, GATED>;
+    constexpr size_t lds = kSmLut + kSmCode2 + static_cast<size_t>(WAVES) * region + (LORA ? TT * 1024 : 0); // (+ the adapter's tiles)
+    auto kern = gemm4_mfma_sm_kernel<T, ROWS, WAVES, TT, NESTED, SINGLE, ORDER, GROUPED, GATED, LORA>;
     static LdsLimit lim;
     ensure_dynamic_lds(lim, reinterpret_cast<const void*>(kern), lds);
     hipLaunchKernelGGL(kern, dim3(pl.grid_x, (M + 16 * RB - 1) / (16 * RB)), dim3(WAVES * 64), lds, stream, A, B, absmax, absmax8, code2, M, N, K, geom, a);
@@ -666,6 +722,20 @@ void sm_launch_kind(const void* A, const uint8_t* B, const float* absmax, const 
                     return sm_launch_one<T, ROWS, WAVES, 1, false, true, 0, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
             }
             return sm_launch_one<T, ROWS, WAVES, TT, false, false, 0, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+        }
+    }
+    if constexpr (ROWS != 32) {
+        if (pl.lora) { // (one matrix, both kinds of statistics: gemm_4bit_sm_lora checks)
+            if constexpr (TT == 1) {
+                if ((K + kSmChunk - 1) / kSmChunk <= WAVES) {
+                    if (nested)
+                        return sm_launch_one<T, ROWS, WAVES, 1, true, true, 0, false, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+                    return sm_launch_one<T, ROWS, WAVES, 1, false, true, 0, false, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+                }
+            }
+            if (nested)
+                return sm_launch_one<T, ROWS, WAVES, TT, true, false, 0, false, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+            return sm_launch_one<T, ROWS, WAVES, TT, false, false, 0, false, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
         }
     }
     if (pl.grouped) { // (ring instances only)
@@ -777,6 +847,44 @@ bool gemm_4bit_sm_gated(int dtype, const void* A, const uint8_t* B, const float*
         sm_launch_rows<bf16>(A, B, absmax, nullptr, nullptr, M, N, K, geom, pl, a, stream);
     else
         sm_launch_rows<f16>(A, B, absmax, nullptr, nullptr, M, N, K, geom, pl, a, stream);
+    BNB_CHECK_LAUNCH();
+    g_last_gemm_kernel = kKernelSm;
+    return true;
+}
+
+// LoRA form (see the kernel's LORA): the plain launch of the same matrix and M - same plan, same instance skeleton - with the adapter
+// term in the epilogue; t [M, r], B_l [N, r] of the activations' type, 16-byte aligned, 1 <= M <= 16 (the 4-, 8- and 16-row instances),
+// fp32 absmax or nested statistics. false - nothing launched - outside these preconditions.
+bool gemm_4bit_sm_lora_supported(int dtype, const void* A, const uint8_t* B, int M, int N, int K, int blocksize, int r) {
+    return M <= 16 && r >= 8 && r <= 128 && (r % 8) == 0 && static_cast<long long>(N) * r < (1LL << 29) &&
+           gemm_4bit_sm_supported(dtype, A, B, nullptr, M, N, K, blocksize);
+}
+bool gemm_4bit_sm_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                       const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r,
+                       int M, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
+    if (!gemm_4bit_sm_lora_supported(dtype, A, B, M, N, K, blocksize, r) || !gemm_4bit_sm_serves(absmax, absmax8, blocksize) || !aligned_to(lora_t, 16) ||
+        !aligned_to(lora_b, 16) || (absmax8 != nullptr && (absmax_code == nullptr || absmax_offset == nullptr)))
+        return false;
+    SmPlan pl = sm_plan(M, N);
+    if (pl.rows > 16 || pl.tt > kSmMaxTiles)
+        return false;
+    pl.lora = true;
+    SmArgs a{};
+#ifdef BNB_PROFILING
+    a.dbg = nullptr;
+#endif
+    a.absmax_offset = absmax_offset;
+    a.out = out;
+    a.bias = bias;
+    a.lora_t = lora_t;
+    a.lora_b = lora_b;
+    a.lora_r = r;
+    a.lora_scaling = scaling;
+    const int geom = pl.R | ((quant_type == kFP4) ? (1 << 16) : 0) | (ilog2(blocksize) << 20);
+    if (dtype == 2)
+        sm_launch_rows<bf16>(A, B, absmax, absmax8, absmax_code, M, N, K, geom, pl, a, stream);
+    else
+        sm_launch_rows<f16>(A, B, absmax, absmax8, absmax_code, M, N, K, geom, pl, a, stream);
     BNB_CHECK_LAUNCH();
     g_last_gemm_kernel = kKernelSm;
     return true;

@@ -63,7 +63,8 @@ enum StreamFlags : int {
     kPeer = 64,    // "peer chain" form (M = 1): x taken from / y delivered to the ranks' exchange buffers - see PeerChain
     kExact = 128,  // exact geometry (M = 1, K = 4096: SW = 2, G = 8, every row, lane and ring position valid): see launch_one
     kLateArgs = 256, // sweep-only: the epilogue's out / bias pointers loaded where they are used (the form up to round 6; A/B runs)
-    kGated = 512     // rows are (gate, up) pairs of ONE interleaved [2F, K] matrix: out[m, i] = silu(row 2 i) * (row 2 i + 1), [M, F]
+    kGated = 512,    // rows are (gate, up) pairs of ONE interleaved [2F, K] matrix: out[m, i] = silu(row 2 i) * (row 2 i + 1), [M, F]
+    kLora = 1024     // LoRA adapter term as the epilogue: out[m, n] = T((acc + bias[n]) + scaling * sum_j t[m, j] * B_l[n, j]) - see lora_dot
 };
 
 // One weight matrix of a launch.
@@ -159,6 +160,11 @@ struct StreamArgs {
     int rows_total; // sum of N over the group
     int nmat;
     StreamMat mat[kMaxGroup];
+    // LoRA epilogue (kLora instances; behind everything the other instances read, outside the preloaded dwords)
+    const void* lora_t = nullptr; // [M, r] of T: the down-projected activations x @ lora_A^T
+    const void* lora_b = nullptr; // [N, r] of T: lora_B.weight as stored
+    int lora_r = 0;               // 8 <= r <= 128, r % 8 == 0: every row of both starts 16-byte aligned
+    float lora_scaling = 0.0f;
 };
 
 template <bool FP4> __device__ __forceinline__ float code_literal(int i) {
@@ -222,6 +228,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     static_assert(!GATED || (!PEER && !GROUPED && !NESTED && !CODEPTR && !(FLAGS & kLateArgs) && TypeInfo<T>::bytes == 2),
                   "the gated form: one matrix, fp32 absmax, literal table, 16-bit activations");
     static_assert(!PEER || (MB == 1 && !MULTI && !GROUPED && WAVES == 16), "the peer-chain form is the M = 1, single-phase kernel");
+    // LoRA epilogue (bnb_mi355x_gemm_4bit_lora): everything in front of the epilogue is the plain kernel's, fp32 absmax or nested statistics
+    constexpr bool LORA = (FLAGS & kLora) != 0;
+    static_assert(!LORA || (!PEER && !GROUPED && !GATED && !CODEPTR && !(FLAGS & kLateArgs) && TypeInfo<T>::bytes == 2),
+                  "the LoRA form: one matrix, literal table, 16-bit activations");
     // Exact geometry: the host selects this instance only when K = kExactSW * 2048, M = 1 and the rows divide evenly over workgroups
     // and row groups with at least one ring position each (exact_geometry()). Everything the general instance decides at run time in
     // front of its first weight request - bounds of the row list, of the row, of the segment, the division of the wavefront id - is a
@@ -564,6 +574,9 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     // stored. Requested here behind the ring issue and pinned in SGPRs in front of the first barrier, it runs under the latency of
     // the first weight bytes. (Grouped launches pick the matrix per row: left as they are.)
     [[maybe_unused]] uintptr_t ep_out = 0, ep_bias = 0;
+    // (LoRA) the adapter's kernarg fields: requested and pinned with the epilogue's pointers
+    [[maybe_unused]] uintptr_t lo_t = 0, lo_b = 0;
+    [[maybe_unused]] int lo_r = 0, lo_s = 0;
     uint32_t epoch = 0;     // (peer chain) the exchange this launch consumes
     uint32_t epoch_raw = 0; // ... the epoch word as loaded
     for (int ph = 0; ph < P; ++ph) {
@@ -623,6 +636,12 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
             if constexpr (EARLY_ARGS) {
                 ep_out = reinterpret_cast<uintptr_t>(p.mat[0].out);
                 ep_bias = reinterpret_cast<uintptr_t>(p.mat[0].bias);
+                if constexpr (LORA) {
+                    lo_t = reinterpret_cast<uintptr_t>(p.lora_t);
+                    lo_b = reinterpret_cast<uintptr_t>(p.lora_b);
+                    lo_r = p.lora_r;
+                    lo_s = __builtin_bit_cast(int, p.lora_scaling);
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -726,6 +745,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
         if constexpr (EARLY_ARGS) {
             if (ph == 0)
                 asm volatile("" : "+s"(ep_out), "+s"(ep_bias)); // (opaque: the values live in SGPRs from here - not re-loaded behind the last barrier)
+            if constexpr (LORA) {
+                if (ph == 0)
+                    asm volatile("" : "+s"(lo_t), "+s"(lo_b), "+s"(lo_r), "+s"(lo_s));
+            }
         }
         __syncthreads();
         if (ph == 0)
@@ -775,6 +798,36 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     [[maybe_unused]] uint32_t epoch_out = 0;
     if constexpr (PEER)
         epoch_out = epoch + 1u;
+    // (LoRA) lora[m, n] = sum_j float(t[m, j]) * float(B_l[n, j]) in fp32, in an order that depends on r alone: 16-byte pieces (8 values)
+    // of the two rows in ascending j, element e of a piece into chain e & 3 by one fused multiply-add, the chains combined as
+    // (c0 + c1) + (c2 + c3). It does not depend on the segment partials: the thread of output idx = tid - the only output of a thread
+    // wherever a workgroup holds at most THREADS / MB rows - computes it HERE, in front of the final barrier, while the wavefronts
+    // that started later still decode; behind the barrier the epilogue only adds it. (Further trips of the epilogue loop: on the spot.)
+    auto lora_dot = [&](int mrow, int nrow) -> float {
+        const unsigned char* const tp = reinterpret_cast<const unsigned char*>(lo_t) + static_cast<long>(mrow) * lo_r * 2;
+        const unsigned char* const bp = reinterpret_cast<const unsigned char*>(lo_b) + static_cast<long>(nrow) * lo_r * 2;
+        float c[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int j = 0; j < lo_r; j += 8) {
+            float tf[8], bf[8];
+            // (global address space: a generic pointer made from an integer compiles to flat loads)
+            typedef const u32x4 __attribute__((address_space(1))) * gvec_ptr;
+            const u32x4 tv = *(gvec_ptr)(reinterpret_cast<uintptr_t>(tp + j * 2)), bv = *(gvec_ptr)(reinterpret_cast<uintptr_t>(bp + j * 2));
+            unpack16<T>(tv, tf);
+            unpack16<T>(bv, bf);
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                c[e & 3] = __builtin_fmaf(tf[e], bf[e], c[e & 3]);
+        }
+        return (c[0] + c[1]) + (c[2] + c[3]);
+    };
+    [[maybe_unused]] float lora_kept = 0.0f;
+    if constexpr (LORA) {
+        if (tid < nrows * MB) {
+            const int m = (MB == 1) ? 0 : tid / nrows, rl = tid - m * nrows;
+            if (m0 + m < M)
+                lora_kept = lora_dot(m0 + m, row_begin + rl);
+        }
+    }
     __syncthreads();
     BNB_ST_STAMP(7)
     if constexpr (GATED) {
@@ -821,7 +874,14 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
         T* const out = EARLY_ARGS ? reinterpret_cast<T*>(ep_out) : static_cast<T*>(p.mat[mi].out);
         const int out_n = GROUPED ? p.mat[mi].N : hot_N; // (one matrix: its N is the preloaded row count)
         const float b = bias ? static_cast<float>(bias[row]) : 0.0f;
-        const T tv = static_cast<T>(v + b);
+        float vb = v + b;
+        if constexpr (LORA) {
+            // T((acc + bias) + scaling * lora): every intermediate an fp32 VALUE (opaque: no mixed-precision FMA folds the sum into
+            // the conversion), one rounding to T
+            const float lv = (idx == tid) ? lora_kept : lora_dot(m0 + m, row);
+            vb = rounded_f32(rounded_f32(vb) + rounded_f32(__builtin_bit_cast(float, lo_s) * lv));
+        }
+        const T tv = static_cast<T>(vb);
         if constexpr (PEER) {
             if (out != nullptr)
                 out[row] = tv;
@@ -1038,7 +1098,7 @@ bool exact_geometry(const Geometry& ge, int M, int rows_total, int K, int ns) {
 // (Nested statistics: the exact form was built and measured BEHIND the general one at 4096^2 - FP4 bs 128 nested 4.50 against
 // 4.36 us - and is not instantiated: DESIGN 6b.)
 template <typename T, int MB, int WAVES, int NS, int FLAGS> constexpr bool has_exact_twin() {
-    return TypeInfo<T>::bytes == 2 && MB == 1 && WAVES == 16 && NS == kRing && (FLAGS & ~(kFp4 | kGated)) == kNT;
+    return TypeInfo<T>::bytes == 2 && MB == 1 && WAVES == 16 && NS == kRing && (FLAGS & ~(kFp4 | kGated | kLora)) == kNT;
 }
 // stream tuning knob `nt`, values above 1 (A/B of the fixed-cost levers, tools/stream_fixed_cost_ab.py): 2 = the general instance where
 // the exact one would be selected, 3 = the general instance with the epilogue's pointers loaded late (bf16, NF4 fp32-absmax and
@@ -1477,6 +1537,65 @@ bool gemv_4bit_stream_gated(int dtype, const void* A, const uint8_t* B, const fl
         fp4 ? launch_gated<bf16, kNT | kGated | kFp4>(a, stream) : launch_gated<bf16, kNT | kGated>(a, stream);
     else
         fp4 ? launch_gated<f16, kNT | kGated | kFp4>(a, stream) : launch_gated<f16, kNT | kGated>(a, stream);
+    BNB_CHECK_LAUNCH();
+    g_last_gemm_kernel = kKernelStream;
+    return true;
+}
+
+// LoRA form (bnb_mi355x_gemm_4bit_lora): the plain call's instance (launch_mb: one row -> 16 wavefronts, two -> 16 or 8, more ->
+// passes of four on 8; production ring, non-temporal loads, literal table, fp32 absmax or nested statistics) with the adapter term
+// out[m, n] = T((acc + bias[n]) + scaling * sum_j t[m, j] * B_l[n, j]) as its epilogue. 16-bit activations. The shape half of the
+// preconditions, shared with the host layer's query:
+bool gemv_4bit_stream_lora_supported(int dtype, int M, int N, int K, int blocksize, int r) {
+    return (dtype == 1 || dtype == 2) && M >= 1 && M <= 65535 && N >= 1 && K > 0 && (K % 32) == 0 && K <= 511 * kSegK && blocksize >= 32 && is_pow2(blocksize) &&
+           r >= 8 && r <= 128 && (r % 8) == 0;
+}
+template <typename T, int FLAGS> static void launch_lora(const StreamArgs& a, hipStream_t stream) {
+    if (a.M == 1)
+        return launch_one<T, 1, 16, kRing, FLAGS>(a, stream);
+    if (a.M == 2 && make_geometry(a.rows_total, a.K, 2, 16, 2, false, 0, 0).P == 1) // (launch_mb's question)
+        return launch_one<T, 2, 16, kRing, FLAGS>(a, stream);
+    if (a.M == 2)
+        return launch_one<T, 2, 8, kRing, FLAGS>(a, stream);
+    launch_one<T, 4, 8, kRing, FLAGS>(a, stream);
+}
+template <typename T> static void launch_lora_flags(const StreamArgs& a, int quant_type, hipStream_t stream) {
+    const int sel = (a.mat[0].absmax8 != nullptr ? 1 : 0) | (quant_type == kFP4 ? 2 : 0);
+    switch (sel) {
+    case 0: return launch_lora<T, kNT | kLora>(a, stream);
+    case 1: return launch_lora<T, kNT | kLora | kNested>(a, stream);
+    case 2: return launch_lora<T, kNT | kLora | kFp4>(a, stream);
+    default: return launch_lora<T, kNT | kLora | kFp4 | kNested>(a, stream);
+    }
+}
+// false - nothing launched - when the call is outside the form's preconditions
+bool gemv_4bit_stream_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                           const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r,
+                           int M, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
+    if (!gemv_4bit_stream_lora_supported(dtype, M, N, K, blocksize, r) || !stream_ok(A, M, K, blocksize) || !aligned_to(B, 16) || !aligned_to(absmax, 4) ||
+        !aligned_to(lora_t, 16) || !aligned_to(lora_b, 16) || (absmax8 != nullptr && (absmax_code == nullptr || absmax_offset == nullptr)))
+        return false;
+    StreamArgs a;
+#ifdef BNB_PROFILING
+    a.dbg = nullptr;
+#endif
+    a.A = A;
+    a.code16 = nullptr;
+    a.M = M;
+    a.K = K;
+    a.bs_shift = ilog2(blocksize);
+    a.rows_total = N;
+    a.nmat = 1;
+    for (int i = 0; i < kMaxGroup; ++i)
+        a.mat[i] = StreamMat{B, absmax, absmax8, absmax_code, absmax_offset, out, bias, N, i == 0 ? 0 : 0x7FFFFFFF};
+    a.lora_t = lora_t;
+    a.lora_b = lora_b;
+    a.lora_r = r;
+    a.lora_scaling = scaling;
+    if (dtype == 2)
+        launch_lora_flags<bf16>(a, quant_type, stream);
+    else
+        launch_lora_flags<f16>(a, quant_type, stream);
     BNB_CHECK_LAUNCH();
     g_last_gemm_kernel = kKernelStream;
     return true;

@@ -496,6 +496,54 @@ class FFN4bit(nn.Module):
         return ffn_4bit(xc, self.gate_up, self.gate_up_state, down.weight, down.weight.quant_state, gate_up_bias=gb, down_bias=db)
 
 
+class Linear4bitLoRA(nn.Module):
+    """A :class:`Linear4bit` base layer with ONE LoRA adapter beside it, ``base(x) + scaling * lora_B(lora_A(x))``, as TWO launches for
+    a decode step: ``t = F.linear(x, lora_A)`` and the base layer's fused matmul with the adapter term as its epilogue
+    (:func:`bitsandbytes_amd.matmul_4bit_lora`; its two-launch composition where the fused launch does not serve the call). Inference
+    only; no dropout, no DoRA.
+
+    Build it with :meth:`from_linear` AFTER the checkpoint is loaded and the base layer is quantized on the device. The base layer is
+    held by reference - its packed bytes are not copied - and the adapter matrices are cast ONCE to the compute dtype, contiguous. The
+    module is not part of any state dict: the base layer and the adapter keep owning what a checkpoint stores."""
+
+    def __init__(self, base: "Linear4bit", lora_A: torch.Tensor, lora_B: torch.Tensor, scaling: float):
+        super().__init__()
+        object.__setattr__(self, "base", base)  # (referenced, not registered: state_dict() of this module is empty)
+        self.register_buffer("lora_A", lora_A, persistent=False)
+        self.register_buffer("lora_B", lora_B, persistent=False)
+        self.scaling = float(scaling)
+
+    @classmethod
+    def from_linear(cls, base: "Linear4bit", lora_A: torch.Tensor, lora_B: torch.Tensor, scaling: float) -> "Linear4bitLoRA":
+        fix_4bit_weight_quant_state_from_module(base)
+        if getattr(base.weight, "quant_state", None) is None:
+            raise ValueError("Linear4bitLoRA.from_linear: the base layer must be quantized (load the checkpoint and move the model to the device first)")
+        if lora_A.dim() != 2 or lora_B.dim() != 2 or lora_A.shape[1] != base.in_features or lora_B.shape[0] != base.out_features \
+                or lora_A.shape[0] != lora_B.shape[1]:
+            raise ValueError(f"Linear4bitLoRA.from_linear: lora_A must be [r, {base.in_features}] and lora_B [{base.out_features}, r], "
+                             f"got {tuple(lora_A.shape)} and {tuple(lora_B.shape)}")
+        cd = base.compute_dtype if base.compute_dtype is not None else lora_A.dtype
+        dev = base.weight.device
+        return cls(base, lora_A.detach().to(device=dev, dtype=cd).contiguous(), lora_B.detach().to(device=dev, dtype=cd).contiguous(), scaling)
+
+    def forward(self, x: torch.Tensor):
+        from ..autograd import matmul_4bit_lora
+
+        base = self.base
+        fix_4bit_weight_quant_state_from_module(base)
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("Linear4bitLoRA is inference only (no autograd formula): call it under torch.no_grad() or with detached inputs")
+        inp_dtype = x.dtype
+        xc = x.to(self.lora_A.dtype)
+        bias = base.bias
+        if bias is not None:
+            bias = bias.detach()
+            if bias.dtype != xc.dtype:
+                bias = bias.to(xc.dtype)
+        t = torch.nn.functional.linear(xc, self.lora_A)
+        return matmul_4bit_lora(xc, base.weight, base.weight.quant_state, t, self.lora_B, self.scaling, bias=bias).to(inp_dtype)
+
+
 class LinearFP4(Linear4bit):
     def __init__(self, input_features, output_features, bias=True, compute_dtype=None, compress_statistics=True,
                  quant_storage=torch.uint8, device=None):

@@ -189,6 +189,19 @@ int bnb_mi355x_gemm_4bit_experts_ffn_supported(int dtype, int E, int N, int K, i
  * needs no device beyond the CU count the route queries use) and compose the plain call with silu and a multiply where it says 0. */
 void bnb_mi355x_gemm_4bit_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K, int blocksize, int quant_type, bnb_stream_t stream);
 int bnb_mi355x_gemm_4bit_gated_supported(int dtype, int M, int N, int K, int blocksize);
+/* LoRA adapter beside a 4-bit base layer, y = base(x) + scaling * lora_B(lora_A(x)), with the adapter term as the EPILOGUE of the
+ * fused matmul: A [M, K], B / statistics / bias as for bnb_mi355x_gemm_4bit (fp32 absmax, or nested statistics with absmax_8bit != NULL),
+ * lora_t [M, r] = x @ lora_A^T (the caller's small matmul), lora_b [N, r] = lora_B.weight as stored (row-major), both of A's type:
+ *     lora[m, n] = sum_{j < r} float(t[m, j]) * float(B_l[n, j])      fp32, in an order that depends on r (and the family) only
+ *     out[m, n]  = T((acc[m, n] + bias[n]) + scaling * lora[m, n])    acc = the plain call's fp32 sum; ONE rounding to T
+ * The launch is the kernel family the plain call on the same matrix, M and statistics runs, and it exists only where that family is the
+ * streaming kernel (1) or the streaming MFMA kernel (7); bnb_mi355x_last_gemm_kernel reports 1 or 7. With t == 0 the result is the
+ * plain call's. dtype 1 / 2 (fp16 / bf16) only, 1 <= M <= 16, blocksize >= 64, K % blocksize == 0, r % 8 == 0, 8 <= r <= 128,
+ * A / B / lora_t / lora_b 16-byte aligned. A call outside these preconditions prints a message and ends the process, like every failed
+ * launch of this ABI: ask bnb_mi355x_gemm_4bit_lora_supported first (pure host logic over the shapes, aligned pointers assumed, 256 CUs
+ * without a device) and add the adapter term with a second launch where it says 0. */
+void bnb_mi355x_gemm_4bit_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r, int M, int N, int K, int blocksize, int quant_type, bnb_stream_t stream);
+int bnb_mi355x_gemm_4bit_lora_supported(int dtype, int M, int N, int K, int blocksize, int nested, int r);
 
 /* Grouped gemm_4bit: `count` weight matrices applied to the SAME activations A[M, K] in one launch -
  *   out[i][M, N[i]] = A * dequant(B[i])^T (+ bias[i])        i = 0 .. count-1
