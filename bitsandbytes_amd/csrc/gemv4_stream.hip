@@ -898,8 +898,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
                     // gated production: this thread's row and its neighbour's are (gate, up) of activation row / 2. silu in fp32
                     // ( g / (1 + exp(-g)), exact expf and IEEE division: torch's own kernel ), rounded to T; the product in fp32,
                     // rounded to T - bit for bit what `F.silu(g) * u` gives on the T-valued outputs of the two unsharded layers
-                    // (tests/checks/peer_ranks.py sweeps every finite 16-bit pattern of g). Rows come in fours (host-enforced): the
-                    // thread of row 4 i stores ONE granule = activations 2 i, 2 i + 1 of this rank.
+                    // (tests/checks/peer_ranks.py sweeps every finite 16-bit pattern of g here; tests/test_gpu_epilogue_values.py sweeps
+                    // every pattern through the kGated epilogue above and its copies in gemm4_mfma_sm.hip and gemm4_experts.hip).
+                    // Rows come in fours (host-enforced): the thread of row 4 i stores ONE granule = activations 2 i, 2 i + 1 of
+                    // this rank.
                     const float gf = static_cast<float>(tv), uf = static_cast<float>(__builtin_bit_cast(T, static_cast<unsigned short>(other)));
                     const T st = static_cast<T>(gf / (1.0f + expf(-gf)));
                     const T at = static_cast<T>(__fmul_rn(static_cast<float>(st), uf));
