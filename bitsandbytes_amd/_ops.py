@@ -548,3 +548,40 @@ def _(A, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: str, lora
       absmax_code=None, absmax_offset=None):
     N, _, _ = _check_gemm_4bit_lora(A, B, shapeB, absmax, blocksize, quant_type, lora_t, lora_b, bias, absmax_8bit, absmax_code, absmax_offset)
     return torch.empty((*A.shape[:-1], N), dtype=A.dtype, device=A.device)
+
+
+# ---------------------------------------------------------------------------------------------- lora_shrink
+# Not a reference op: the LoRA "shrink" matmul of a decode step, t = x @ lora_a^T, as a kernel of this library - the launch in front of
+# gemm_4bit_lora. x [*, K], lora_a [R, K] = lora_A.weight as stored, or several of them concatenated along dim 0 (`splits`: their row
+# counts); both 16-bit, contiguous. t[m, j] = T(sum_k x[m, k] * lora_a[j, k]): fp32 sum in an order that depends on K alone, ONE rounding.
+# Returns ONE buffer: without splits it is viewed as [*, R]; with splits it is flat, [M * R], and part i is the CONTIGUOUS [M, r_i]
+# matrix at element offset M * (r_0 + ... + r_{i-1}) - what gemm_4bit_lora takes as lora_t. Served for 1 ... 16 rows, K % 64 == 0,
+# R % 8 == 0, 8 <= R <= 1024, up to 8 splits of 8 ... 128 rows each a multiple of 8 (backends/hip.py: lora_shrink_supported); anything
+# else raises. Inference only: no autograd formula.
+torch.library.define("bitsandbytes_amd::lora_shrink", "(Tensor x, Tensor lora_a, int[]? splits=None) -> Tensor")
+
+LORA_SHRINK_MAX_SPLITS = 8
+
+
+def _check_lora_shrink(x, lora_a, splits):
+    """Argument checks shared by the fake kernel and the device kernel; returns (M, R, K)."""
+    torch._check(lora_a.dim() == 2, lambda: f"lora_a must be [R, K] (lora_A.weight as stored), got {tuple(lora_a.shape)}")
+    R, K = int(lora_a.shape[0]), int(lora_a.shape[1])
+    torch._check(R > 0 and K > 0, lambda: f"lora_a must be [R, K] with positive sizes, got {tuple(lora_a.shape)}")
+    torch._check(x.dtype in _FLOAT_DTYPES, lambda: f"x must be a 16/32-bit float tensor, got {x.dtype}")
+    torch._check(x.dim() >= 1 and x.shape[-1] == K, lambda: f"x inner dim ({x.shape[-1] if x.dim() else None}) must equal lora_a.shape[1] ({K})")
+    torch._check(lora_a.dtype == x.dtype and lora_a.device == x.device, lambda: f"lora_a must be a {x.dtype} tensor on x's device")
+    torch._check(x.is_contiguous() and lora_a.is_contiguous(), lambda: "x and lora_a must be contiguous")
+    if splits is not None:
+        torch._check(1 <= len(splits) <= LORA_SHRINK_MAX_SPLITS, lambda: f"splits must hold 1 ... {LORA_SHRINK_MAX_SPLITS} row counts, got {len(splits)}")
+        torch._check(all(int(r) > 0 for r in splits) and sum(int(r) for r in splits) == R,
+                     lambda: f"splits must be positive and sum to R = lora_a.shape[0] ({R}), got {list(splits)}")
+    return x.numel() // K, R, K
+
+
+@register_fake("bitsandbytes_amd::lora_shrink")
+def _(x, lora_a, splits: Optional[Sequence[int]] = None):
+    M, R, _ = _check_lora_shrink(x, lora_a, splits)
+    if splits is None:
+        return torch.empty((*x.shape[:-1], R), dtype=x.dtype, device=x.device)
+    return torch.empty((M * R,), dtype=x.dtype, device=x.device)

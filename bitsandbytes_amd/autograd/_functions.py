@@ -9,6 +9,7 @@ fused into the GEMM kernel.
 """
 from __future__ import annotations
 
+from collections.abc import Sequence
 from typing import Optional
 from warnings import warn
 
@@ -351,6 +352,45 @@ def matmul_4bit_lora(x: torch.Tensor, weight: torch.Tensor, quant_state: F.Quant
     y = matmul_4bit(x, weight, quant_state, bias=bias)
     out = torch.addmm(y.reshape(-1, N), lora_t.reshape(-1, r).to(y.dtype), lora_b.to(y.dtype).t(), alpha=float(scaling))
     return out.view(*x.shape[:-1], N)
+
+
+def lora_shrink(x: torch.Tensor, lora_A: torch.Tensor, splits: Optional[Sequence[int]] = None):
+    """``t = x @ lora_A.T`` - the LoRA "shrink" matmul in front of :func:`matmul_4bit_lora` - as ONE hand-written launch. ``x``:
+    ``[*, K]``; ``lora_A``: ``[R, K]``, PEFT's ``lora_A.weight`` as stored, or the ``lora_A`` of several layers that share ``x`` (Q/K/V,
+    gate/up) concatenated along dim 0 with ``splits = (r_0, r_1, ...)``. Returns ``[*, R]``, or with ``splits`` a tuple of CONTIGUOUS
+    ``[*, r_i]`` tensors - views into one buffer, each 16-byte aligned, each ready to be a member's ``lora_t``.
+
+    The kernel serves 1 ... 16 rows of fp16 / bf16 on the device, ``K % 64 == 0``, ``R % 8 == 0``, ``8 <= R <= 1024``, up to 8 splits
+    of 8 ... 128 rows, each a multiple of 8 (``backends.hip.lora_shrink_supported``): an fp32 sum in an order that depends on ``K``
+    alone, rounded once, so a stacked call's parts are bit-identical to separate calls on the members. Every other call - CPU tensors,
+    fp32, more rows, misaligned operands, classes the measurements exclude - composes ``F.linear`` and a ``.contiguous()`` per part,
+    whose bits are the BLAS library's. Neither path reads data on the host, so both can be captured in a graph. Inference only: there
+    is no autograd formula."""
+    if lora_A.dim() != 2 or x.dim() < 1 or x.shape[-1] != lora_A.shape[1]:
+        raise ValueError(f"lora_shrink: lora_A must be [R, K] and x [*, K], got {tuple(lora_A.shape)} and {tuple(x.shape)}")
+    R, K = int(lora_A.shape[0]), int(lora_A.shape[1])
+    if splits is not None:
+        splits = [int(r) for r in splits]
+        if not splits or min(splits) < 1 or sum(splits) != R:
+            raise ValueError(f"lora_shrink: splits must be positive and sum to lora_A.shape[0] ({R}), got {splits}")
+    if torch.is_grad_enabled() and (x.requires_grad or lora_A.requires_grad):
+        raise RuntimeError("lora_shrink is inference only (no autograd formula): call it under torch.no_grad() or with detached inputs")
+    lead = tuple(x.shape[:-1])
+    M = x.numel() // K if K else 0
+    if x.device.type == "cuda" and lora_A.device == x.device and lora_A.dtype == x.dtype and M > 0 and not _is_compiling():
+        from ..backends import hip
+
+        if hip.lora_shrink_supported(x.dtype, M, R, K) and hip.lora_shrink_splits_ok(splits):
+            xc, ac = x.contiguous(), lora_A.contiguous()
+            if xc.data_ptr() % 16 == 0 and ac.data_ptr() % 16 == 0:
+                buf = torch.ops.bitsandbytes_amd.lora_shrink.default(xc, ac, splits)
+                if splits is None:
+                    return buf
+                return tuple(p.view(*lead, r) for p, r in zip(buf.split([M * r for r in splits]), splits))
+    t = torch.nn.functional.linear(x, lora_A.to(x.dtype))
+    if splits is None:
+        return t
+    return tuple(p.contiguous() for p in t.split(splits, dim=-1))
 
 
 def matmul_4bit_grouped(A: torch.Tensor, weights, quant_states, biases=None, outs=None):

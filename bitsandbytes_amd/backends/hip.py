@@ -12,6 +12,7 @@ dequantize once, then ``F.linear`` on hipBLASLt (reference :904-916).
 """
 from __future__ import annotations
 
+import ctypes as ct
 import functools
 from collections.abc import Sequence
 from math import prod
@@ -21,7 +22,7 @@ from warnings import warn
 import torch
 
 from .._ops import (GATED_CODES, _check_gemm_4bit_experts, _check_gemm_4bit_experts_ffn, _check_gemm_4bit_gated, _check_gemm_4bit_lora,
-                     register_kernel)
+                     _check_lora_shrink, register_kernel)
 from ..cextension import lib
 
 _DT_NAME = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}
@@ -649,6 +650,39 @@ def _(A, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: str, lora
             _ptr(bias if bias is None else bias.contiguous()), lora_t.data_ptr(), lora_b.data_ptr(), float(scaling), r, M, N, K, blocksize,
             _QT_CODE[quant_type], _stream(A),
         )
+    return out
+
+
+# ------------------------------------------------------------------------------------------ lora_shrink
+def lora_shrink_supported(dtype: torch.dtype, M: int, R: int, K: int) -> bool:
+    """Whether ``bitsandbytes_amd::lora_shrink`` has a kernel for ``M`` rows against ``R`` adapter rows of length ``K``: 16-bit operands,
+    ``1 <= M <= 16``, ``K % 64 == 0``, ``R % 8 == 0``, ``8 <= R <= 1024``, minus the classes the measurements exclude (pure host logic of
+    the library; no device is queried)."""
+    if dtype not in (torch.float16, torch.bfloat16) or max(M, R, K) >= 2**31 or min(M, R, K) < 1:
+        return False
+    return bool(lib.bnb_mi355x_lora_shrink_supported(_DT_CODE[dtype], M, R, K))
+
+
+def lora_shrink_splits_ok(splits) -> bool:
+    """Whether the kernel takes this split table: 1 ... 8 parts of 8 ... 128 rows, each a multiple of 8 (``None``: no splits)."""
+    return splits is None or (1 <= len(splits) <= 8 and all(8 <= int(r) <= 128 and int(r) % 8 == 0 for r in splits))
+
+
+@register_kernel("bitsandbytes_amd::lora_shrink", "cuda")
+def _(x, lora_a, splits: Optional[Sequence[int]] = None):
+    """One launch of csrc/lora_shrink.hip; the split table travels by value in the kernel's arguments."""
+    M, R, K = _check_lora_shrink(x, lora_a, splits)
+    out = torch.empty((*x.shape[:-1], R) if splits is None else (M * R,), dtype=x.dtype, device=x.device)
+    if M == 0:
+        return out
+    if (not lora_shrink_supported(x.dtype, M, R, K) or not lora_shrink_splits_ok(splits) or x.data_ptr() % 16 or lora_a.data_ptr() % 16
+            or out.data_ptr() % 16):
+        raise ValueError(f"lora_shrink: no kernel for M={M}, R={R}, K={K}, splits={None if splits is None else list(splits)}, dtype={x.dtype} "
+                         "(x and lora_a 16-byte aligned); use F.linear - bitsandbytes_amd.lora_shrink does")
+    n = 0 if splits is None else len(splits)
+    table = (ct.c_int * n)(*[int(r) for r in splits]) if n else None
+    with _device_of(x):
+        lib.bnb_mi355x_lora_shrink(_DT_CODE[x.dtype], x.data_ptr(), lora_a.data_ptr(), out.data_ptr(), M, R, K, table, n, _stream(x))
     return out
 
 

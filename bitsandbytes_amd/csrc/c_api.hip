@@ -73,6 +73,9 @@ bool gemm_4bit_sm_lora(int dtype, const void* A, const uint8_t* B, const float* 
                        const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r,
                        int M, int N, int K, int blocksize, int quant_type, hipStream_t stream);
 extern thread_local TlsKnob g_mfma_knob0, g_mfma_knob1;
+// lora_shrink.hip
+bool lora_shrink_supported(int dtype, int M, int R, int K);
+bool lora_shrink(int dtype, const void* x, const void* lora_a, void* t, int M, int R, int K, const int* splits, int n_splits, hipStream_t stream);
 // gemm4_grad_input.hip
 bool gemm_4bit_grad_input_supported(int dtype, const void* G, const uint8_t* B, int M, int N, int K, int blocksize);
 size_t gemm_4bit_grad_input_workspace_bytes(int M, int N, int K);
@@ -527,6 +530,16 @@ int bnb_mi355x_gemm_4bit_lora_supported(int dtype, int M, int N, int K, int bloc
                ? 1
                : 0;
 }
+
+// ------------------------------------------------------------------ LoRA shrink (t = x lora_A^T, the launch in front of gemm_4bit_lora)
+void bnb_mi355x_lora_shrink(int dtype, const void* x, const void* lora_a, void* t, int M, int R, int K, const int* splits, int n_splits, bnb_stream_t s) {
+    if (!lora_shrink(dtype, x, lora_a, t, M, R, K, splits, n_splits, S(s))) {
+        fprintf(stderr, "bitsandbytes_amd: lora_shrink: no kernel for dtype %d, M=%d, R=%d, K=%d, n_splits=%d (fp16 / bf16, 1 <= M <= 16, K %% 64 == 0, R %% 8 == 0, 8 <= R <= 1024, up to 8 splits of 8 ... 128 rows, each a multiple of 8, that sum to R; x / lora_a / t 16-byte aligned)\n",
+                dtype, M, R, K, n_splits);
+        exit(1);
+    }
+}
+int bnb_mi355x_lora_shrink_supported(int dtype, int M, int R, int K) { return lora_shrink_supported(dtype, M, R, K) ? 1 : 0; }
 
 // ------------------------------------------------------------------ peer chain (the all-gather fused into the gemv launches)
 static uint32_t peer_chain_spin_bound() {

@@ -512,6 +512,9 @@ class Linear4bitLoRA(nn.Module):
         self.register_buffer("lora_A", lora_A, persistent=False)
         self.register_buffer("lora_B", lora_B, persistent=False)
         self.scaling = float(scaling)
+        # True: t = x @ lora_A^T comes from the library's own launch (bitsandbytes_amd.lora_shrink) instead of F.linear. Off by
+        # default: the two differ in the order of the fp32 sum, so the default forward keeps the bits it had.
+        self.fused_shrink = False
 
     @classmethod
     def from_linear(cls, base: "Linear4bit", lora_A: torch.Tensor, lora_B: torch.Tensor, scaling: float) -> "Linear4bitLoRA":
@@ -526,8 +529,10 @@ class Linear4bitLoRA(nn.Module):
         dev = base.weight.device
         return cls(base, lora_A.detach().to(device=dev, dtype=cd).contiguous(), lora_B.detach().to(device=dev, dtype=cd).contiguous(), scaling)
 
-    def forward(self, x: torch.Tensor):
-        from ..autograd import matmul_4bit_lora
+    def forward(self, x: torch.Tensor, t: Optional[torch.Tensor] = None):
+        """``t``: a precomputed ``x @ lora_A.T`` (``[*, r]``) - a caller that shrank the stacked ``lora_A`` of several layers that share
+        ``x`` in one launch (``lora_shrink(x, stacked, splits=...)``) passes each member its part."""
+        from ..autograd import lora_shrink, matmul_4bit_lora
 
         base = self.base
         fix_4bit_weight_quant_state_from_module(base)
@@ -540,7 +545,10 @@ class Linear4bitLoRA(nn.Module):
             bias = bias.detach()
             if bias.dtype != xc.dtype:
                 bias = bias.to(xc.dtype)
-        t = torch.nn.functional.linear(xc, self.lora_A)
+        if t is None:
+            t = lora_shrink(xc, self.lora_A) if self.fused_shrink else torch.nn.functional.linear(xc, self.lora_A)
+        elif t.dtype != xc.dtype:
+            t = t.to(xc.dtype)
         return matmul_4bit_lora(xc, base.weight, base.weight.quant_state, t, self.lora_B, self.scaling, bias=bias).to(inp_dtype)
 
 

@@ -202,6 +202,22 @@ int bnb_mi355x_gemm_4bit_gated_supported(int dtype, int M, int N, int K, int blo
  * without a device) and add the adapter term with a second launch where it says 0. */
 void bnb_mi355x_gemm_4bit_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r, int M, int N, int K, int blocksize, int quant_type, bnb_stream_t stream);
 int bnb_mi355x_gemm_4bit_lora_supported(int dtype, int M, int N, int K, int blocksize, int nested, int r);
+/* LoRA shrink, the launch in front of bnb_mi355x_gemm_4bit_lora: x [M, K] and lora_a [R, K] row-major (lora_A.weight as stored, or up
+ * to eight of them concatenated along dim 0), T = fp16 / bf16 (dtype 1 / 2) for both and for t:
+ *     t[m, j] = T( sum_{k < K} float(x[m, k]) * float(lora_a[j, k]) )      fp32 sum, ONE rounding to T
+ * The order of the sum is a function of K alone: K is cut into steps of 32 k, wavefront w of sixteen adds steps w, w + 16, ... in
+ * ascending order into one fp32 accumulator (a step is one v_mfma_f32_16x16x32), and the sixteen accumulators are added in ascending
+ * w. It does not depend on M, on R, on where row j sits in lora_a, on the splits or on the grid: a stacked call's parts are
+ * bit-identical to separate calls on the members. One launch, no workspace, no traffic between workgroups.
+ * splits (a HOST array of n_splits ints, read during the call and passed to the kernel by value; n_splits 0 ... 8): with n_splits == 0
+ * t is [M, R]. Otherwise part i is a CONTIGUOUS [M, splits[i]] matrix at element offset M * (splits[0] + ... + splits[i-1]) of t (M * R
+ * elements in all), so every part is 16-byte aligned and can be passed as lora_t to bnb_mi355x_gemm_4bit_lora as it is.
+ * 1 <= M <= 16, K % 64 == 0, R % 8 == 0, 8 <= R <= 1024, every splits[i] % 8 == 0 and in [8, 128], sum of splits == R, x / lora_a / t
+ * 16-byte aligned. A call outside these preconditions prints a message and ends the process. bnb_mi355x_lora_shrink_supported (pure
+ * host logic, aligned pointers assumed) answers 1 where the preconditions hold AND the launch measured ahead of the BLAS matmul it
+ * replaces; compose the matmul yourself where it says 0. */
+void bnb_mi355x_lora_shrink(int dtype, const void* x, const void* lora_a, void* t, int M, int R, int K, const int* splits, int n_splits, bnb_stream_t stream);
+int bnb_mi355x_lora_shrink_supported(int dtype, int M, int R, int K);
 
 /* Grouped gemm_4bit: `count` weight matrices applied to the SAME activations A[M, K] in one launch -
  *   out[i][M, N[i]] = A * dequant(B[i])^T (+ bias[i])        i = 0 .. count-1
