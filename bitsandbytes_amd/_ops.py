@@ -585,3 +585,78 @@ def _(x, lora_a, splits: Optional[Sequence[int]] = None):
     if splits is None:
         return torch.empty((*x.shape[:-1], R), dtype=x.dtype, device=x.device)
     return torch.empty((M * R,), dtype=x.dtype, device=x.device)
+
+
+# ---------------------------------------------------------------------------------------------- lora_shrink_ids
+# Not a reference op: lora_shrink for a mixed-adapter decode batch - every row of x (a request) names its own adapter. lora_a
+# [A_n, R, K] = the lora_A.weight of A_n adapters, stacked (1 <= A_n <= 64); ids [*] with x's leading dims, int32 or int64, on x's device
+# and read by the kernel only. t[m] = lora_shrink(x, lora_a[ids[m]])[m], bit for bit, where 0 <= ids[m] < A_n; a row with any other id
+# has no adapter and is zeros. `splits` and the returned buffer: as for lora_shrink. Served where lora_shrink's preconditions hold
+# (backends/hip.py: lora_shrink_ids_supported); anything else raises. Inference only: no autograd formula.
+torch.library.define("bitsandbytes_amd::lora_shrink_ids", "(Tensor x, Tensor lora_a, Tensor ids, int[]? splits=None) -> Tensor")
+
+LORA_MAX_ADAPTERS = 64
+
+
+def _check_lora_shrink_ids(x, lora_a, ids, splits):
+    """Argument checks shared by the fake kernel and the device kernel; returns (M, A_n, R, K)."""
+    torch._check(lora_a.dim() == 3, lambda: f"lora_a must be [A_n, R, K] (the adapters' lora_A.weight, stacked), got {tuple(lora_a.shape)}")
+    A_n, R, K = (int(v) for v in lora_a.shape)
+    torch._check(A_n > 0 and R > 0 and K > 0, lambda: f"lora_a must be [A_n, R, K] with positive sizes, got {tuple(lora_a.shape)}")
+    torch._check(A_n <= LORA_MAX_ADAPTERS, lambda: f"lora_a stacks {A_n} adapters, at most {LORA_MAX_ADAPTERS} are served")
+    torch._check(x.dtype in _FLOAT_DTYPES, lambda: f"x must be a 16/32-bit float tensor, got {x.dtype}")
+    torch._check(x.dim() >= 1 and x.shape[-1] == K, lambda: f"x inner dim ({x.shape[-1] if x.dim() else None}) must equal lora_a.shape[2] ({K})")
+    torch._check(lora_a.dtype == x.dtype and lora_a.device == x.device, lambda: f"lora_a must be a {x.dtype} tensor on x's device")
+    torch._check(ids.dtype in (torch.int32, torch.int64), lambda: f"ids must be int32 or int64, got {ids.dtype}")
+    torch._check(tuple(ids.shape) == tuple(x.shape[:-1]), lambda: f"ids must be [*] = {tuple(x.shape[:-1])} (x's leading dims), got {tuple(ids.shape)}")
+    torch._check(ids.device == x.device, lambda: "ids must live on x's device")
+    torch._check(x.is_contiguous() and lora_a.is_contiguous() and ids.is_contiguous(), lambda: "x, lora_a and ids must be contiguous")
+    if splits is not None:
+        torch._check(1 <= len(splits) <= LORA_SHRINK_MAX_SPLITS, lambda: f"splits must hold 1 ... {LORA_SHRINK_MAX_SPLITS} row counts, got {len(splits)}")
+        torch._check(all(int(r) > 0 for r in splits) and sum(int(r) for r in splits) == R,
+                     lambda: f"splits must be positive and sum to R = lora_a.shape[1] ({R}), got {list(splits)}")
+    return x.numel() // K, A_n, R, K
+
+
+@register_fake("bitsandbytes_amd::lora_shrink_ids")
+def _(x, lora_a, ids, splits: Optional[Sequence[int]] = None):
+    M, _, R, _ = _check_lora_shrink_ids(x, lora_a, ids, splits)
+    if splits is None:
+        return torch.empty((*x.shape[:-1], R), dtype=x.dtype, device=x.device)
+    return torch.empty((M * R,), dtype=x.dtype, device=x.device)
+
+
+# ---------------------------------------------------------------------------------------------- gemm_4bit_lora_ids
+# Not a reference op: gemm_4bit_lora for a mixed-adapter decode batch. lora_b [A_n, N, r] = the lora_B.weight of A_n adapters of one
+# rank, stacked (1 <= A_n <= 64); scalings [A_n] float32; ids [*] with A's leading dims, int32 or int64; all on A's device and read by
+# the kernel only. Row m: out = T((acc + bias) + scalings[ids[m]] * (t[m] @ lora_b[ids[m]]^T)), the bits of gemm_4bit_lora with that
+# adapter, where 0 <= ids[m] < A_n; a row with any other id has no adapter and gets gemm_4bit's bits (its lora_t row is never read).
+# Served exactly where gemm_4bit_lora is (backends/hip.py: gemm_4bit_lora_ids_supported); anything else raises. Inference only.
+torch.library.define(
+    "bitsandbytes_amd::gemm_4bit_lora_ids",
+    "(Tensor A, Tensor B, int[] shapeB, Tensor absmax, int blocksize, str quant_type, Tensor lora_t, Tensor lora_b, Tensor scalings, Tensor ids, "
+    "Tensor? bias=None, Tensor? absmax_8bit=None, Tensor? absmax_code=None, Tensor? absmax_offset=None) -> Tensor",
+)
+
+
+def _check_gemm_4bit_lora_ids(A, B, shapeB, absmax, blocksize, quant_type, lora_t, lora_b, scalings, ids, bias, absmax_8bit, absmax_code, absmax_offset):
+    """Argument checks shared by the fake kernel and the device kernel; returns (N, K, r, A_n)."""
+    torch._check(lora_b.dim() == 3, lambda: f"lora_b must be [A_n, N, r] (the adapters' lora_B.weight, stacked), got {tuple(lora_b.shape)}")
+    A_n = int(lora_b.shape[0])
+    torch._check(1 <= A_n <= LORA_MAX_ADAPTERS, lambda: f"lora_b must stack 1 ... {LORA_MAX_ADAPTERS} adapters, got {A_n}")
+    torch._check(lora_b.is_contiguous(), lambda: "lora_t and lora_b must be contiguous")
+    N, K, r = _check_gemm_4bit_lora(A, B, shapeB, absmax, blocksize, quant_type, lora_t, lora_b[0], bias, absmax_8bit, absmax_code, absmax_offset)
+    torch._check(scalings.dtype == torch.float32 and tuple(scalings.shape) == (A_n,) and scalings.device == A.device and scalings.is_contiguous(),
+                 lambda: f"scalings must be a contiguous float32 tensor [A_n] = [{A_n}] on A's device, got {scalings.dtype} {tuple(scalings.shape)}")
+    torch._check(ids.dtype in (torch.int32, torch.int64), lambda: f"ids must be int32 or int64, got {ids.dtype}")
+    torch._check(tuple(ids.shape) == tuple(A.shape[:-1]), lambda: f"ids must be [*] = {tuple(A.shape[:-1])} (A's leading dims), got {tuple(ids.shape)}")
+    torch._check(ids.device == A.device and ids.is_contiguous(), lambda: "ids must be contiguous and live on A's device")
+    return N, K, r, A_n
+
+
+@register_fake("bitsandbytes_amd::gemm_4bit_lora_ids")
+def _(A, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: str, lora_t, lora_b, scalings, ids, bias=None, absmax_8bit=None,
+      absmax_code=None, absmax_offset=None):
+    N, _, _, _ = _check_gemm_4bit_lora_ids(A, B, shapeB, absmax, blocksize, quant_type, lora_t, lora_b, scalings, ids, bias, absmax_8bit, absmax_code,
+                                           absmax_offset)
+    return torch.empty((*A.shape[:-1], N), dtype=A.dtype, device=A.device)

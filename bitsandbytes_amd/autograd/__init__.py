@@ -1,4 +1,4 @@
-from ._functions import (MatMul4Bit, ffn_4bit, lora_shrink, matmul_4bit, matmul_4bit_experts, matmul_4bit_gated, matmul_4bit_grouped, matmul_4bit_lora,
+from ._functions import (MatMul4Bit, ffn_4bit, lora_shrink, lora_shrink_ids, matmul_4bit, matmul_4bit_experts, matmul_4bit_gated, matmul_4bit_grouped, matmul_4bit_lora, matmul_4bit_lora_ids,
                          moe_ffn_4bit)
 
-__all__ = ["MatMul4Bit", "matmul_4bit", "matmul_4bit_experts", "matmul_4bit_grouped", "moe_ffn_4bit", "matmul_4bit_gated", "ffn_4bit", "matmul_4bit_lora", "lora_shrink"]
+__all__ = ["MatMul4Bit", "matmul_4bit", "matmul_4bit_experts", "matmul_4bit_grouped", "moe_ffn_4bit", "matmul_4bit_gated", "ffn_4bit", "matmul_4bit_lora", "lora_shrink", "lora_shrink_ids", "matmul_4bit_lora_ids"]

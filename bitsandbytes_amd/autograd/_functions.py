@@ -393,6 +393,110 @@ def lora_shrink(x: torch.Tensor, lora_A: torch.Tensor, splits: Optional[Sequence
     return tuple(p.contiguous() for p in t.split(splits, dim=-1))
 
 
+def matmul_4bit_lora_ids(x: torch.Tensor, weight: torch.Tensor, quant_state: F.QuantState, lora_t: torch.Tensor, lora_B: torch.Tensor,
+                         scalings: torch.Tensor, adapter_ids: torch.Tensor, bias: Optional[torch.Tensor] = None):
+    """:func:`matmul_4bit_lora` for a mixed-adapter decode batch: row ``m`` of ``x`` (a request) adds
+    ``scalings[id] * lora_t[m] @ lora_B[id].T`` with ``id = adapter_ids[m]``. ``lora_B``: ``[A_n, N, r]``, the ``lora_B.weight`` of
+    ``A_n`` adapters of one rank (``1 <= A_n <= 64``; pad smaller ranks with zeros), ``scalings``: ``[A_n]``, ``adapter_ids``: ``[*]``
+    with ``x``'s leading dims, int32 or int64, ``lora_t``: ``[*, r]`` from :func:`lora_shrink_ids`; all on ``x``'s device. A row whose
+    id is outside ``[0, A_n)`` has no adapter: it gets ``matmul_4bit``'s result, and its ``lora_t`` row is not used.
+
+    ONE launch wherever :func:`matmul_4bit_lora`'s fused launch exists (``backends.hip.gemm_4bit_lora_ids_supported``): the ids stay
+    on the device, and a row with an adapter has the bits of ``matmul_4bit_lora`` with that adapter at the same batch size. Every
+    other call gathers ``lora_B.index_select(0, ids)`` and adds ``scalings[ids] * torch.bmm(...)`` to ``matmul_4bit``'s output with the
+    rows without an adapter masked: NOT bit-identical to the fused call (two roundings), inside the same derived bound
+    (``tests/lora_cases.py: tolerance``). Neither path reads data on the host, so both can be captured in a graph and follow ids
+    written into the same buffer. Inference only: there is no autograd formula."""
+    if quant_state is None:
+        raise ValueError("quant_state is required")
+    if len(quant_state.shape) != 2:
+        raise ValueError(f"matmul_4bit_lora_ids: quant_state.shape must be [N, K], got {list(quant_state.shape)}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, lora_t, lora_B, scalings, bias)):
+        raise RuntimeError("matmul_4bit_lora_ids is inference only (no autograd formula): call it under torch.no_grad() "
+                           "or with detached inputs")
+    N, K = int(quant_state.shape[0]), int(quant_state.shape[1])
+    if x.shape[-1] != K:
+        raise ValueError(f"matmul_4bit_lora_ids: x inner dim ({x.shape[-1]}) must equal quant_state.shape[1] ({K})")
+    if lora_B.dim() != 3 or lora_B.shape[1] != N or tuple(lora_t.shape) != (*x.shape[:-1], lora_B.shape[2]):
+        raise ValueError(f"matmul_4bit_lora_ids: lora_B must be [A_n, N, r] = [A_n, {N}, r] and lora_t [*, r] with x's leading dims, "
+                         f"got {tuple(lora_B.shape)} and {tuple(lora_t.shape)}")
+    A_n, r = int(lora_B.shape[0]), int(lora_B.shape[2])
+    if not 1 <= A_n <= 64 or tuple(scalings.shape) != (A_n,):
+        raise ValueError(f"matmul_4bit_lora_ids: lora_B must stack 1 ... 64 adapters and scalings be [A_n], got {A_n} and {tuple(scalings.shape)}")
+    if adapter_ids.dtype not in (torch.int32, torch.int64) or tuple(adapter_ids.shape) != tuple(x.shape[:-1]) or adapter_ids.device != x.device:
+        raise ValueError(f"matmul_4bit_lora_ids: adapter_ids must be an int32 / int64 tensor of shape {tuple(x.shape[:-1])} (x's leading dims) "
+                         f"on x's device, got {adapter_ids.dtype} {tuple(adapter_ids.shape)} on {adapter_ids.device}")
+    if (x.numel() > 0 and weight.data_ptr() % 16 == 0 and lora_t.dtype == x.dtype and lora_B.dtype == x.dtype and scalings.device == x.device
+            and (bias is None or bias.dtype == x.dtype) and _lora_fused(x, quant_state, r)):
+        xc, tc, bc, ic = x.contiguous(), lora_t.contiguous(), lora_B.contiguous(), adapter_ids.contiguous()
+        sc = scalings.to(torch.float32).contiguous()
+        if xc.data_ptr() % 16 == 0 and tc.data_ptr() % 16 == 0 and bc.data_ptr() % 16 == 0:
+            op = torch.ops.bitsandbytes_amd.gemm_4bit_lora_ids.default
+            if not quant_state.nested:
+                return op(xc, weight.view(-1, 1), quant_state.shape, quant_state.absmax, quant_state.blocksize, quant_state.quant_type, tc, bc,
+                          sc, ic, bias=bias)
+            return op(xc, weight.view(-1, 1), quant_state.shape, quant_state.state2.absmax, quant_state.blocksize, quant_state.quant_type, tc, bc,
+                      sc, ic, bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code,
+                      absmax_offset=quant_state.offset)
+    y = matmul_4bit(x, weight, quant_state, bias=bias).reshape(-1, N)
+    ids = adapter_ids.reshape(-1).to(torch.int64)
+    valid = (ids >= 0) & (ids < A_n)
+    safe = torch.where(valid, ids, torch.zeros_like(ids))
+    # (the adapter term in fp32, added to the rounded base result and rounded once more: the two roundings of matmul_4bit_lora's composition)
+    term = torch.bmm(lora_B.index_select(0, safe).float(), lora_t.reshape(-1, r, 1).float()).view(-1, N)
+    out = (y.float() + term * scalings.to(device=y.device, dtype=torch.float32).index_select(0, safe).view(-1, 1)).to(y.dtype)
+    return torch.where(valid.view(-1, 1), out, y).view(*x.shape[:-1], N)  # (a select: no NaN from a t row or an adapter the row does not use)
+
+
+def lora_shrink_ids(x: torch.Tensor, lora_A: torch.Tensor, adapter_ids: torch.Tensor, splits: Optional[Sequence[int]] = None):
+    """:func:`lora_shrink` for a mixed-adapter decode batch: row ``m`` of ``x`` (a request) uses adapter ``adapter_ids[m]`` of the
+    stack ``lora_A`` ``[A_n, R, K]`` - the ``lora_A.weight`` of ``A_n`` adapters (``1 <= A_n <= 64``), or with ``splits`` the stacked
+    ``lora_A`` of several layers that share ``x``, per adapter. ``adapter_ids``: ``[*]`` with ``x``'s leading dims, int32 or int64, on
+    ``x``'s device. A row whose id is outside ``[0, A_n)`` has no adapter: its ``t`` is zeros. Returns ``[*, R]``, or with ``splits`` a
+    tuple of contiguous ``[*, r_i]`` tensors, as :func:`lora_shrink` does.
+
+    ONE launch where :func:`lora_shrink`'s kernel preconditions hold (``backends.hip.lora_shrink_ids_supported``): the ids are read by
+    the kernel only, the workgroups of adapters no row names read nothing, and a row with an adapter has the bits of
+    ``lora_shrink(x, lora_A[id])``'s row at the same batch size. Every other call - CPU tensors, fp32, more than 16 rows, misaligned
+    operands - gathers ``lora_A.index_select(0, ids)`` and composes ``torch.bmm`` with the rows without an adapter masked: the same
+    values inside ``lora_shrink``'s tolerance, the bits the BLAS library's. Neither path reads data on the host, so both can be
+    captured in a graph and follow ids written into the same buffer. Inference only: there is no autograd formula."""
+    if lora_A.dim() != 3 or x.dim() < 1 or x.shape[-1] != lora_A.shape[2]:
+        raise ValueError(f"lora_shrink_ids: lora_A must be [A_n, R, K] and x [*, K], got {tuple(lora_A.shape)} and {tuple(x.shape)}")
+    A_n, R, K = (int(v) for v in lora_A.shape)
+    if adapter_ids.dtype not in (torch.int32, torch.int64) or tuple(adapter_ids.shape) != tuple(x.shape[:-1]) or adapter_ids.device != x.device:
+        raise ValueError(f"lora_shrink_ids: adapter_ids must be an int32 / int64 tensor of shape {tuple(x.shape[:-1])} (x's leading dims) on "
+                         f"x's device, got {adapter_ids.dtype} {tuple(adapter_ids.shape)} on {adapter_ids.device}")
+    if not 1 <= A_n <= 64:
+        raise ValueError(f"lora_shrink_ids: lora_A must stack 1 ... 64 adapters, got {A_n}")
+    if splits is not None:
+        splits = [int(r) for r in splits]
+        if not splits or min(splits) < 1 or sum(splits) != R:
+            raise ValueError(f"lora_shrink_ids: splits must be positive and sum to lora_A.shape[1] ({R}), got {splits}")
+    if torch.is_grad_enabled() and (x.requires_grad or lora_A.requires_grad):
+        raise RuntimeError("lora_shrink_ids is inference only (no autograd formula): call it under torch.no_grad() or with detached inputs")
+    lead = tuple(x.shape[:-1])
+    M = x.numel() // K if K else 0
+    if x.device.type == "cuda" and lora_A.device == x.device and lora_A.dtype == x.dtype and M > 0 and not _is_compiling():
+        from ..backends import hip
+
+        if hip.lora_shrink_ids_supported(x.dtype, M, A_n, R, K) and hip.lora_shrink_splits_ok(splits):
+            xc, ac, ic = x.contiguous(), lora_A.contiguous(), adapter_ids.contiguous()
+            if xc.data_ptr() % 16 == 0 and ac.data_ptr() % 16 == 0:
+                buf = torch.ops.bitsandbytes_amd.lora_shrink_ids.default(xc, ac, ic, splits)
+                if splits is None:
+                    return buf
+                return tuple(p.view(*lead, r) for p, r in zip(buf.split([M * r for r in splits]), splits))
+    ids = adapter_ids.reshape(-1).to(torch.int64)
+    valid = (ids >= 0) & (ids < A_n)
+    gathered = lora_A.to(x.dtype).index_select(0, torch.where(valid, ids, torch.zeros_like(ids)))  # [M, R, K]
+    t = torch.bmm(gathered, x.reshape(-1, K, 1)).view(-1, R)
+    t = torch.where(valid.view(-1, 1), t, torch.zeros_like(t)).view(*lead, R)  # (a select: no 0 * NaN from an adapter the row does not use)
+    if splits is None:
+        return t
+    return tuple(p.contiguous() for p in t.split(splits, dim=-1))
+
+
 def matmul_4bit_grouped(A: torch.Tensor, weights, quant_states, biases=None, outs=None):
     """``[matmul_4bit(A, B_i, state_i, bias=bias_i) for i]`` for 4-bit weights that share their input - the Q/K/V
     projections of an attention block, the gate/up projections of an MLP. On MI355X a decode-sized batch (M <= 4) is

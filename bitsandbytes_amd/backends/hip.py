@@ -22,7 +22,8 @@ from warnings import warn
 import torch
 
 from .._ops import (GATED_CODES, _check_gemm_4bit_experts, _check_gemm_4bit_experts_ffn, _check_gemm_4bit_gated, _check_gemm_4bit_lora,
-                     _check_lora_shrink, register_kernel)
+                     _check_gemm_4bit_lora_ids,
+                     _check_lora_shrink, _check_lora_shrink_ids, register_kernel)
 from ..cextension import lib
 
 _DT_NAME = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}
@@ -683,6 +684,78 @@ def _(x, lora_a, splits: Optional[Sequence[int]] = None):
     table = (ct.c_int * n)(*[int(r) for r in splits]) if n else None
     with _device_of(x):
         lib.bnb_mi355x_lora_shrink(_DT_CODE[x.dtype], x.data_ptr(), lora_a.data_ptr(), out.data_ptr(), M, R, K, table, n, _stream(x))
+    return out
+
+
+# ------------------------------------------------------------------------------------------ gemm_4bit_lora_ids
+def gemm_4bit_lora_ids_supported(dtype: torch.dtype, M: int, N: int, K: int, blocksize: int, nested: bool, r: int, A_n: int) -> bool:
+    """Whether ``bitsandbytes_amd::gemm_4bit_lora_ids`` has a kernel: exactly where :func:`gemm_4bit_lora_supported` answers True,
+    for every stack of ``1 <= A_n <= 64`` adapters."""
+    if dtype not in (torch.float16, torch.bfloat16) or max(M, N, K, r, A_n) >= 2**31 or min(M, N, K, r, A_n) < 1:
+        return False
+    return bool(lib.bnb_mi355x_gemm_4bit_lora_ids_supported(_DT_CODE[dtype], M, N, K, blocksize, 1 if nested else 0, r, A_n))
+
+
+@register_kernel("bitsandbytes_amd::gemm_4bit_lora_ids", "cuda")
+def _(A, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: str, lora_t, lora_b, scalings, ids, bias=None, absmax_8bit=None,
+      absmax_code=None, absmax_offset=None):
+    """One launch of the streaming kernel's or the streaming MFMA kernel's mixed-adapter LoRA instance - the family the plain call runs."""
+    N, K, r, A_n = _check_gemm_4bit_lora_ids(A, B, shapeB, absmax, blocksize, quant_type, lora_t, lora_b, scalings, ids, bias, absmax_8bit,
+                                             absmax_code, absmax_offset)
+    M = A.numel() // K
+    out = torch.empty((*A.shape[:-1], N), dtype=A.dtype, device=A.device)
+    if M == 0:
+        return out
+    A = A.contiguous()
+    B = B.contiguous()
+    absmax = absmax.contiguous()
+    nested = absmax_8bit is not None
+    a8 = absmax_8bit.contiguous() if nested else None
+    code = absmax_code.contiguous() if nested else None
+    offset32 = absmax_offset.to(dtype=torch.float32) if nested else None
+    with _device_of(A):
+        # (inside the guard: the route depends on the current device's CU count)
+        if (not gemm_4bit_lora_ids_supported(A.dtype, M, N, K, blocksize, nested, r, A_n) or A.data_ptr() % 16 or B.data_ptr() % 16
+                or absmax.data_ptr() % 4 or lora_t.data_ptr() % 16 or lora_b.data_ptr() % 16 or ids.data_ptr() % ids.element_size()
+                or scalings.data_ptr() % 4):
+            raise ValueError(f"gemm_4bit_lora_ids: no kernel for M={M}, N={N}, K={K}, blocksize={blocksize}, r={r}, A_n={A_n}, dtype={A.dtype} "
+                             "(A, B, lora_t and lora_b 16-byte aligned); gather the adapters and add the term to gemm_4bit's output - "
+                             "matmul_4bit_lora_ids does")
+        lib.bnb_mi355x_gemm_4bit_lora_ids(
+            _DT_CODE[A.dtype], A.data_ptr(), B.data_ptr(), absmax.data_ptr(), _ptr(a8), _ptr(code), _ptr(offset32), out.data_ptr(),
+            _ptr(bias if bias is None else bias.contiguous()), lora_t.data_ptr(), lora_b.data_ptr(), scalings.data_ptr(), ids.data_ptr(),
+            ids.element_size(), A_n, r, M, N, K, blocksize, _QT_CODE[quant_type], _stream(A),
+        )
+    return out
+
+
+# ------------------------------------------------------------------------------------------ lora_shrink_ids
+def lora_shrink_ids_supported(dtype: torch.dtype, M: int, A_n: int, R: int, K: int) -> bool:
+    """Whether ``bitsandbytes_amd::lora_shrink_ids`` has a kernel for ``M`` rows against a stack of ``A_n`` adapters of ``R`` rows of
+    length ``K``: the preconditions of ``lora_shrink`` and ``1 <= A_n <= 64``, minus the classes the measurements exclude (pure host
+    logic of the library; no device is queried)."""
+    if dtype not in (torch.float16, torch.bfloat16) or max(M, A_n, R, K) >= 2**31 or min(M, A_n, R, K) < 1:
+        return False
+    return bool(lib.bnb_mi355x_lora_shrink_ids_supported(_DT_CODE[dtype], M, A_n, R, K))
+
+
+@register_kernel("bitsandbytes_amd::lora_shrink_ids", "cuda")
+def _(x, lora_a, ids, splits: Optional[Sequence[int]] = None):
+    """One launch of csrc/lora_shrink.hip's mixed-adapter kernel; the ids stay on the device."""
+    M, A_n, R, K = _check_lora_shrink_ids(x, lora_a, ids, splits)
+    out = torch.empty((*x.shape[:-1], R) if splits is None else (M * R,), dtype=x.dtype, device=x.device)
+    if M == 0:
+        return out
+    if (not lora_shrink_ids_supported(x.dtype, M, A_n, R, K) or not lora_shrink_splits_ok(splits) or x.data_ptr() % 16 or lora_a.data_ptr() % 16
+            or out.data_ptr() % 16 or ids.data_ptr() % ids.element_size()):
+        raise ValueError(f"lora_shrink_ids: no kernel for M={M}, A_n={A_n}, R={R}, K={K}, splits={None if splits is None else list(splits)}, "
+                         f"dtype={x.dtype} (x and lora_a 16-byte aligned); gather the adapters and use torch.bmm - "
+                         "bitsandbytes_amd.lora_shrink_ids does")
+    n = 0 if splits is None else len(splits)
+    table = (ct.c_int * n)(*[int(r) for r in splits]) if n else None
+    with _device_of(x):
+        lib.bnb_mi355x_lora_shrink_ids(_DT_CODE[x.dtype], x.data_ptr(), lora_a.data_ptr(), ids.data_ptr(), ids.element_size(), out.data_ptr(),
+                                       M, A_n, R, K, table, n, _stream(x))
     return out
 
 

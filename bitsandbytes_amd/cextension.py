@@ -92,9 +92,16 @@ def _declare(dll: ct.CDLL) -> None:
     # (dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, lora_t, lora_b, scaling, r, M, N, K, blocksize, quant_type, stream)
     sig(["bnb_mi355x_gemm_4bit_lora"], [_I32] + [_VOID_P] * 10 + [ct.c_float] + [_I32] * 6 + [_VOID_P])
     sig(["bnb_mi355x_gemm_4bit_lora_supported"], [_I32] * 7, _I32)  # (dtype, M, N, K, blocksize, nested, r)
+    # (dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, lora_t, lora_b, scalings, ids, index_bytes, A_n, r, M, N, K,
+    #  blocksize, quant_type, stream)
+    sig(["bnb_mi355x_gemm_4bit_lora_ids"], [_I32] + [_VOID_P] * 12 + [_I32] * 8 + [_VOID_P])
+    sig(["bnb_mi355x_gemm_4bit_lora_ids_supported"], [_I32] * 8, _I32)  # (dtype, M, N, K, blocksize, nested, r, A_n)
     # (dtype, x, lora_a, t, M, R, K, splits (host int[n_splits] or NULL), n_splits, stream)
     sig(["bnb_mi355x_lora_shrink"], [_I32] + [_VOID_P] * 3 + [_I32] * 3 + [_VOID_P, _I32, _VOID_P])
     sig(["bnb_mi355x_lora_shrink_supported"], [_I32] * 4, _I32)  # (dtype, M, R, K)
+    # (dtype, x, lora_a, ids, index_bytes, t, M, A_n, R, K, splits (host int[n_splits] or NULL), n_splits, stream)
+    sig(["bnb_mi355x_lora_shrink_ids"], [_I32] + [_VOID_P] * 3 + [_I32, _VOID_P] + [_I32] * 4 + [_VOID_P, _I32, _VOID_P])
+    sig(["bnb_mi355x_lora_shrink_ids_supported"], [_I32] * 5, _I32)  # (dtype, M, A_n, R, K)
     # (dtype, A, count, B[], absmax[], absmax_8bit[], absmax_code[], absmax_offset[], out[], bias[], N[], M, K, blocksize, quant_type, stream)
     sig(["bnb_mi355x_gemm_4bit_grouped"], [_I32, _VOID_P, _I32] + [_VOID_P] * 8 + [_I32] * 4 + [_VOID_P])
     sig(["bnb_mi355x_gemm_4bit_grouped_route"], [_I32, _I32, _VOID_P, _I32, _I32, _I32], _I32)  # (dtype, count, N[], M, K, blocksize)
@@ -155,7 +162,9 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_gemm_4bit_experts_ffn", "bnb_mi355x_gemm_4bit_experts_ffn_supported",
        "bnb_mi355x_gemm_4bit_gated", "bnb_mi355x_gemm_4bit_gated_supported",
        "bnb_mi355x_gemm_4bit_lora", "bnb_mi355x_gemm_4bit_lora_supported",
+       "bnb_mi355x_gemm_4bit_lora_ids", "bnb_mi355x_gemm_4bit_lora_ids_supported",
        "bnb_mi355x_lora_shrink", "bnb_mi355x_lora_shrink_supported",
+       "bnb_mi355x_lora_shrink_ids", "bnb_mi355x_lora_shrink_ids_supported",
        "bnb_mi355x_gemm_4bit_grad_input", "bnb_mi355x_gemm_4bit_grad_input_workspace_bytes", "bnb_mi355x_gemm_4bit_grad_input_supported",
        "bnb_mi355x_peer_buffer_bytes", "bnb_mi355x_peer_alloc", "bnb_mi355x_peer_free", "bnb_mi355x_peer_export", "bnb_mi355x_peer_open",
        "bnb_mi355x_peer_close", "bnb_mi355x_peer_allgather", "bnb_mi355x_peer_status",

@@ -72,10 +72,19 @@ bool gemm_4bit_sm_lora_supported(int dtype, const void* A, const uint8_t* B, int
 bool gemm_4bit_sm_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
                        const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r,
                        int M, int N, int K, int blocksize, int quant_type, hipStream_t stream);
+bool gemv_4bit_stream_lora_ids(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                               const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, const float* scalings,
+                               const void* ids, int index_bytes, int A_n, int r, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream);
+bool gemm_4bit_sm_lora_ids(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                           const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, const float* scalings,
+                           const void* ids, int index_bytes, int A_n, int r, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream);
 extern thread_local TlsKnob g_mfma_knob0, g_mfma_knob1;
 // lora_shrink.hip
 bool lora_shrink_supported(int dtype, int M, int R, int K);
 bool lora_shrink(int dtype, const void* x, const void* lora_a, void* t, int M, int R, int K, const int* splits, int n_splits, hipStream_t stream);
+bool lora_shrink_ids_supported(int dtype, int M, int A_n, int R, int K);
+bool lora_shrink_ids(int dtype, const void* x, const void* lora_a, const void* ids, int index_bytes, void* t, int M, int A_n, int R, int K,
+                     const int* splits, int n_splits, hipStream_t stream);
 // gemm4_grad_input.hip
 bool gemm_4bit_grad_input_supported(int dtype, const void* G, const uint8_t* B, int M, int N, int K, int blocksize);
 size_t gemm_4bit_grad_input_workspace_bytes(int M, int N, int K);
@@ -531,6 +540,33 @@ int bnb_mi355x_gemm_4bit_lora_supported(int dtype, int M, int N, int K, int bloc
                : 0;
 }
 
+// (mixed-adapter form: lora_b [A_n, N, r], scalings [A_n] fp32 and one adapter id per row on the device; the uniform call's family)
+void bnb_mi355x_gemm_4bit_lora_ids(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit,
+                                   const float* absmax_code, const float* absmax_offset, void* out, const void* bias, const void* lora_t,
+                                   const void* lora_b, const float* scalings, const void* ids, int index_bytes, int A_n, int r, int M, int N, int K,
+                                   int blocksize, int quant_type, bnb_stream_t s) {
+    if (quant_type != kFP4 && quant_type != kNF4) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_lora_ids: quant_type must be 1 (FP4) or 2 (NF4), got %d\n", quant_type);
+        exit(1);
+    }
+    const int family = lora_family(dtype, A, B, absmax, absmax_8bit, lora_t, lora_b, M, N, K, blocksize, r);
+    const bool ok = family == kKernelSm ? gemm_4bit_sm_lora_ids(dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, lora_t, lora_b,
+                                                                scalings, ids, index_bytes, A_n, r, M, N, K, blocksize, quant_type, S(s))
+                    : family == kKernelStream ? gemv_4bit_stream_lora_ids(dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, lora_t,
+                                                                          lora_b, scalings, ids, index_bytes, A_n, r, M, N, K, blocksize, quant_type, S(s))
+                                              : false;
+    if (!ok) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_lora_ids: no kernel for dtype %d, M=%d, N=%d, K=%d, blocksize=%d, r=%d, A_n=%d, index_bytes=%d (ask bnb_mi355x_gemm_4bit_lora_ids_supported, align A / B / lora_t / lora_b to 16 bytes)\n",
+                dtype, M, N, K, blocksize, r, A_n, index_bytes);
+        exit(1);
+    }
+}
+int bnb_mi355x_gemm_4bit_lora_ids_supported(int dtype, int M, int N, int K, int blocksize, int nested, int r, int A_n) {
+    // (exactly where the uniform launch is served, for every stack of 1 ... 64 adapters: the streaming MFMA kernel rebases lora_b per
+    // adapter, so there is no bound on A_n N r)
+    return A_n >= 1 && A_n <= 64 ? bnb_mi355x_gemm_4bit_lora_supported(dtype, M, N, K, blocksize, nested, r) : 0;
+}
+
 // ------------------------------------------------------------------ LoRA shrink (t = x lora_A^T, the launch in front of gemm_4bit_lora)
 void bnb_mi355x_lora_shrink(int dtype, const void* x, const void* lora_a, void* t, int M, int R, int K, const int* splits, int n_splits, bnb_stream_t s) {
     if (!lora_shrink(dtype, x, lora_a, t, M, R, K, splits, n_splits, S(s))) {
@@ -540,6 +576,16 @@ void bnb_mi355x_lora_shrink(int dtype, const void* x, const void* lora_a, void* 
     }
 }
 int bnb_mi355x_lora_shrink_supported(int dtype, int M, int R, int K) { return lora_shrink_supported(dtype, M, R, K) ? 1 : 0; }
+// (mixed-adapter form: lora_a [A_n, R, K], one adapter id per row of x on the device)
+void bnb_mi355x_lora_shrink_ids(int dtype, const void* x, const void* lora_a, const void* ids, int index_bytes, void* t, int M, int A_n, int R, int K,
+                                const int* splits, int n_splits, bnb_stream_t s) {
+    if (!lora_shrink_ids(dtype, x, lora_a, ids, index_bytes, t, M, A_n, R, K, splits, n_splits, S(s))) {
+        fprintf(stderr, "bitsandbytes_amd: lora_shrink_ids: no kernel for dtype %d, M=%d, A_n=%d, R=%d, K=%d, index_bytes=%d, n_splits=%d (fp16 / bf16, 1 <= M <= 16, 1 <= A_n <= 64, K %% 64 == 0, R %% 8 == 0, 8 <= R <= 1024, ids int32 / int64, up to 8 splits of 8 ... 128 rows, each a multiple of 8, that sum to R; x / lora_a / t 16-byte aligned)\n",
+                dtype, M, A_n, R, K, index_bytes, n_splits);
+        exit(1);
+    }
+}
+int bnb_mi355x_lora_shrink_ids_supported(int dtype, int M, int A_n, int R, int K) { return lora_shrink_ids_supported(dtype, M, A_n, R, K) ? 1 : 0; }
 
 // ------------------------------------------------------------------ peer chain (the all-gather fused into the gemv launches)
 static uint32_t peer_chain_spin_bound() {

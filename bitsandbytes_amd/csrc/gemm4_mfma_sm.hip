@@ -106,6 +106,11 @@ struct SmArgs {
     const void* lora_b; // [N, r] of T: lora_B.weight as stored
     int lora_r;         // 8 <= r <= 128, r % 8 == 0
     float lora_scaling;
+    // mixed-adapter LoRA epilogue (IDS instances; at the END: no other instance's field moves)
+    const void* lora_ids;       // [M] adapter ids on the device, int32 / int64
+    const float* lora_scalings; // [A_n] fp32 on the device
+    int lora_an;                // adapters in the stack: lora_b is [A_n, N, r]
+    int lora_idx64;
 };
 
 // Time stamps (measurement build): s_memtime values collect in scalar registers and are stored ONCE, at the end of the kernel
@@ -162,7 +167,17 @@ __device__ __forceinline__ int sm_swz(int m) { return (m & 3) | ((m & 4) << 1); 
 // steps over k = 0, 32, ... < r in ascending order into ONE accumulator that starts at zero (k >= r and rows past M / past the
 // workgroup's rows are out-of-range loads: zeros), behind its last item and in front of the final barrier, and hands the tile to the
 // combine step through TT KiB of LDS behind the wavefronts' regions. Everything in front of that is the plain kernel's.
-template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false, bool GATED = false, bool LORA = false>
+// IDS (with LORA; bnb_mi355x_gemm_4bit_lora_ids): a mixed-adapter batch - lora_b is a stack [A_n, N, r], batch row m takes adapter
+// ids[m] and scalings[ids[m]], a row whose id is outside [0, A_n) has no adapter and gets the plain call's bits. The B operand differs
+// per batch row, so wavefront t loops over the DISTINCT in-range ids of the batch, wave-uniformly and in ascending id: for id a it
+// chains the same ceil(r / 32) MFMAs from a ZERO accumulator - t's lanes of rows with another id are out-of-range loads (zeros,
+// nothing fetched), B's rows come from adapter a through a resource rebased on lora_b + a N r 2 (64-bit arithmetic: the 31-bit
+// offsets stay those of one adapter) - and SELECTS into the tile it leaves in LDS the accumulator elements of the rows with
+// ids[m] = a. Two adapters never meet in one accumulator: 0 * Inf from someone else's adapter reaches no row. A row with an adapter
+// has the uniform instance's bits (a row of an MFMA does not depend on the other rows). A compile-time variant: the uniform
+// instances' code is untouched.
+template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false, bool GATED = false, bool LORA = false,
+          bool IDS = false>
 __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
     // hot arguments as separate scalars: preloaded into SGPRs by the command processor (14 dwords)
     const void* hot_A, const uint8_t* hot_B, const float* hot_absmax, const uint8_t* hot_absmax8, const float* hot_code2, int hot_M,
@@ -194,6 +209,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
     static_assert(TT >= 1 && TT <= kSmMaxTiles && (!SINGLE || TT == 1), "tiles per workgroup");
     static_assert(!GATED || (ROWS != 32 && !GROUPED && !NESTED && ORDER == 0), "gated instances: up to 16 rows, one matrix, fp32 absmax");
     static_assert(!LORA || (ROWS != 32 && !GROUPED && !GATED && ORDER == 0), "LoRA instances: up to 16 rows, one matrix");
+    static_assert(!IDS || LORA, "IDS is a variant of the LoRA instances");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -407,6 +423,15 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
         lo_s = __builtin_bit_cast(int, p.lora_scaling);
         asm volatile("" : "+s"(lo_t), "+s"(lo_b), "+s"(lo_r), "+s"(lo_s));
     }
+    [[maybe_unused]] uintptr_t lo_ids = 0, lo_sc = 0;
+    [[maybe_unused]] int lo_an = 0, lo_i64 = 0;
+    if constexpr (IDS) {
+        lo_ids = reinterpret_cast<uintptr_t>(p.lora_ids);
+        lo_sc = reinterpret_cast<uintptr_t>(p.lora_scalings);
+        lo_an = p.lora_an;
+        lo_i64 = p.lora_idx64;
+        asm volatile("" : "+s"(lo_ids), "+s"(lo_sc), "+s"(lo_an), "+s"(lo_i64));
+    }
     __syncthreads();
     BNB_SM_STAMP(5)
     if constexpr (!SINGLE) {
@@ -565,7 +590,66 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
             for (int rb = 0; rb < RB; ++rb)
                 *reinterpret_cast<f32x4*>(region + ((z * TT + t) * RB + rb) * 1024 + lane * 16) = acc[z][t][rb];
     constexpr int kLoraLds = kRegions + WAVES * REGION; // (LoRA) TT tiles of 1 KiB, in the accumulators' lane layout
-    if constexpr (LORA) {
+    // (IDS) behind the tiles: per batch row of the block, scalings[ids[m]] and whether the row has an adapter (16 floats + 16 ints)
+    constexpr int kLoraRowLds = kLoraLds + TT * 1024;
+    if constexpr (IDS) {
+        static_assert(TT <= WAVES, "one wavefront per tile");
+        if (wave < TT) {
+            // lanes 0 ... 15 hold the adapter of batch row m_base + lane: the whole 64-bit id compared with [0, A_n) before anything
+            // is addressed with it; 64 = no adapter (rows past M too)
+            typedef const long long __attribute__((address_space(1))) * gi64_ptr;
+            typedef const int __attribute__((address_space(1))) * gi32_ptr;
+            typedef const float __attribute__((address_space(1))) * gf32_ptr;
+            int ad = 64;
+            if (lane < 16 && m_base + lane < M) {
+                const long long id = lo_i64 ? ((gi64_ptr)lo_ids)[m_base + lane] : static_cast<long long>(((gi32_ptr)lo_ids)[m_base + lane]);
+                if (id >= 0 && id < static_cast<long long>(lo_an))
+                    ad = static_cast<int>(id);
+            }
+            if (wave == 0 && lane < 16) {
+                reinterpret_cast<float*>(smem + kLoraRowLds)[lane] = ad < 64 ? ((gf32_ptr)lo_sc)[ad] : 0.0f;
+                reinterpret_cast<int*>(smem + kLoraRowLds + 64)[lane] = ad < 64 ? 1 : 0;
+            }
+            // the adapters present in the batch, as a wave-uniform 64-bit set (A_n <= 64)
+            uint64_t present = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int v = __builtin_amdgcn_readlane(ad, i);
+                present |= v < 64 ? (1ull << v) : 0ull;
+            }
+            const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(lo_t), 0, 0x7FFFFFFF, 0x00020000);
+            const int lm = m_base + ln, lnrow = row0 + 16 * wave + ln;
+            f32x4 keep = {0.f, 0.f, 0.f, 0.f};
+            while (present != 0) {
+                const int a = __builtin_ctzll(present); // (ascending id)
+                present &= present - 1;
+                const uint32_t selm = static_cast<uint32_t>(__builtin_amdgcn_ballot_w64(lane < 16 && ad == a)); // bit m: row m_base + m has adapter a
+                const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(
+                    reinterpret_cast<void*>(lo_b + static_cast<uint64_t>(a) * static_cast<uint64_t>(N) * static_cast<uint64_t>(lo_r) * 2u), 0, 0x7FFFFFFF,
+                    0x00020000);
+                const uint32_t inv_m = ((selm >> ln) & 1u) ? 0u : kOob;
+                u32x4 ta[4], tb[4];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int k = 32 * s + 8 * lg;
+                    const uint32_t inv_k = k < lo_r ? 0u : kOob;
+                    ta[s] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_t, (static_cast<uint32_t>(lm * lo_r + k) * 2u) | inv_k | inv_m, 0, 0));
+                    tb[s] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                          rs_b, (static_cast<uint32_t>(lnrow * lo_r + k) * 2u) | inv_k | (lnrow < row_end ? 0u : kOob), 0, 0));
+                }
+                f32x4 lacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    if (32 * s < lo_r) // (wave-uniform)
+                        lacc = SmMma<T>::run(ta[s], tb[s], lacc);
+                // accumulator layout: lane (ln, lg) holds batch rows 4 lg ... 4 lg + 3 of weight column ln
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    keep[e] = ((selm >> (4 * lg + e)) & 1u) ? lacc[e] : keep[e];
+            }
+            *reinterpret_cast<f32x4*>(smem + kLoraLds + wave * 1024 + lane * 16) = keep;
+        }
+    } else if constexpr (LORA) {
         static_assert(TT <= WAVES, "one wavefront per tile");
         if (wave < TT) {
             // operand shape of v_mfma_f32_16x16x32: lane (ln, lg) holds 8 consecutive k of row ln - batch row ln of t, weight row ln of the
@@ -636,7 +720,13 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
             const T* bias = static_cast<const T*>(g_bias);
             const float b = bias ? static_cast<float>(bias[n]) : 0.0f;
             float vb = v + b;
-            if constexpr (LORA) {
+            if constexpr (IDS) {
+                // the uniform instance's arithmetic with scalings[ids[m]]; a row without an adapter SKIPS the term: the plain call's bits
+                if (reinterpret_cast<const int*>(smem + kLoraRowLds + 64)[mm16]) {
+                    const float lv = reinterpret_cast<const float*>(smem + kLoraLds + t * 1024)[src];
+                    vb = rounded_f32(rounded_f32(vb) + rounded_f32(reinterpret_cast<const float*>(smem + kLoraRowLds)[mm16] * lv));
+                }
+            } else if constexpr (LORA) {
                 // T((acc + bias) + scaling * lora): every intermediate an fp32 VALUE (opaque: no mixed-precision FMA folds the sum
                 // into the conversion), one rounding to T
                 const float lv = reinterpret_cast<const float*>(smem + kLoraLds + t * 1024)[src];
@@ -676,6 +766,7 @@ struct SmPlan {
     bool grouped = false;
     bool gated = false; // (gate, up) row pairs: R even
     bool lora = false;  // the LoRA epilogue's instances
+    bool lora_ids = false; // (with lora) their mixed-adapter variant
 };
 
 // rows per workgroup: one workgroup per CU when 64 rows are enough, else whole rounds of workgroups
@@ -698,14 +789,15 @@ SmPlan sm_plan(int M, int N, bool gated = false) {
     return pl;
 }
 
-template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false, bool GATED = false, bool LORA = false>
+template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false, bool GATED = false, bool LORA = false,
+          bool IDS = false>
 void sm_launch_one(const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* code2, int M, int N, int K, int geom,
                    const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
     constexpr int V = (ROWS < 16 && WAVES == 8) ? 2 : 1; // (accumulator sets per tile: the kernel's V)
     constexpr int RB = ROWS == 32 ? 2 : 1, SROWS = ROWS == 32 ? 16 : ROWS;
     constexpr size_t region = (SROWS * 512 + kSmScratch) > V * TT * RB * 1024 ? (SROWS * 512 + kSmScratch) : V * TT * RB * 1024;
-    constexpr size_t lds = kSmLut + kSmCode2 + static_cast<size_t>(WAVES) * region + (LORA ? TT * 1024 : 0); // (+ the adapter's tiles)
-    auto kern = gemm4_mfma_sm_kernel<T, ROWS, WAVES, TT, NESTED, SINGLE, ORDER, GROUPED, GATED, LORA>;
+    constexpr size_t lds = kSmLut + kSmCode2 + static_cast<size_t>(WAVES) * region + (LORA ? TT * 1024 : 0) + (IDS ? 128 : 0); // (+ the adapter's tiles, + the rows' scalings)
+    auto kern = gemm4_mfma_sm_kernel<T, ROWS, WAVES, TT, NESTED, SINGLE, ORDER, GROUPED, GATED, LORA, IDS>;
     static LdsLimit lim;
     ensure_dynamic_lds(lim, reinterpret_cast<const void*>(kern), lds);
     hipLaunchKernelGGL(kern, dim3(pl.grid_x, (M + 16 * RB - 1) / (16 * RB)), dim3(WAVES * 64), lds, stream, A, B, absmax, absmax8, code2, M, N, K, geom, a);
@@ -722,6 +814,20 @@ void sm_launch_kind(const void* A, const uint8_t* B, const float* absmax, const 
                     return sm_launch_one<T, ROWS, WAVES, 1, false, true, 0, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
             }
             return sm_launch_one<T, ROWS, WAVES, TT, false, false, 0, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+        }
+    }
+    if constexpr (ROWS != 32) {
+        if (pl.lora && pl.lora_ids) { // (the LoRA instances' skeletons, mixed-adapter epilogue)
+            if constexpr (TT == 1) {
+                if ((K + kSmChunk - 1) / kSmChunk <= WAVES) {
+                    if (nested)
+                        return sm_launch_one<T, ROWS, WAVES, 1, true, true, 0, false, false, true, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+                    return sm_launch_one<T, ROWS, WAVES, 1, false, true, 0, false, false, true, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+                }
+            }
+            if (nested)
+                return sm_launch_one<T, ROWS, WAVES, TT, true, false, 0, false, false, true, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+            return sm_launch_one<T, ROWS, WAVES, TT, false, false, 0, false, false, true, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
         }
     }
     if constexpr (ROWS != 32) {
@@ -880,6 +986,47 @@ bool gemm_4bit_sm_lora(int dtype, const void* A, const uint8_t* B, const float* 
     a.lora_b = lora_b;
     a.lora_r = r;
     a.lora_scaling = scaling;
+    const int geom = pl.R | ((quant_type == kFP4) ? (1 << 16) : 0) | (ilog2(blocksize) << 20);
+    if (dtype == 2)
+        sm_launch_rows<bf16>(A, B, absmax, absmax8, absmax_code, M, N, K, geom, pl, a, stream);
+    else
+        sm_launch_rows<f16>(A, B, absmax, absmax8, absmax_code, M, N, K, geom, pl, a, stream);
+    BNB_CHECK_LAUNCH();
+    g_last_gemm_kernel = kKernelSm;
+    return true;
+}
+
+// Mixed-adapter LoRA form (see the kernel's IDS): the LoRA form's plan and instance skeleton; lora_b [A_n, N, r], scalings [A_n] fp32
+// and ids [M] (int32 / int64) on the device. The kernel rebases lora_b's buffer resource per adapter with 64-bit arithmetic, so the
+// preconditions carry no bound on A_n N r. false - nothing launched - outside the preconditions.
+bool gemm_4bit_sm_lora_ids(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                           const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, const float* scalings,
+                           const void* ids, int index_bytes, int A_n, int r, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
+    if (!gemm_4bit_sm_lora_supported(dtype, A, B, M, N, K, blocksize, r) || !gemm_4bit_sm_serves(absmax, absmax8, blocksize) || !aligned_to(lora_t, 16) ||
+        !aligned_to(lora_b, 16) || (absmax8 != nullptr && (absmax_code == nullptr || absmax_offset == nullptr)) || A_n < 1 || A_n > 64 ||
+        (index_bytes != 4 && index_bytes != 8) || ids == nullptr || scalings == nullptr || !aligned_to(ids, static_cast<size_t>(index_bytes)) ||
+        !aligned_to(scalings, 4))
+        return false;
+    SmPlan pl = sm_plan(M, N);
+    if (pl.rows > 16 || pl.tt > kSmMaxTiles)
+        return false;
+    pl.lora = true;
+    pl.lora_ids = true;
+    SmArgs a{};
+#ifdef BNB_PROFILING
+    a.dbg = nullptr;
+#endif
+    a.absmax_offset = absmax_offset;
+    a.out = out;
+    a.bias = bias;
+    a.lora_t = lora_t;
+    a.lora_b = lora_b;
+    a.lora_r = r;
+    a.lora_scaling = 0.0f;
+    a.lora_ids = ids;
+    a.lora_scalings = scalings;
+    a.lora_an = A_n;
+    a.lora_idx64 = index_bytes == 8 ? 1 : 0;
     const int geom = pl.R | ((quant_type == kFP4) ? (1 << 16) : 0) | (ilog2(blocksize) << 20);
     if (dtype == 2)
         sm_launch_rows<bf16>(A, B, absmax, absmax8, absmax_code, M, N, K, geom, pl, a, stream);

@@ -64,7 +64,8 @@ enum StreamFlags : int {
     kExact = 128,  // exact geometry (M = 1, K = 4096: SW = 2, G = 8, every row, lane and ring position valid): see launch_one
     kLateArgs = 256, // sweep-only: the epilogue's out / bias pointers loaded where they are used (the form up to round 6; A/B runs)
     kGated = 512,    // rows are (gate, up) pairs of ONE interleaved [2F, K] matrix: out[m, i] = silu(row 2 i) * (row 2 i + 1), [M, F]
-    kLora = 1024     // LoRA adapter term as the epilogue: out[m, n] = T((acc + bias[n]) + scaling * sum_j t[m, j] * B_l[n, j]) - see lora_dot
+    kLora = 1024,    // LoRA adapter term as the epilogue: out[m, n] = T((acc + bias[n]) + scaling * sum_j t[m, j] * B_l[n, j]) - see lora_dot
+    kLoraIds = 2048  // (with kLora) mixed-adapter batch: row m takes B_l and scaling from adapter ids[m] of a stack; a row without one is plain
 };
 
 // One weight matrix of a launch.
@@ -165,6 +166,11 @@ struct StreamArgs {
     const void* lora_b = nullptr; // [N, r] of T: lora_B.weight as stored
     int lora_r = 0;               // 8 <= r <= 128, r % 8 == 0: every row of both starts 16-byte aligned
     float lora_scaling = 0.0f;
+    // mixed-adapter LoRA epilogue (kLoraIds instances; at the END: no other instance's field moves)
+    const void* lora_ids = nullptr;        // [M] adapter ids on the device, int32 / int64
+    const float* lora_scalings = nullptr;  // [A_n] fp32 on the device
+    int lora_an = 0;                       // adapters in the stack: lora_b is [A_n, N, r]
+    int lora_idx64 = 0;
 };
 
 template <bool FP4> __device__ __forceinline__ float code_literal(int i) {
@@ -232,6 +238,9 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     constexpr bool LORA = (FLAGS & kLora) != 0;
     static_assert(!LORA || (!PEER && !GROUPED && !GATED && !CODEPTR && !(FLAGS & kLateArgs) && TypeInfo<T>::bytes == 2),
                   "the LoRA form: one matrix, literal table, 16-bit activations");
+    // mixed-adapter form (bnb_mi355x_gemm_4bit_lora_ids): a compile-time variant of the LoRA epilogue - the uniform instances' code is untouched
+    constexpr bool LORA_IDS = (FLAGS & kLoraIds) != 0;
+    static_assert(!LORA_IDS || LORA, "kLoraIds is a variant of the LoRA form");
     // Exact geometry: the host selects this instance only when K = kExactSW * 2048, M = 1 and the rows divide evenly over workgroups
     // and row groups with at least one ring position each (exact_geometry()). Everything the general instance decides at run time in
     // front of its first weight request - bounds of the row list, of the row, of the segment, the division of the wavefront id - is a
@@ -577,6 +586,8 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     // (LoRA) the adapter's kernarg fields: requested and pinned with the epilogue's pointers
     [[maybe_unused]] uintptr_t lo_t = 0, lo_b = 0;
     [[maybe_unused]] int lo_r = 0, lo_s = 0;
+    [[maybe_unused]] uintptr_t lo_ids = 0, lo_sc = 0;
+    [[maybe_unused]] int lo_an = 0, lo_i64 = 0;
     uint32_t epoch = 0;     // (peer chain) the exchange this launch consumes
     uint32_t epoch_raw = 0; // ... the epoch word as loaded
     for (int ph = 0; ph < P; ++ph) {
@@ -641,6 +652,12 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
                     lo_b = reinterpret_cast<uintptr_t>(p.lora_b);
                     lo_r = p.lora_r;
                     lo_s = __builtin_bit_cast(int, p.lora_scaling);
+                    if constexpr (LORA_IDS) {
+                        lo_ids = reinterpret_cast<uintptr_t>(p.lora_ids);
+                        lo_sc = reinterpret_cast<uintptr_t>(p.lora_scalings);
+                        lo_an = p.lora_an;
+                        lo_i64 = p.lora_idx64;
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -748,6 +765,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
             if constexpr (LORA) {
                 if (ph == 0)
                     asm volatile("" : "+s"(lo_t), "+s"(lo_b), "+s"(lo_r), "+s"(lo_s));
+                if constexpr (LORA_IDS) {
+                    if (ph == 0)
+                        asm volatile("" : "+s"(lo_ids), "+s"(lo_sc), "+s"(lo_an), "+s"(lo_i64));
+                }
             }
         }
         __syncthreads();
@@ -803,9 +824,20 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     // (c0 + c1) + (c2 + c3). It does not depend on the segment partials: the thread of output idx = tid - the only output of a thread
     // wherever a workgroup holds at most THREADS / MB rows - computes it HERE, in front of the final barrier, while the wavefronts
     // that started later still decode; behind the barrier the epilogue only adds it. (Further trips of the epilogue loop: on the spot.)
-    auto lora_dot = [&](int mrow, int nrow) -> float {
+    // (kLoraIds) `adapter`: the row's adapter in the stack [A_n, N, r] - the same pieces, chains and order, B_l's row read from that
+    // adapter's matrix. lora_adapter(m): the id of batch row m, compared as a 64-bit value with [0, A_n) BEFORE any address is formed
+    // from it; -1: the row has no adapter - its t row and the scalings are never read, its output is the plain call's.
+    [[maybe_unused]] auto lora_adapter = [&](int mrow) -> int {
+        typedef const long long __attribute__((address_space(1))) * gi64_ptr;
+        typedef const int __attribute__((address_space(1))) * gi32_ptr;
+        const long long id = lo_i64 ? ((gi64_ptr)lo_ids)[mrow] : static_cast<long long>(((gi32_ptr)lo_ids)[mrow]);
+        return (id >= 0 && id < static_cast<long long>(lo_an)) ? static_cast<int>(id) : -1;
+    };
+    auto lora_dot = [&](int mrow, int nrow, [[maybe_unused]] int adapter = 0) -> float {
         const unsigned char* const tp = reinterpret_cast<const unsigned char*>(lo_t) + static_cast<long>(mrow) * lo_r * 2;
-        const unsigned char* const bp = reinterpret_cast<const unsigned char*>(lo_b) + static_cast<long>(nrow) * lo_r * 2;
+        const unsigned char* bp = reinterpret_cast<const unsigned char*>(lo_b) + static_cast<long>(nrow) * lo_r * 2;
+        if constexpr (LORA_IDS)
+            bp += static_cast<long>(adapter) * hot_N * lo_r * 2;
         float c[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         for (int j = 0; j < lo_r; j += 8) {
             float tf[8], bf[8];
@@ -821,11 +853,18 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
         return (c[0] + c[1]) + (c[2] + c[3]);
     };
     [[maybe_unused]] float lora_kept = 0.0f;
+    [[maybe_unused]] int lora_kept_id = -1;
     if constexpr (LORA) {
         if (tid < nrows * MB) {
             const int m = (MB == 1) ? 0 : tid / nrows, rl = tid - m * nrows;
-            if (m0 + m < M)
-                lora_kept = lora_dot(m0 + m, row_begin + rl);
+            if (m0 + m < M) {
+                if constexpr (LORA_IDS) {
+                    lora_kept_id = lora_adapter(m0 + m);
+                    if (lora_kept_id >= 0)
+                        lora_kept = lora_dot(m0 + m, row_begin + rl, lora_kept_id);
+                } else
+                    lora_kept = lora_dot(m0 + m, row_begin + rl);
+            }
         }
     }
     __syncthreads();
@@ -875,7 +914,16 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
         const int out_n = GROUPED ? p.mat[mi].N : hot_N; // (one matrix: its N is the preloaded row count)
         const float b = bias ? static_cast<float>(bias[row]) : 0.0f;
         float vb = v + b;
-        if constexpr (LORA) {
+        if constexpr (LORA_IDS) {
+            // the uniform form's arithmetic with the row's own adapter and scalings[id]; a row without an adapter SKIPS the term (not
+            // 0 * 0: the plain call's bits, whatever the stack and lora_t hold)
+            const int ad = (idx == tid) ? lora_kept_id : lora_adapter(m0 + m);
+            if (ad >= 0) {
+                typedef const float __attribute__((address_space(1))) * gf32_ptr;
+                const float lv = (idx == tid) ? lora_kept : lora_dot(m0 + m, row, ad);
+                vb = rounded_f32(rounded_f32(vb) + rounded_f32(((gf32_ptr)lo_sc)[ad] * lv));
+            }
+        } else if constexpr (LORA) {
             // T((acc + bias) + scaling * lora): every intermediate an fp32 VALUE (opaque: no mixed-precision FMA folds the sum into
             // the conversion), one rounding to T
             const float lv = (idx == tid) ? lora_kept : lora_dot(m0 + m, row);
@@ -1100,7 +1148,7 @@ bool exact_geometry(const Geometry& ge, int M, int rows_total, int K, int ns) {
 // (Nested statistics: the exact form was built and measured BEHIND the general one at 4096^2 - FP4 bs 128 nested 4.50 against
 // 4.36 us - and is not instantiated: DESIGN 6b.)
 template <typename T, int MB, int WAVES, int NS, int FLAGS> constexpr bool has_exact_twin() {
-    return TypeInfo<T>::bytes == 2 && MB == 1 && WAVES == 16 && NS == kRing && (FLAGS & ~(kFp4 | kGated | kLora)) == kNT;
+    return TypeInfo<T>::bytes == 2 && MB == 1 && WAVES == 16 && NS == kRing && (FLAGS & ~(kFp4 | kGated | kLora | kLoraIds)) == kNT;
 }
 // stream tuning knob `nt`, values above 1 (A/B of the fixed-cost levers, tools/stream_fixed_cost_ab.py): 2 = the general instance where
 // the exact one would be selected, 3 = the general instance with the epilogue's pointers loaded late (bf16, NF4 fp32-absmax and
@@ -1598,6 +1646,55 @@ bool gemv_4bit_stream_lora(int dtype, const void* A, const uint8_t* B, const flo
         launch_lora_flags<bf16>(a, quant_type, stream);
     else
         launch_lora_flags<f16>(a, quant_type, stream);
+    BNB_CHECK_LAUNCH();
+    g_last_gemm_kernel = kKernelStream;
+    return true;
+}
+
+// Mixed-adapter LoRA form (bnb_mi355x_gemm_4bit_lora_ids): the LoRA form's instance skeleton with kLoraIds - lora_b [A_n, N, r],
+// scalings [A_n] fp32 and ids [M] (int32 / int64) on the device. false - nothing launched - outside the preconditions.
+template <typename T> static void launch_lora_ids_flags(const StreamArgs& a, int quant_type, hipStream_t stream) {
+    const int sel = (a.mat[0].absmax8 != nullptr ? 1 : 0) | (quant_type == kFP4 ? 2 : 0);
+    switch (sel) {
+    case 0: return launch_lora<T, kNT | kLora | kLoraIds>(a, stream);
+    case 1: return launch_lora<T, kNT | kLora | kLoraIds | kNested>(a, stream);
+    case 2: return launch_lora<T, kNT | kLora | kLoraIds | kFp4>(a, stream);
+    default: return launch_lora<T, kNT | kLora | kLoraIds | kFp4 | kNested>(a, stream);
+    }
+}
+bool gemv_4bit_stream_lora_ids(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                               const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, const float* scalings,
+                               const void* ids, int index_bytes, int A_n, int r, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
+    if (!gemv_4bit_stream_lora_supported(dtype, M, N, K, blocksize, r) || !stream_ok(A, M, K, blocksize) || !aligned_to(B, 16) || !aligned_to(absmax, 4) ||
+        !aligned_to(lora_t, 16) || !aligned_to(lora_b, 16) || (absmax8 != nullptr && (absmax_code == nullptr || absmax_offset == nullptr)) || A_n < 1 ||
+        A_n > 64 || (index_bytes != 4 && index_bytes != 8) || ids == nullptr || scalings == nullptr || !aligned_to(ids, static_cast<size_t>(index_bytes)) ||
+        !aligned_to(scalings, 4))
+        return false;
+    StreamArgs a;
+#ifdef BNB_PROFILING
+    a.dbg = nullptr;
+#endif
+    a.A = A;
+    a.code16 = nullptr;
+    a.M = M;
+    a.K = K;
+    a.bs_shift = ilog2(blocksize);
+    a.rows_total = N;
+    a.nmat = 1;
+    for (int i = 0; i < kMaxGroup; ++i)
+        a.mat[i] = StreamMat{B, absmax, absmax8, absmax_code, absmax_offset, out, bias, N, i == 0 ? 0 : 0x7FFFFFFF};
+    a.lora_t = lora_t;
+    a.lora_b = lora_b;
+    a.lora_r = r;
+    a.lora_scaling = 0.0f;
+    a.lora_ids = ids;
+    a.lora_scalings = scalings;
+    a.lora_an = A_n;
+    a.lora_idx64 = index_bytes == 8 ? 1 : 0;
+    if (dtype == 2)
+        launch_lora_ids_flags<bf16>(a, quant_type, stream);
+    else
+        launch_lora_ids_flags<f16>(a, quant_type, stream);
     BNB_CHECK_LAUNCH();
     g_last_gemm_kernel = kKernelStream;
     return true;

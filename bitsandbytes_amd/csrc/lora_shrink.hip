@@ -19,6 +19,10 @@
 // sixteen tiles meet in LDS and one thread per output adds them in ascending w, ((p0 + p1) + p2) + ... + p15 (wavefronts without a
 // step contribute their zero), and rounds once. Every column of an MFMA is computed independently of the others, so t[m, j] does not
 // depend on R, on where row j sits in A, on the splits, or on the grid; it does not depend on M either (one family for M = 1 ... 16).
+//
+// Mixed-adapter form (lora_shrink_ids_kernel): A is a stack [A_n, R, K], every row of x names its adapter by an id
+// on the device, the grid gets a second dimension (adapter), and the tile body below runs with the rows of other adapters masked
+// out of the x operand - same steps, same order, so a row has the bits of the uniform kernel's call with its adapter.
 #include "bnb_common.h"
 
 namespace bnb {
@@ -46,6 +50,7 @@ constexpr int kShrinkTile = 8;      // adapter rows per workgroup
 constexpr int kShrinkBatch = 8;     // steps of a wavefront whose loads are issued together (16 x 16 bytes in flight per lane)
 constexpr int kShrinkMaxSplits = 8; // the grouped call's member cap
 constexpr int kShrinkMaxRows = 16, kShrinkMaxRank = 1024, kShrinkMaxPart = 128;
+constexpr int kShrinkMaxAdapters = 64; // the mixed-adapter form: adapters in a stack (the grid's second dimension)
 constexpr int kShrinkShortK = 4096, kShrinkLongK = 14336; // the K buckets of the predicate (measured at their upper ends)
 
 // the split table, by value in the kernarg segment: r[i] rows in part i, zero behind the last part (no splits: r[0] = R)
@@ -53,17 +58,27 @@ struct ShrinkSplits {
     int r[kShrinkMaxSplits];
 };
 
-template <typename T>
-__global__ __launch_bounds__(kShrinkWaves * 64) void lora_shrink_kernel(const T* __restrict__ x, const T* __restrict__ A, T* __restrict__ t, int M,
-                                                                        int K, const ShrinkSplits sp) {
+// One workgroup's tile: adapter rows j0 ... j0 + 7 of A against the rows of x. IDS (lora_shrink_ids_kernel): `sel` has bit m set for
+// the rows of x that carry this workgroup's adapter, `none` for the rows that this workgroup writes as zeros. The operand lanes of a
+// row outside `sel` hold the literal zero and never load; the MFMAs run as before, and a row of an MFMA does not depend on the other
+// rows, so a selected row's sum is the uniform kernel's, bit for bit. Only rows in `sel` or `none` are stored.
+template <typename T, bool IDS>
+__device__ __forceinline__ void shrink_tile(const T* __restrict__ x, const T* __restrict__ A, T* __restrict__ t, int M, int K, const ShrinkSplits& sp,
+                                            [[maybe_unused]] uint32_t sel, [[maybe_unused]] uint32_t none) {
     __shared__ __attribute__((aligned(16))) float part[kShrinkWaves][kShrinkTile][16]; // [wavefront][column j][row m]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ln = lane & 15, lg = lane >> 4; // MFMA roles: row of x / adapter row ln, k group lg
     const int j0 = blockIdx.x * kShrinkTile;
-    const int steps = K >> 5;
-    const bool x_lane = ln < M, a_lane = ln < kShrinkTile;
+    int steps = K >> 5;
+    bool x_lane = ln < M;
+    if constexpr (IDS) {
+        x_lane = ((sel >> ln) & 1u) != 0; // (sel has no bit at or above M)
+        if (sel == 0)
+            steps = 0; // only rows without an adapter to write: no load at all
+    }
+    const bool a_lane = ln < kShrinkTile;
     // 16-byte pieces: step s of a row is pieces 4 s ... 4 s + 3, this lane's is 4 s + lg (idle lanes point at row 0 and never load)
     const u32x4* xp = reinterpret_cast<const u32x4*>(x + static_cast<size_t>(x_lane ? ln : 0) * K) + lg;
     const u32x4* ap = reinterpret_cast<const u32x4*>(A + static_cast<size_t>(j0 + (a_lane ? ln : 0)) * K) + lg;
@@ -89,10 +104,18 @@ __global__ __launch_bounds__(kShrinkWaves * 64) void lora_shrink_kernel(const T*
     __syncthreads();
     if (tid < M * kShrinkTile) {
         const int m = tid >> 3, j = tid & 7;
+        if constexpr (IDS) {
+            if ((((sel | none) >> m) & 1u) == 0)
+                return; // another adapter's row: its workgroups write it
+        }
         float sum = part[0][j][m];
 #pragma unroll
         for (int w = 1; w < kShrinkWaves; ++w)
             sum += part[w][j][m];
+        if constexpr (IDS) {
+            if (((sel >> m) & 1u) == 0)
+                sum = 0.f; // a row without an adapter
+        }
         // the part that holds this tile: rows [base, base + rr) of A, stored as a contiguous [M, rr] matrix at element M * base
         int base = 0, rr = sp.r[0], pre = 0;
 #pragma unroll
@@ -106,6 +129,37 @@ __global__ __launch_bounds__(kShrinkWaves * 64) void lora_shrink_kernel(const T*
         }
         t[static_cast<size_t>(M) * base + static_cast<size_t>(m) * rr + (j0 + j - base)] = from_f32<T>(sum);
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kShrinkWaves * 64) void lora_shrink_kernel(const T* __restrict__ x, const T* __restrict__ A, T* __restrict__ t, int M,
+                                                                        int K, const ShrinkSplits sp) {
+    shrink_tile<T, false>(x, A, t, M, K, sp, 0u, 0u);
+}
+
+// Mixed-adapter form (bnb_mi355x_lora_shrink_ids): A is [A_n, R, K], ids holds one adapter id per row of x on the DEVICE, and
+//     t[m, :] = the uniform kernel's row m for adapter ids[m]        0 <= ids[m] < A_n
+//     t[m, :] = 0                                                    otherwise (the row has no adapter)
+// Grid (tile of 8 adapter rows, adapter). Every wavefront reads the <= 16 ids itself - one load, two ballots, the result wave-uniform:
+// no LDS list, no barrier - and a workgroup whose adapter no row names returns before it requests a byte of A or x. Rows without an
+// adapter are written as zeros by the workgroups of adapter 0, so every element of t is written exactly once and a captured graph
+// needs no memset node. An id is only ever COMPARED (as a 64-bit value: 2^32 + 1 is out of range, not adapter 1); every address is
+// formed from blockIdx.y < A_n.
+template <typename T>
+__global__ __launch_bounds__(kShrinkWaves * 64) void lora_shrink_ids_kernel(const T* __restrict__ x, const T* __restrict__ A, T* __restrict__ t,
+                                                                            const void* __restrict__ ids, int idx64, int M, int R, int K, int A_n,
+                                                                            const ShrinkSplits sp) {
+    const int lane = threadIdx.x & 63;
+    const int a = blockIdx.y;
+    long long id = -1;
+    if (lane < M)
+        id = idx64 ? static_cast<const long long*>(ids)[lane] : static_cast<long long>(static_cast<const int*>(ids)[lane]);
+    const bool in_range = id >= 0 && id < static_cast<long long>(A_n);
+    const uint32_t sel = static_cast<uint32_t>(__builtin_amdgcn_ballot_w64(lane < M && id == static_cast<long long>(a)));
+    const uint32_t none = a == 0 ? static_cast<uint32_t>(__builtin_amdgcn_ballot_w64(lane < M && !in_range)) : 0u;
+    if ((sel | none) == 0)
+        return; // (uniform over the workgroup: every wavefront computed the same masks)
+    shrink_tile<T, true>(x, A + static_cast<size_t>(a) * R * K, t, M, K, sp, sel, none);
 }
 
 bool shrink_shape_ok(int dtype, int M, int R, int K) {
@@ -128,26 +182,32 @@ bool lora_shrink_supported(int dtype, int M, int R, int K) {
     return K <= kShrinkLongK && M >= 2 && M <= 4;
 }
 
+// the split table of a call (false: not a table the kernel takes)
+static bool shrink_split_table(int R, const int* splits, int n_splits, ShrinkSplits& sp) {
+    if (n_splits < 0 || n_splits > kShrinkMaxSplits || (n_splits > 0 && splits == nullptr))
+        return false;
+    sp = {};
+    if (n_splits == 0) {
+        sp.r[0] = R;
+        return true;
+    }
+    int total = 0;
+    for (int i = 0; i < n_splits; ++i) {
+        if (splits[i] < 8 || splits[i] > kShrinkMaxPart || (splits[i] % 8) != 0)
+            return false;
+        sp.r[i] = splits[i];
+        total += splits[i];
+    }
+    return total == R;
+}
+
 // One launch; false (nothing launched) outside the preconditions. The predicate above is NOT consulted: an excluded class still
 // computes the documented result, it is only not worth a launch of its own.
 bool lora_shrink(int dtype, const void* x, const void* lora_a, void* t, int M, int R, int K, const int* splits, int n_splits, hipStream_t stream) {
+    ShrinkSplits sp;
     if (!shrink_shape_ok(dtype, M, R, K) || x == nullptr || lora_a == nullptr || t == nullptr || !aligned_to(x, 16) || !aligned_to(lora_a, 16) ||
-        !aligned_to(t, 16) || n_splits < 0 || n_splits > kShrinkMaxSplits || (n_splits > 0 && splits == nullptr))
+        !aligned_to(t, 16) || !shrink_split_table(R, splits, n_splits, sp))
         return false;
-    ShrinkSplits sp = {};
-    if (n_splits == 0) {
-        sp.r[0] = R;
-    } else {
-        int total = 0;
-        for (int i = 0; i < n_splits; ++i) {
-            if (splits[i] < 8 || splits[i] > kShrinkMaxPart || (splits[i] % 8) != 0)
-                return false;
-            sp.r[i] = splits[i];
-            total += splits[i];
-        }
-        if (total != R)
-            return false;
-    }
     const dim3 grid(R / kShrinkTile), block(kShrinkWaves * 64);
     if (dtype == 1)
         hipLaunchKernelGGL(lora_shrink_kernel<f16>, grid, block, 0, stream, static_cast<const f16*>(x), static_cast<const f16*>(lora_a), static_cast<f16*>(t), M,
@@ -155,6 +215,32 @@ bool lora_shrink(int dtype, const void* x, const void* lora_a, void* t, int M, i
     else
         hipLaunchKernelGGL(lora_shrink_kernel<bf16>, grid, block, 0, stream, static_cast<const bf16*>(x), static_cast<const bf16*>(lora_a),
                            static_cast<bf16*>(t), M, K, sp);
+    BNB_CHECK_LAUNCH();
+    return true;
+}
+
+// Whether bnb_mi355x_lora_shrink_ids serves the shape: the preconditions, minus the classes that the measurements exclude
+// (profiles/lora_multi_bench.txt). Pure host logic.
+bool lora_shrink_ids_supported(int dtype, int M, int A_n, int R, int K) {
+    return shrink_shape_ok(dtype, M, R, K) && A_n >= 1 && A_n <= kShrinkMaxAdapters;
+}
+
+// The mixed-adapter launch: lora_a [A_n, R, K], ids [M] on the device (int32 / int64: index_bytes 4 / 8). false (nothing launched)
+// outside the preconditions; the predicate above is not consulted.
+bool lora_shrink_ids(int dtype, const void* x, const void* lora_a, const void* ids, int index_bytes, void* t, int M, int A_n, int R, int K,
+                     const int* splits, int n_splits, hipStream_t stream) {
+    ShrinkSplits sp;
+    if (!shrink_shape_ok(dtype, M, R, K) || A_n < 1 || A_n > kShrinkMaxAdapters || (index_bytes != 4 && index_bytes != 8) || x == nullptr ||
+        lora_a == nullptr || ids == nullptr || t == nullptr || !aligned_to(x, 16) || !aligned_to(lora_a, 16) || !aligned_to(t, 16) ||
+        !aligned_to(ids, static_cast<size_t>(index_bytes)) || !shrink_split_table(R, splits, n_splits, sp))
+        return false;
+    const dim3 grid(R / kShrinkTile, A_n), block(kShrinkWaves * 64);
+    if (dtype == 1)
+        hipLaunchKernelGGL(lora_shrink_ids_kernel<f16>, grid, block, 0, stream, static_cast<const f16*>(x), static_cast<const f16*>(lora_a),
+                           static_cast<f16*>(t), ids, index_bytes == 8 ? 1 : 0, M, R, K, A_n, sp);
+    else
+        hipLaunchKernelGGL(lora_shrink_ids_kernel<bf16>, grid, block, 0, stream, static_cast<const bf16*>(x), static_cast<const bf16*>(lora_a),
+                           static_cast<bf16*>(t), ids, index_bytes == 8 ? 1 : 0, M, R, K, A_n, sp);
     BNB_CHECK_LAUNCH();
     return true;
 }

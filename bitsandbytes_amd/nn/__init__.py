@@ -5,6 +5,7 @@ from .modules import (
     EmbeddingNF4,
     FFN4bit,
     Linear4bitLoRA,
+    Linear4bitMultiLoRA,
     Linear4bit,
     LinearFP4,
     LinearNF4,
@@ -13,4 +14,4 @@ from .modules import (
 )
 
 __all__ = ["Linear4bit", "LinearFP4", "LinearNF4", "Params4bit", "Embedding4bit", "EmbeddingFP4", "EmbeddingNF4",
-           "parametrize", "linear4bit_group_forward", "FFN4bit", "Linear4bitLoRA"]
+           "parametrize", "linear4bit_group_forward", "FFN4bit", "Linear4bitLoRA", "Linear4bitMultiLoRA"]

@@ -552,6 +552,106 @@ class Linear4bitLoRA(nn.Module):
         return matmul_4bit_lora(xc, base.weight, base.weight.quant_state, t, self.lora_B, self.scaling, bias=bias).to(inp_dtype)
 
 
+class Linear4bitMultiLoRA(nn.Module):
+    """A :class:`Linear4bit` base layer with a STACK of LoRA adapters beside it for mixed-adapter decode batches: row ``m`` of ``x`` (a
+    request) computes ``base(x[m]) + scalings[id] * lora_B[id](lora_A[id](x[m]))`` with ``id = adapter_ids[m]``; a row whose id is
+    outside ``[0, A_n)`` has no adapter and gets ``base(x[m])``. TWO launches for a decode step, whatever the ids
+    (:func:`bitsandbytes_amd.lora_shrink_ids`, :func:`bitsandbytes_amd.matmul_4bit_lora_ids`; their gather compositions where the fused
+    launches do not serve the call). The ids stay on the device: ``forward`` captures in a graph and a replay follows ids written
+    into the same buffer. Inference only; no dropout, no DoRA.
+
+    ``lora_A``: ``[A_n, r, K]``, ``lora_B``: ``[A_n, N, r]``, ``scalings``: ``[A_n]`` - one rank for the stack, ``1 <= A_n <= 64``;
+    :meth:`from_adapters` stacks adapters of different ranks. The base layer is held by reference, the stacks are cast ONCE to the
+    compute dtype (``scalings`` to float32), and the module is not part of any state dict."""
+
+    def __init__(self, base: "Linear4bit", lora_A: torch.Tensor, lora_B: torch.Tensor, scalings: torch.Tensor):
+        super().__init__()
+        if lora_A.dim() != 3 or lora_B.dim() != 3 or lora_A.shape[0] != lora_B.shape[0] or lora_A.shape[1] != lora_B.shape[2] \
+                or tuple(scalings.shape) != (lora_A.shape[0],) or not 1 <= lora_A.shape[0] <= 64:
+            raise ValueError(f"Linear4bitMultiLoRA: lora_A must be [A_n, r, K], lora_B [A_n, N, r] and scalings [A_n] with 1 <= A_n <= 64, "
+                             f"got {tuple(lora_A.shape)}, {tuple(lora_B.shape)} and {tuple(scalings.shape)}")
+        object.__setattr__(self, "base", base)  # (referenced, not registered: state_dict() of this module is empty)
+        self.register_buffer("lora_A", lora_A, persistent=False)
+        self.register_buffer("lora_B", lora_B, persistent=False)
+        self.register_buffer("scalings", scalings, persistent=False)
+
+    @classmethod
+    def from_stacks(cls, base: "Linear4bit", lora_A: torch.Tensor, lora_B: torch.Tensor, scalings) -> "Linear4bitMultiLoRA":
+        """From stacked tensors ``[A_n, r, K]``, ``[A_n, N, r]`` and ``A_n`` scalings (a tensor or a sequence of floats): moved to the
+        base layer's device, cast to its compute dtype, contiguous."""
+        fix_4bit_weight_quant_state_from_module(base)
+        if getattr(base.weight, "quant_state", None) is None:
+            raise ValueError("Linear4bitMultiLoRA: the base layer must be quantized (load the checkpoint and move the model to the device first)")
+        if lora_A.dim() != 3 or lora_B.dim() != 3 or lora_A.shape[2] != base.in_features or lora_B.shape[1] != base.out_features:
+            raise ValueError(f"Linear4bitMultiLoRA: lora_A must be [A_n, r, {base.in_features}] and lora_B [A_n, {base.out_features}, r], "
+                             f"got {tuple(lora_A.shape)} and {tuple(lora_B.shape)}")
+        cd = base.compute_dtype if base.compute_dtype is not None else lora_A.dtype
+        dev = base.weight.device
+        sc = torch.as_tensor(scalings, dtype=torch.float32).detach().to(device=dev).contiguous()
+        return cls(base, lora_A.detach().to(device=dev, dtype=cd).contiguous(), lora_B.detach().to(device=dev, dtype=cd).contiguous(), sc)
+
+    @classmethod
+    def from_adapters(cls, base: "Linear4bit", adapters) -> "Linear4bitMultiLoRA":
+        """``adapters``: a sequence of ``(lora_A_i [r_i, K], lora_B_i [N, r_i], scaling_i)`` - adapter ``i`` gets id ``i``. Adapters of
+        different rank are stacked by ZERO-PADDING to the largest rank rounded up to a multiple of 8 (the kernels' granule): rows of
+        zeros appended to ``lora_A_i``, columns of zeros to ``lora_B_i``. The padded adapter is equal in VALUE to the unpadded one - the
+        extra terms of both sums are exact zeros - but bit-identity with a call on the unpadded adapter is not promised: the adapter
+        sum's order depends on the rank."""
+        adapters = list(adapters)
+        if not 1 <= len(adapters) <= 64:
+            raise ValueError(f"Linear4bitMultiLoRA.from_adapters: 1 ... 64 adapters, got {len(adapters)}")
+        K, N = base.in_features, base.out_features
+        for a, b, _ in adapters:
+            if a.dim() != 2 or b.dim() != 2 or a.shape[1] != K or b.shape[0] != N or a.shape[0] != b.shape[1] or a.shape[0] < 1:
+                raise ValueError(f"Linear4bitMultiLoRA.from_adapters: every adapter must be (lora_A [r, {K}], lora_B [{N}, r], scaling), "
+                                 f"got {tuple(a.shape)} and {tuple(b.shape)}")
+        r = -(-max(int(a.shape[0]) for a, _, _ in adapters) // 8) * 8
+        A = torch.zeros(len(adapters), r, K, dtype=adapters[0][0].dtype, device=adapters[0][0].device)
+        B = torch.zeros(len(adapters), N, r, dtype=adapters[0][1].dtype, device=adapters[0][1].device)
+        for i, (a, b, _) in enumerate(adapters):
+            A[i, :a.shape[0]] = a.detach().to(A.dtype)
+            B[i, :, :b.shape[1]] = b.detach().to(B.dtype)
+        return cls.from_stacks(base, A, B, [float(s) for _, _, s in adapters])
+
+    @staticmethod
+    def shrink_group(x: torch.Tensor, members, adapter_ids: torch.Tensor):
+        """The ``t`` of several :class:`Linear4bitMultiLoRA` layers that share ``x`` (Q / K / V, gate / up) and the SAME adapter order in
+        ONE launch: their ``lora_A`` stacks are concatenated per adapter into ``[A_n, sum r_i, K]`` (build the concatenation once and
+        pass it instead of the members to avoid the copy: ``members`` may be ``(stacked, splits)``) and
+        ``lora_shrink_ids(x, stacked, adapter_ids, splits)`` returns one contiguous ``[*, r_i]`` tensor per member - pass each to its
+        member's ``forward(x, adapter_ids, t=...)``."""
+        from ..autograd import lora_shrink_ids
+
+        if isinstance(members, tuple) and len(members) == 2 and isinstance(members[0], torch.Tensor):
+            stacked, splits = members
+        else:
+            stacked = torch.cat([m.lora_A for m in members], dim=1).contiguous()
+            splits = [int(m.lora_A.shape[1]) for m in members]
+        return lora_shrink_ids(x.to(stacked.dtype), stacked, adapter_ids, splits=tuple(splits))
+
+    def forward(self, x: torch.Tensor, adapter_ids: torch.Tensor, t: Optional[torch.Tensor] = None):
+        """``adapter_ids``: ``[*]`` with ``x``'s leading dims, int32 or int64, on ``x``'s device. ``t``: a precomputed mixed-adapter
+        shrink (``[*, r]``, :meth:`shrink_group`)."""
+        from ..autograd import lora_shrink_ids, matmul_4bit_lora_ids
+
+        base = self.base
+        fix_4bit_weight_quant_state_from_module(base)
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("Linear4bitMultiLoRA is inference only (no autograd formula): call it under torch.no_grad() or with detached inputs")
+        inp_dtype = x.dtype
+        xc = x.to(self.lora_A.dtype)
+        bias = base.bias
+        if bias is not None:
+            bias = bias.detach()
+            if bias.dtype != xc.dtype:
+                bias = bias.to(xc.dtype)
+        if t is None:
+            t = lora_shrink_ids(xc, self.lora_A, adapter_ids)
+        elif t.dtype != xc.dtype:
+            t = t.to(xc.dtype)
+        return matmul_4bit_lora_ids(xc, base.weight, base.weight.quant_state, t, self.lora_B, self.scalings, adapter_ids, bias=bias).to(inp_dtype)
+
+
 class LinearFP4(Linear4bit):
     def __init__(self, input_features, output_features, bias=True, compute_dtype=None, compress_statistics=True,
                  quant_storage=torch.uint8, device=None):

@@ -202,6 +202,22 @@ int bnb_mi355x_gemm_4bit_gated_supported(int dtype, int M, int N, int K, int blo
  * without a device) and add the adapter term with a second launch where it says 0. */
 void bnb_mi355x_gemm_4bit_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r, int M, int N, int K, int blocksize, int quant_type, bnb_stream_t stream);
 int bnb_mi355x_gemm_4bit_lora_supported(int dtype, int M, int N, int K, int blocksize, int nested, int r);
+/* Mixed-adapter form of bnb_mi355x_gemm_4bit_lora: a decode batch in which every row (request) has its own adapter. lora_b [A_n, N, r]
+ * row-major - the lora_B.weight of A_n adapters of ONE rank r, stacked -, scalings [A_n] fp32 and ids [M] (int32 / int64: index_bytes
+ * 4 / 8) on the DEVICE, read by the kernel only; 1 <= A_n <= 64:
+ *     out[m, n] = T((acc[m, n] + bias[n]) + scalings[ids[m]] * sum_j float(t[m, j]) * float(lora_b[ids[m], n, j]))    0 <= ids[m] < A_n
+ *     out[m, n] = the plain bnb_mi355x_gemm_4bit call's bits                                                          otherwise
+ * The whole 64-bit id is compared before any address is formed from it. A row without an adapter SKIPS the adapter term: its lora_t
+ * row and the scalings are never read. A row with one is BIT-IDENTICAL to row m of bnb_mi355x_gemm_4bit_lora(..., lora_t,
+ * lora_b + ids[m] * N * r, scalings[ids[m]], ...) at the same M, N, K and statistics: the same kernel family and instance skeleton,
+ * the same order of the adapter sum. Streaming kernel: the row's thread reads B_l's row from its adapter's matrix. Streaming MFMA
+ * kernel: the tile's wavefront loops over the distinct in-range ids of the batch in ascending order, one MFMA chain from a zero
+ * accumulator per adapter (t's lanes of other rows are out-of-range loads; lora_b's buffer resource is rebased per adapter with 64-bit
+ * arithmetic, so no bound on A_n * N * r), and keeps of each product only the rows of that adapter. Every other precondition: as for
+ * bnb_mi355x_gemm_4bit_lora; ids aligned to index_bytes. bnb_mi355x_gemm_4bit_lora_ids_supported answers 1 exactly where
+ * bnb_mi355x_gemm_4bit_lora_supported does, for every 1 <= A_n <= 64. */
+void bnb_mi355x_gemm_4bit_lora_ids(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, const float* scalings, const void* ids, int index_bytes, int A_n, int r, int M, int N, int K, int blocksize, int quant_type, bnb_stream_t stream);
+int bnb_mi355x_gemm_4bit_lora_ids_supported(int dtype, int M, int N, int K, int blocksize, int nested, int r, int A_n);
 /* LoRA shrink, the launch in front of bnb_mi355x_gemm_4bit_lora: x [M, K] and lora_a [R, K] row-major (lora_A.weight as stored, or up
  * to eight of them concatenated along dim 0), T = fp16 / bf16 (dtype 1 / 2) for both and for t:
  *     t[m, j] = T( sum_{k < K} float(x[m, k]) * float(lora_a[j, k]) )      fp32 sum, ONE rounding to T
@@ -218,6 +234,21 @@ int bnb_mi355x_gemm_4bit_lora_supported(int dtype, int M, int N, int K, int bloc
  * replaces; compose the matmul yourself where it says 0. */
 void bnb_mi355x_lora_shrink(int dtype, const void* x, const void* lora_a, void* t, int M, int R, int K, const int* splits, int n_splits, bnb_stream_t stream);
 int bnb_mi355x_lora_shrink_supported(int dtype, int M, int R, int K);
+/* Mixed-adapter LoRA shrink: a decode batch in which every row (request) has its own adapter. lora_a [A_n, R, K] row-major - the
+ * lora_A.weight of A_n adapters, stacked -, 1 <= A_n <= 64; ids: M values on the DEVICE, int32 (index_bytes 4) or int64 (8), read by
+ * the kernel only: no host synchronisation, and a captured graph follows new ids written into the same buffer.
+ *     t[m, j] = T( sum_{k < K} float(x[m, k]) * float(lora_a[ids[m], j, k]) )      0 <= ids[m] < A_n
+ *     t[m, :] = 0                                                                  otherwise: the row has no adapter
+ * The whole 64-bit id is compared (2^32 + 1 is out of range, not adapter 1), before any address is formed. A row with an adapter is
+ * BIT-IDENTICAL to row m of bnb_mi355x_lora_shrink(x, lora_a + ids[m] * R * K, ...) at the same M: same steps, same order. One launch
+ * on a grid of (R / 8, A_n) workgroups; those of an adapter that no row names return before they read lora_a or x, so the traffic is
+ * that of the distinct adapters of the batch; every element of t is written exactly once (rows without an adapter by adapter 0's
+ * workgroups). splits, t's layout and every other precondition: as for bnb_mi355x_lora_shrink; ids aligned to index_bytes. A call
+ * outside the preconditions prints a message and ends the process. bnb_mi355x_lora_shrink_ids_supported (pure host logic, aligned
+ * pointers assumed) answers 1 where the preconditions hold, minus the classes in which the launch measured behind the gathered
+ * torch.bmm it replaces (none excluded so far). */
+void bnb_mi355x_lora_shrink_ids(int dtype, const void* x, const void* lora_a, const void* ids, int index_bytes, void* t, int M, int A_n, int R, int K, const int* splits, int n_splits, bnb_stream_t stream);
+int bnb_mi355x_lora_shrink_ids_supported(int dtype, int M, int A_n, int R, int K);
 
 /* Grouped gemm_4bit: `count` weight matrices applied to the SAME activations A[M, K] in one launch -
  *   out[i][M, N[i]] = A * dequant(B[i])^T (+ bias[i])        i = 0 .. count-1
