@@ -22,6 +22,14 @@ def _is_compiling() -> bool:
     return torch.compiler.is_compiling()
 
 
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """``t`` contiguous and 16-byte aligned, as the fused decode launches want their operands: a view that starts elsewhere (a slice
+    of a larger buffer) is copied into storage of its own - one copy launch; the raw ops refuse such a view, and the compositions
+    would hand it to another kernel family, with other bits."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _gemm_4bit_from_state(A: torch.Tensor, B: torch.Tensor, quant_state: F.QuantState, bias):
     """Call the gemm_4bit op with the (possibly nested) statistics of ``quant_state``."""
     if not quant_state.nested:
@@ -192,6 +200,10 @@ def matmul_4bit_experts(
             f"matmul_4bit_experts: x inner dim ({x.shape[-1]}) must equal quant_state.shape[2] ({quant_state.shape[2]}); "
             "expert tensors in [E, K, N] orientation (contraction over the unpacked dimension) are not supported")
     packed = packed.view(-1, 1)
+    if x.device.type == "cuda" and not _is_compiling():
+        # (the kernel wants 16-byte aligned activations and weights and the op refuses anything else: a view that starts elsewhere - a
+        # slice of a larger buffer - is copied into storage of its own, one launch, instead of ending the caller's step)
+        x, packed = _aligned16(x), _aligned16(packed)
     if row_scale is None and gated == "none":
         op, extra = torch.ops.bitsandbytes_amd.gemm_4bit_experts.default, {}
     else:
@@ -272,11 +284,10 @@ def matmul_4bit_gated(x: torch.Tensor, gate_up: torch.Tensor, gate_up_state: F.Q
                            "or with detached inputs")
     if x.shape[-1] != gate_up_state.shape[1]:
         raise ValueError(f"matmul_4bit_gated: x inner dim ({x.shape[-1]}) must equal quant_state.shape[1] ({gate_up_state.shape[1]})")
-    if x.numel() > 0 and gate_up.data_ptr() % 16 == 0 and _gated_fused(x, gate_up_state):
-        xc = x.contiguous()
-        if xc.data_ptr() % 16 == 0 and (bias is None or bias.dtype == x.dtype):
-            return torch.ops.bitsandbytes_amd.gemm_4bit_gated.default(xc, gate_up.view(-1, 1), gate_up_state.shape, gate_up_state.absmax,
-                                                                      gate_up_state.blocksize, gate_up_state.quant_type, bias=bias)
+    if x.numel() > 0 and (bias is None or bias.dtype == x.dtype) and _gated_fused(x, gate_up_state):
+        # (misaligned views are copied: the composition below would run them on another kernel family - not the same bits)
+        return torch.ops.bitsandbytes_amd.gemm_4bit_gated.default(_aligned16(x), _aligned16(gate_up).view(-1, 1), gate_up_state.shape,
+                                                                  gate_up_state.absmax, gate_up_state.blocksize, gate_up_state.quant_type, bias=bias)
     y = matmul_4bit(x, gate_up, gate_up_state, bias=bias)
     return torch.nn.functional.silu(y[..., 0::2]) * y[..., 1::2]
 
@@ -338,17 +349,17 @@ def matmul_4bit_lora(x: torch.Tensor, weight: torch.Tensor, quant_state: F.Quant
         raise ValueError(f"matmul_4bit_lora: lora_b must be [N, r] = [{N}, r] and lora_t [*, r] with x's leading dims, "
                          f"got {tuple(lora_b.shape)} and {tuple(lora_t.shape)}")
     r = int(lora_b.shape[1])
-    if (x.numel() > 0 and weight.data_ptr() % 16 == 0 and lora_t.dtype == x.dtype and lora_b.dtype == x.dtype
+    if (x.numel() > 0 and lora_t.dtype == x.dtype and lora_b.dtype == x.dtype
             and (bias is None or bias.dtype == x.dtype) and _lora_fused(x, quant_state, r)):
-        xc, tc, bc = x.contiguous(), lora_t.contiguous(), lora_b.contiguous()
-        if xc.data_ptr() % 16 == 0 and tc.data_ptr() % 16 == 0 and bc.data_ptr() % 16 == 0:
-            op = torch.ops.bitsandbytes_amd.gemm_4bit_lora.default
-            if not quant_state.nested:
-                return op(xc, weight.view(-1, 1), quant_state.shape, quant_state.absmax, quant_state.blocksize, quant_state.quant_type, tc, bc,
-                          float(scaling), bias=bias)
-            return op(xc, weight.view(-1, 1), quant_state.shape, quant_state.state2.absmax, quant_state.blocksize, quant_state.quant_type, tc, bc,
-                      float(scaling), bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code,
-                      absmax_offset=quant_state.offset)
+        # (misaligned views are copied, so that the call keeps the fused launch and its bits)
+        xc, tc, bc, weight = _aligned16(x), _aligned16(lora_t), _aligned16(lora_b), _aligned16(weight)
+        op = torch.ops.bitsandbytes_amd.gemm_4bit_lora.default
+        if not quant_state.nested:
+            return op(xc, weight.view(-1, 1), quant_state.shape, quant_state.absmax, quant_state.blocksize, quant_state.quant_type, tc, bc,
+                      float(scaling), bias=bias)
+        return op(xc, weight.view(-1, 1), quant_state.shape, quant_state.state2.absmax, quant_state.blocksize, quant_state.quant_type, tc, bc,
+                  float(scaling), bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code,
+                  absmax_offset=quant_state.offset)
     y = matmul_4bit(x, weight, quant_state, bias=bias)
     out = torch.addmm(y.reshape(-1, N), lora_t.reshape(-1, r).to(y.dtype), lora_b.to(y.dtype).t(), alpha=float(scaling))
     return out.view(*x.shape[:-1], N)
@@ -363,7 +374,7 @@ def lora_shrink(x: torch.Tensor, lora_A: torch.Tensor, splits: Optional[Sequence
     The kernel serves 1 ... 16 rows of fp16 / bf16 on the device, ``K % 64 == 0``, ``R % 8 == 0``, ``8 <= R <= 1024``, up to 8 splits
     of 8 ... 128 rows, each a multiple of 8 (``backends.hip.lora_shrink_supported``): an fp32 sum in an order that depends on ``K``
     alone, rounded once, so a stacked call's parts are bit-identical to separate calls on the members. Every other call - CPU tensors,
-    fp32, more rows, misaligned operands, classes the measurements exclude - composes ``F.linear`` and a ``.contiguous()`` per part,
+    fp32, more rows, classes the measurements exclude - composes ``F.linear`` and a ``.contiguous()`` per part,
     whose bits are the BLAS library's. Neither path reads data on the host, so both can be captured in a graph. Inference only: there
     is no autograd formula."""
     if lora_A.dim() != 2 or x.dim() < 1 or x.shape[-1] != lora_A.shape[1]:
@@ -381,12 +392,10 @@ def lora_shrink(x: torch.Tensor, lora_A: torch.Tensor, splits: Optional[Sequence
         from ..backends import hip
 
         if hip.lora_shrink_supported(x.dtype, M, R, K) and hip.lora_shrink_splits_ok(splits):
-            xc, ac = x.contiguous(), lora_A.contiguous()
-            if xc.data_ptr() % 16 == 0 and ac.data_ptr() % 16 == 0:
-                buf = torch.ops.bitsandbytes_amd.lora_shrink.default(xc, ac, splits)
-                if splits is None:
-                    return buf
-                return tuple(p.view(*lead, r) for p, r in zip(buf.split([M * r for r in splits]), splits))
+            buf = torch.ops.bitsandbytes_amd.lora_shrink.default(_aligned16(x), _aligned16(lora_A), splits)  # (misaligned views: copied)
+            if splits is None:
+                return buf
+            return tuple(p.view(*lead, r) for p, r in zip(buf.split([M * r for r in splits]), splits))
     t = torch.nn.functional.linear(x, lora_A.to(x.dtype))
     if splits is None:
         return t
@@ -426,18 +435,18 @@ def matmul_4bit_lora_ids(x: torch.Tensor, weight: torch.Tensor, quant_state: F.Q
     if adapter_ids.dtype not in (torch.int32, torch.int64) or tuple(adapter_ids.shape) != tuple(x.shape[:-1]) or adapter_ids.device != x.device:
         raise ValueError(f"matmul_4bit_lora_ids: adapter_ids must be an int32 / int64 tensor of shape {tuple(x.shape[:-1])} (x's leading dims) "
                          f"on x's device, got {adapter_ids.dtype} {tuple(adapter_ids.shape)} on {adapter_ids.device}")
-    if (x.numel() > 0 and weight.data_ptr() % 16 == 0 and lora_t.dtype == x.dtype and lora_B.dtype == x.dtype and scalings.device == x.device
+    if (x.numel() > 0 and lora_t.dtype == x.dtype and lora_B.dtype == x.dtype and scalings.device == x.device
             and (bias is None or bias.dtype == x.dtype) and _lora_fused(x, quant_state, r)):
-        xc, tc, bc, ic = x.contiguous(), lora_t.contiguous(), lora_B.contiguous(), adapter_ids.contiguous()
+        # (misaligned views are copied, so that the call keeps the fused launch and its bits)
+        xc, tc, bc, weight, ic = _aligned16(x), _aligned16(lora_t), _aligned16(lora_B), _aligned16(weight), adapter_ids.contiguous()
         sc = scalings.to(torch.float32).contiguous()
-        if xc.data_ptr() % 16 == 0 and tc.data_ptr() % 16 == 0 and bc.data_ptr() % 16 == 0:
-            op = torch.ops.bitsandbytes_amd.gemm_4bit_lora_ids.default
-            if not quant_state.nested:
-                return op(xc, weight.view(-1, 1), quant_state.shape, quant_state.absmax, quant_state.blocksize, quant_state.quant_type, tc, bc,
-                          sc, ic, bias=bias)
-            return op(xc, weight.view(-1, 1), quant_state.shape, quant_state.state2.absmax, quant_state.blocksize, quant_state.quant_type, tc, bc,
-                      sc, ic, bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code,
-                      absmax_offset=quant_state.offset)
+        op = torch.ops.bitsandbytes_amd.gemm_4bit_lora_ids.default
+        if not quant_state.nested:
+            return op(xc, weight.view(-1, 1), quant_state.shape, quant_state.absmax, quant_state.blocksize, quant_state.quant_type, tc, bc,
+                      sc, ic, bias=bias)
+        return op(xc, weight.view(-1, 1), quant_state.shape, quant_state.state2.absmax, quant_state.blocksize, quant_state.quant_type, tc, bc,
+                  sc, ic, bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code,
+                  absmax_offset=quant_state.offset)
     y = matmul_4bit(x, weight, quant_state, bias=bias).reshape(-1, N)
     ids = adapter_ids.reshape(-1).to(torch.int64)
     valid = (ids >= 0) & (ids < A_n)
@@ -457,8 +466,8 @@ def lora_shrink_ids(x: torch.Tensor, lora_A: torch.Tensor, adapter_ids: torch.Te
 
     ONE launch where :func:`lora_shrink`'s kernel preconditions hold (``backends.hip.lora_shrink_ids_supported``): the ids are read by
     the kernel only, the workgroups of adapters no row names read nothing, and a row with an adapter has the bits of
-    ``lora_shrink(x, lora_A[id])``'s row at the same batch size. Every other call - CPU tensors, fp32, more than 16 rows, misaligned
-    operands - gathers ``lora_A.index_select(0, ids)`` and composes ``torch.bmm`` with the rows without an adapter masked: the same
+    ``lora_shrink(x, lora_A[id])``'s row at the same batch size. Every other call - CPU tensors, fp32, more than 16 rows -
+    gathers ``lora_A.index_select(0, ids)`` and composes ``torch.bmm`` with the rows without an adapter masked: the same
     values inside ``lora_shrink``'s tolerance, the bits the BLAS library's. Neither path reads data on the host, so both can be
     captured in a graph and follow ids written into the same buffer. Inference only: there is no autograd formula."""
     if lora_A.dim() != 3 or x.dim() < 1 or x.shape[-1] != lora_A.shape[2]:
@@ -481,12 +490,10 @@ def lora_shrink_ids(x: torch.Tensor, lora_A: torch.Tensor, adapter_ids: torch.Te
         from ..backends import hip
 
         if hip.lora_shrink_ids_supported(x.dtype, M, A_n, R, K) and hip.lora_shrink_splits_ok(splits):
-            xc, ac, ic = x.contiguous(), lora_A.contiguous(), adapter_ids.contiguous()
-            if xc.data_ptr() % 16 == 0 and ac.data_ptr() % 16 == 0:
-                buf = torch.ops.bitsandbytes_amd.lora_shrink_ids.default(xc, ac, ic, splits)
-                if splits is None:
-                    return buf
-                return tuple(p.view(*lead, r) for p, r in zip(buf.split([M * r for r in splits]), splits))
+            buf = torch.ops.bitsandbytes_amd.lora_shrink_ids.default(_aligned16(x), _aligned16(lora_A), adapter_ids.contiguous(), splits)
+            if splits is None:
+                return buf
+            return tuple(p.view(*lead, r) for p, r in zip(buf.split([M * r for r in splits]), splits))
     ids = adapter_ids.reshape(-1).to(torch.int64)
     valid = (ids >= 0) & (ids < A_n)
     gathered = lora_A.to(x.dtype).index_select(0, torch.where(valid, ids, torch.zeros_like(ids)))  # [M, R, K]

@@ -269,6 +269,8 @@ def _(A, absmax, indices, row_len: int, blocksize: int, quant_type: str, dtype: 
     A = A.contiguous()
     absmax = absmax.contiguous()
     indices = indices.contiguous()
+    if A.data_ptr() % 4:  # (the kernel reads the packed rows a dword at a time; the C entry point ends the process on anything else)
+        A = A.clone()
     num_rows = (A.numel() * A.element_size() * 2) // row_len
     out = torch.empty((*indices.shape, row_len), dtype=dtype, device=A.device)
     with _device_of(A):

@@ -126,7 +126,9 @@ void bnb_mi355x_dequantize_4bit_nested(int dtype, const unsigned char* A, const 
  * F.embedding on the packed bytes, F.embedding on absmax, dequantize_4bit). A is the packed
  * [num_rows, row_len] table, absmax its fp32 scales (un-nested); row_len % 8 == 0 and
  * row_len % blocksize == 0; indices are int32 (index_bytes 4) or int64 (8). Values are bit-identical to
- * cdequantize_blockwise_* applied to the gathered rows. An index outside [0, num_rows) gives a row of NaN. */
+ * cdequantize_blockwise_* applied to the gathered rows. An index outside [0, num_rows) gives a row of NaN. A must be 4-byte aligned
+ * (the packed rows are read a dword at a time) and out 16-byte aligned; absmax and indices need their element's alignment. A call
+ * outside these preconditions prints a message and ends the process, like every failed launch of this ABI. */
 void bnb_mi355x_dequantize_4bit_rows(int dtype, const unsigned char* A, const float* absmax, const void* indices, int index_bytes, void* out, long rows_out, long num_rows, int row_len, int blocksize, int quant_type, bnb_stream_t stream);
 
 /* gemm_4bit with an explicit kernel choice and a caller-owned split-K workspace:

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
-"""Out-of-bounds WRITES and alignment assumptions of every C-ABI entry point of the path: all operands are carved out of larger
-buffers at RANDOM element offsets (so pointers are aligned to the element size and nothing more), every output (and scratch) region
-sits between guard bands filled with 0xA5, and after each call
+"""Out-of-bounds WRITES and alignment assumptions of the C-ABI entry points of the base path - quantize_4bit (plain, nested),
+dequantize_4bit (plain, nested), the 8-bit blockwise pair, gemm_4bit and gemm_4bit_grad_input; the fused decode entry points
+(experts, experts_ffn, gated, lora, lora_ids, lora_shrink, lora_shrink_ids, grouped, dequantize_4bit_rows) are
+tests/checks/guard_fused.py's: all operands are carved out of larger buffers (tests/guard_bands.py) at RANDOM element offsets (so
+pointers are aligned to the element size and nothing more), every output (and scratch) region sits between guard bands filled with
+0xA5, and after each call
   * the guard bands must be untouched,
   * the result must equal (quantize / dequantize: bit for bit; matmuls: within 1e-2 / 1e-5) what the public operator gives on
     freshly allocated, aligned tensors.
@@ -21,56 +24,14 @@ import bitsandbytes_amd as bnb  # noqa: E402
 import bitsandbytes_amd.functional as F  # noqa: E402
 from bitsandbytes_amd.backends import hip  # noqa: E402
 
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from guard_bands import Carved, carve_in, carve_out, read  # noqa: E402,F401
+
 DEV = "cuda"
-G = 8192  # guard bytes on each side
-PAT = 0xA5
 DT_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 DT_NAME = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}
 QT_CODE = {"fp4": 1, "nf4": 2}
 lib = bnb.lib
-
-
-class Carved:
-    """nbytes inside a guarded buffer, starting `off` bytes past a 256-byte-aligned address."""
-
-    def __init__(self, nbytes, off):
-        self.buf = torch.full((nbytes + 2 * G + 512,), PAT, dtype=torch.uint8, device=DEV)
-        base = self.buf.data_ptr()
-        self.start = G + (-base - G) % 256 + off
-        self.nbytes = nbytes
-        self.view = self.buf[self.start:self.start + nbytes]
-
-    def ptr(self):
-        return self.view.data_ptr()
-
-    def put(self, t):
-        self.view.copy_(t.contiguous().view(-1).view(torch.uint8))
-        return self
-
-    def as_tensor(self, dtype, shape):
-        return self.view.view(dtype).view(*shape)  # (only when the offset keeps torch's alignment rule for the dtype)
-
-    def bytes(self):
-        return self.view.clone()
-
-    def guards_ok(self):
-        lo = self.buf[:self.start]
-        hi = self.buf[self.start + self.nbytes:]
-        return bool((lo == PAT).all()) and bool((hi == PAT).all())
-
-
-def carve_in(t, rng, elt=None):
-    elt = elt or t.element_size()
-    c = Carved(t.numel() * t.element_size(), elt * rng.randint(0, 31))
-    return c.put(t)
-
-
-def carve_out(nbytes, rng, elt):
-    return Carved(nbytes, elt * rng.randint(0, 31))
-
-
-def read(c, dtype, n):
-    return c.bytes().view(dtype)[:n] if c.nbytes else torch.empty(0, dtype=dtype, device=DEV)
 
 
 def main():

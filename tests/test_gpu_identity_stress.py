@@ -50,8 +50,11 @@ def test_random_shapes_through_the_public_operators_against_the_oracle():
 
 
 def test_no_entry_point_writes_outside_its_outputs_or_needs_more_than_element_alignment():
-    """tests/checks/guard_stress.py: every operand of every C-ABI entry point carved out of a larger buffer at a random element
-    offset, outputs and scratch between guard bands: bands untouched, results equal to the public operator on aligned tensors."""
+    """tests/checks/guard_stress.py: every operand of the base path's C-ABI entry points - quantize_4bit (plain, nested),
+    dequantize_4bit (plain, nested), the 8-bit blockwise pair, gemm_4bit, gemm_4bit_grad_input - carved out of a larger buffer at a
+    random element offset, outputs and scratch between guard bands: bands untouched, results equal to the public operator on aligned
+    tensors. The fused decode entry points and the rest of the reference ABI: tests/checks/guard_fused.py, run by
+    tests/test_gpu_guard_fused.py; tests/test_guard_bands_host.py keeps the ledger of which entry point runs where."""
     if not gpu_ready() and not os.path.exists("/dev/kfd") and os.environ.get("BNB_REQUIRE_GPU") != "1":
         pytest.skip("no GPU device on this host")
     assert gpu_ready(), "GPU tests selected but torch.cuda.is_available() is False"
