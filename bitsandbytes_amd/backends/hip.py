@@ -586,8 +586,8 @@ def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str,
 # ------------------------------------------------------------------------------------------ gemm_4bit_gated
 def gemm_4bit_gated_supported(dtype: torch.dtype, M: int, N: int, K: int, blocksize: int) -> bool:
     """Whether ``bitsandbytes_amd::gemm_4bit_gated`` has a kernel for ``M`` rows on the interleaved ``[N = 2 F, K]`` matrix: the
-    plain call of that shape runs the streaming or the streaming MFMA kernel, 16-bit activations, ``M <= 16``, blocksize >= 64
-    (pure host logic of the library plus the CU count of the current device, as the route queries)."""
+    plain call of that shape runs the streaming or the streaming MFMA kernel (so ``N * K < 2**32``), 16-bit activations, ``M <= 16``,
+    blocksize >= 64 (pure host logic of the library plus the CU count of the current device, as the route queries)."""
     if dtype not in (torch.float16, torch.bfloat16) or max(M, N, K) >= 2**31 or min(M, N, K) < 1:
         return False
     return bool(lib.bnb_mi355x_gemm_4bit_gated_supported(_DT_CODE[dtype], M, N, K, blocksize))
@@ -619,8 +619,8 @@ def _(A, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: str, bias
 # ------------------------------------------------------------------------------------------ gemm_4bit_lora
 def gemm_4bit_lora_supported(dtype: torch.dtype, M: int, N: int, K: int, blocksize: int, nested: bool, r: int) -> bool:
     """Whether ``bitsandbytes_amd::gemm_4bit_lora`` has a kernel for ``M`` rows on the ``[N, K]`` matrix with a rank-``r`` adapter: the
-    plain call of that shape runs the streaming or the streaming MFMA kernel, 16-bit activations, ``M <= 16``, blocksize >= 64,
-    ``r % 8 == 0``, ``8 <= r <= 128`` (pure host logic of the library plus the CU count of the current device, as the route queries)."""
+    plain call of that shape runs the streaming or the streaming MFMA kernel (so ``N * K < 2**32``), 16-bit activations, ``M <= 16``,
+    blocksize >= 64, ``r % 8 == 0``, ``8 <= r <= 128`` (pure host logic of the library plus the CU count of the current device, as the route queries)."""
     if dtype not in (torch.float16, torch.bfloat16) or max(M, N, K, r) >= 2**31 or min(M, N, K, r) < 1:
         return False
     return bool(lib.bnb_mi355x_gemm_4bit_lora_supported(_DT_CODE[dtype], M, N, K, blocksize, 1 if nested else 0, r))

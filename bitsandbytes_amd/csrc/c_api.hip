@@ -34,6 +34,7 @@ bool gemv_4bit_grouped(int dtype, const void* A, int count, const uint8_t* const
 void gemv_4bit_stream_tuning(int ns, int sw, int rows_per_wg, int nt, int waves);
 bool gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, bool nested);
 bool gemv_4bit_stream_gated_supported(int dtype, int M, int N, int K, int blocksize);
+bool gemv_4bit_stream_size_ok(long N, long K);
 bool gemv_4bit_stream_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K,
                             int blocksize, int quant_type, hipStream_t stream);
 bool gemv_4bit_stream_lora_supported(int dtype, int M, int N, int K, int blocksize, int r);
@@ -450,7 +451,10 @@ int bnb_mi355x_gemm_4bit_grouped_route(int dtype, int count, const int* N, int M
         if (ok)
             return 2;
     }
-    return (!any_mfma && M <= 4) ? 1 : 0;
+    bool stream_sizes = true; // (gemv_4bit_grouped: every member below 2^32 elements)
+    for (int i = 0; i < count; ++i)
+        stream_sizes = stream_sizes && gemv_4bit_stream_size_ok(N[i], K);
+    return (!any_mfma && M <= 4 && stream_sizes) ? 1 : 0;
 }
 size_t bnb_mi355x_gemm_4bit_workspace_bytes(int kernel, int dtype, int M, int N, int K, int blocksize) {
     // alignment of A/B is unknown here; assume the aligned (fast) case, an unused workspace is harmless

@@ -905,6 +905,12 @@ bool gemm_4bit_sm_routes(int dtype, int M, int N, int K, int blocksize) {
 // >= 64 (a 64-k MFMA pair stays inside one quantization block) - or, round 5, blocksize 32 with fp32 absmax (`plain_absmax`: the
 // caller knows, the shape-only queries assume it), which the register-transposed kernel's BS32 instances serve at any M.
 bool gemm_4bit_mfma_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize, bool plain_absmax) {
+    // No MFMA kernel is claimed at or past 2^32 weight elements: the streaming MFMA, register-transposed and tall-tile kernels stop there
+    // by their own predicates (32-bit byte offsets), the K-quarter kernel at 2^31. The producer/consumer kernel addresses with `long` and
+    // was bit-exact on 2^32 + 130 rows in the one run that tried it, but no test of the suite holds it there: the route states
+    // one limit for all of them, and such a weight runs the generic kernel (csrc/gemv4_stream.hip: stream_size_ok).
+    if (static_cast<long long>(N) * K >= (1LL << 32))
+        return false;
     if (blocksize == 32) // (the BS32 instances' own preconditions: literal code table, 32-bit byte offsets - ADVICE round 5: a call that
                          // passed this test and failed those used to end the process)
         return plain_absmax && gemm_4bit_rt_supported(dtype, A, B, code16, M, N, K, blocksize);

@@ -375,7 +375,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     Stage st[NS];
     constexpr uint32_t kOob = 0xFFFFFFF0u; // beyond num_records
     constexpr int kRsrcFlags = 0x00020000;
-    constexpr int kRecords = 0x7FFFFFFF;   // the descriptors only exist for the out-of-range trick: valid offsets are < 2^30
+    constexpr int kRecords = 0x7FFFFFFF;   // the descriptors only exist for the out-of-range trick: valid offsets are < 2^31 (stream_size_ok)
     constexpr int kWeightAux = NT ? 2 : 0; // nt: streamed once, read by one CU
 
     // matrix of a concatenated row (grouped launches): wave-uniform scan over <= kMaxGroup descriptors
@@ -1289,6 +1289,13 @@ bool stream_ok(const void* A, int M, int K, int blocksize) {
     // (the phase count travels in 9 bits and grid.y in 16: far beyond any real layer, the generic kernel takes the rest)
     return (K % 32 == 0) && K <= 511 * kSegK && M <= 65535 && blocksize >= 32 && is_pow2(blocksize) && aligned_to(A, 16);
 }
+// The size half of the streaming kernel's preconditions, per weight matrix: N K < 2^32. The weight loads carry the row's byte offset
+// (row * K / 2) as the scalar offset of a descriptor of 2^31 - 1 records, and the range check counts it: a load that ends past byte
+// 2^31 - 1 returns zeros - measured on a 524418 x 8192 weight, whose rows from 2^32 / K - 1 on came out wrong, finite and without an
+// error. The element index of a row (row * K + k0, and the nested group indices e0 / e1) is formed in 32 bits as well: past
+// 2^32 elements it lands 2^32 / blocksize blocks short. Such a weight runs the generic kernel, whose addressing is `long`; the forms
+// without a generic twin (gated, LoRA, grouped) answer "not supported".
+bool stream_size_ok(long N, long K) { return N * K < (1L << 32); }
 
 void launch_stream_any(int dtype, const StreamArgs& a, int quant_type, bool grouped, hipStream_t stream) {
     if (dtype == 2)
@@ -1406,6 +1413,9 @@ static bool peer_geometry(int world, int ns, int K, int blocksize, int mode, lon
 
 } // namespace
 
+// (c_api.hip: the grouped route query asks the same question as gemv_4bit_grouped)
+bool gemv_4bit_stream_size_ok(long N, long K) { return stream_size_ok(N, K); }
+
 bool gemv_4bit_peer_serves(int world, int ns, int K, int blocksize, int mode, long max_values, int wg_limit) {
     return peer_geometry(world, ns, K, blocksize, mode, max_values, wg_limit, nullptr, nullptr);
 }
@@ -1513,7 +1523,7 @@ void gemv_4bit_stream(int dtype, const void* A, const uint8_t* B, const float* a
                    const void* bias, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
     if (M <= 0 || N <= 0 || K <= 0)
         return;
-    if (stream_ok(A, M, K, blocksize) && aligned_to(B, 16)) {
+    if (stream_ok(A, M, K, blocksize) && stream_size_ok(N, K) && aligned_to(B, 16)) {
         StreamArgs a;
 #ifdef BNB_PROFILING
         a.dbg = g_dbg_buf;
@@ -1549,7 +1559,8 @@ void gemv_4bit_stream(int dtype, const void* A, const uint8_t* B, const float* a
 static int gated_mb(int M) { return M == 1 ? 1 : M == 2 ? 2 : 4; }
 static int gated_waves(int M, int N, int K) { return M == 1 ? 16 : (M == 2 && make_geometry(N, K, 2, 16, 2, false, 0, 0, true).P == 1) ? 16 : 8; }
 bool gemv_4bit_stream_gated_supported(int dtype, int M, int N, int K, int blocksize) {
-    if ((dtype != 1 && dtype != 2) || M < 1 || N < 2 || (N & 1) || K <= 0 || (K % 32) != 0 || K > 511 * kSegK || blocksize < 32 || !is_pow2(blocksize))
+    if ((dtype != 1 && dtype != 2) || M < 1 || N < 2 || (N & 1) || K <= 0 || (K % 32) != 0 || K > 511 * kSegK || blocksize < 32 || !is_pow2(blocksize) ||
+        !stream_size_ok(N, K))
         return false;
     const Geometry ge = make_geometry(N, K, gated_mb(M), gated_waves(M, N, K), 2, false, g_tune.sw.load(std::memory_order_relaxed),
                                       g_tune.rows.load(std::memory_order_relaxed), true);
@@ -1598,7 +1609,7 @@ bool gemv_4bit_stream_gated(int dtype, const void* A, const uint8_t* B, const fl
 // preconditions, shared with the host layer's query:
 bool gemv_4bit_stream_lora_supported(int dtype, int M, int N, int K, int blocksize, int r) {
     return (dtype == 1 || dtype == 2) && M >= 1 && M <= 65535 && N >= 1 && K > 0 && (K % 32) == 0 && K <= 511 * kSegK && blocksize >= 32 && is_pow2(blocksize) &&
-           r >= 8 && r <= 128 && (r % 8) == 0;
+           r >= 8 && r <= 128 && (r % 8) == 0 && stream_size_ok(N, K);
 }
 template <typename T, int FLAGS> static void launch_lora(const StreamArgs& a, hipStream_t stream) {
     if (a.M == 1)
@@ -1722,7 +1733,7 @@ bool gemv_4bit_grouped(int dtype, const void* A, int count, const uint8_t* const
     long rows = 0;
     const bool nested = absmax8 != nullptr && absmax8[0] != nullptr;
     for (int i = 0; i < count; ++i) {
-        if (N[i] <= 0 || !aligned_to(B[i], 16))
+        if (N[i] <= 0 || !aligned_to(B[i], 16) || !stream_size_ok(N[i], K))
             return false;
         if (((absmax8 != nullptr && absmax8[i] != nullptr)) != nested)
             return false;

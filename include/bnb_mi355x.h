@@ -139,7 +139,11 @@ void bnb_mi355x_dequantize_4bit_rows(int dtype, const unsigned char* A, const fl
 void bnb_mi355x_gemm_4bit(int kernel, int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, const float* code16, void* out, const void* bias, int M, int N, int K, int blocksize, int quant_type, void* workspace, size_t workspace_bytes, bnb_stream_t stream);
 size_t bnb_mi355x_gemm_4bit_workspace_bytes(int kernel, int dtype, int M, int N, int K, int blocksize);
 /* Which kernel family bnb_mi355x_gemm_4bit(kernel, ...) runs for this problem (aligned pointers assumed): 0 = streaming
- * kernel, 1 = MFMA kernels. The grouped entry point below goes matrix by matrix when any member answers 1. */
+ * kernel, 1 = MFMA kernels. The grouped entry point below goes matrix by matrix when any member answers 1.
+ * Size: the streaming kernel and every MFMA kernel serve weights of N * K < 2^32 elements (the K-quarter kernel N * K < 2^31; 32-bit
+ * byte offsets under descriptors of 2^31 - 1 records). From 2^32 elements on the answer is 0 at every M and the call runs the generic
+ * scalar kernel (family 2, 64-bit addressing, correct and slow); the gated, LoRA and grouped-streaming forms answer "not supported"
+ * there. The expert-indexed kernel (E * N < 2^31 rows) and the fused backward have no element limit. */
 int bnb_mi355x_gemm_4bit_route(int kernel, int dtype, int M, int N, int K, int blocksize);
 /* Which kernel family the calling thread's LAST gemm_4bit / gemv_4bit call (any entry point) launched: 0 none yet, 1 streaming
  * kernel (gemv4_stream_kernel), 2 generic scalar kernel (odd shapes), 3 register-transposed MFMA kernel (gemm4_mfma_rt_kernel),
