@@ -25,7 +25,7 @@
 // Layout: a lane owns 4 consecutive elements (one 16-byte fp32 / 8-byte 16-bit load, one 4-byte store of
 // codes); a wavefront covers 256 consecutive elements per step; the block max is a DPP/shuffle reduction over
 // blocksize/4 lanes, or an accumulation over blocksize/256 steps of one wavefront for the larger blocks.
-#include "bnb_common.h"
+#include "bnb_launchers.h"
 
 #include <atomic>
 

@@ -1,116 +1,29 @@
 // c_api.hip — the extern "C" surface of libbitsandbytes_mi355x.so (declared in include/bnb_mi355x.h).
-// Thin, un-mangled wrappers over the launchers in quantize4.hip, dequantize4.hip, blockwise8.hip,
-// gemv4_stream.hip, gemm4_mfma.hip and gemm4_mfma_rt.hip. Mirrors the symbol set the reference exports for this path from
-// csrc/pythonInterface.cpp:343-841 and csrc/gemm_4bit.cu:136-168.
-#include "bnb_common.h"
+// Thin, un-mangled wrappers over the launchers of the other files (declared in bnb_launchers.h). Mirrors the symbol set the
+// reference exports for this path from csrc/pythonInterface.cpp:343-841 and csrc/gemm_4bit.cu:136-168.
+#include "bnb_launchers.h"
 
 #include "../../include/bnb_mi355x.h"
 
 namespace bnb {
-// quantize4.hip
-void quantize_4bit_f32(const float*, float*, uint8_t*, int, long, int, hipStream_t);
-void quantize_4bit_f16(const void*, float*, uint8_t*, int, long, int, hipStream_t);
-void quantize_4bit_bf16(const void*, float*, uint8_t*, int, long, int, hipStream_t);
-// dequantize4.hip
-void dequantize_4bit_f32(const uint8_t*, const float*, float*, int, long, int, hipStream_t);
-void dequantize_4bit_rows(int, const uint8_t*, const float*, const void*, int, void*, long, long, int, int, int, hipStream_t);
-void dequantize_4bit_f16(const uint8_t*, const float*, void*, int, long, int, hipStream_t);
-void dequantize_4bit_bf16(const uint8_t*, const float*, void*, int, long, int, hipStream_t);
-// blockwise8.hip
-void quantize_8bit_f32(const float*, const float*, float*, uint8_t*, int, long, hipStream_t);
-void quantize_8bit_f16(const float*, const void*, float*, uint8_t*, int, long, hipStream_t);
-void quantize_8bit_bf16(const float*, const void*, float*, uint8_t*, int, long, hipStream_t);
-void dequantize_8bit_f32(const float*, const uint8_t*, const float*, float*, int, long, hipStream_t);
-void dequantize_8bit_f16(const float*, const uint8_t*, const float*, void*, int, long, hipStream_t);
-void dequantize_8bit_bf16(const float*, const uint8_t*, const float*, void*, int, long, hipStream_t);
-// gemv4_stream.hip
-void gemv_4bit_stream(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
-                      const float* absmax_code, const float* absmax_offset, const float* code16, void* out,
-                      const void* bias, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream);
-bool gemv_4bit_grouped(int dtype, const void* A, int count, const uint8_t* const* B, const float* const* absmax,
-                       const uint8_t* const* absmax8, const float* const* absmax_code, const float* const* absmax_offset,
-                       void* const* out, const void* const* bias, const int* N, int M, int K, int blocksize, int quant_type,
-                       hipStream_t stream);
-void gemv_4bit_stream_tuning(int ns, int sw, int rows_per_wg, int nt, int waves);
-bool gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, bool nested);
-bool gemv_4bit_stream_gated_supported(int dtype, int M, int N, int K, int blocksize);
-bool gemv_4bit_stream_size_ok(long N, long K);
-bool gemv_4bit_stream_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K,
-                            int blocksize, int quant_type, hipStream_t stream);
-bool gemv_4bit_stream_lora_supported(int dtype, int M, int N, int K, int blocksize, int r);
-bool gemv_4bit_stream_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
-                           const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r,
-                           int M, int N, int K, int blocksize, int quant_type, hipStream_t stream);
-bool gemv_4bit_peer(void* const* bufs, void* epoch_word, int world, int rank, int dtype, const void* A, const uint8_t* B, const float* absmax,
-                    const uint8_t* absmax8, const float* absmax_code, const float* absmax_offset, const void* bias, void* out_local,
-                    int ns, int K, int blocksize, int quant_type, int mode, long max_values, int wg_limit, uint32_t epoch_offset,
-                    uint32_t spin_bound, hipStream_t stream);
-void peer_chain_read(void* const* bufs, void* epoch_word, int world, int rank, int dtype, void* out, int nvalues, long max_values, uint32_t epoch_offset,
-                     uint32_t spin_bound, hipStream_t stream);
-bool gemv_4bit_peer_serves(int world, int ns, int K, int blocksize, int mode, long max_values, int wg_limit);
 thread_local int g_last_gemm_kernel = kKernelNone;
 #ifdef BNB_PROFILING
 unsigned long long* g_dbg_buf = nullptr; // profiling builds only: device buffer for the kernels' s_memtime stamps
 #endif
-// gemm4_mfma.hip
-bool gemm_4bit_mfma_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize, bool plain_absmax);
-void gemm_4bit_mfma(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
-                    const float* absmax_code, const float* absmax_offset, const float* code16, void* out,
-                    const void* bias, int M, int N, int K, int blocksize, int quant_type, void* workspace,
-                    size_t workspace_bytes, hipStream_t stream);
-size_t gemm_4bit_mfma_workspace_bytes(int M, int N, int K, int blocksize);
-bool gemm_4bit_sm_routes(int dtype, int M, int N, int K, int blocksize);
-bool gemm_4bit_sm_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize);
-bool gemm_4bit_sm_grouped(int dtype, const void* A, int count, const uint8_t* const* B, const float* const* absmax,
-                          const uint8_t* const* absmax8, const float* const* absmax_code, const float* const* absmax_offset,
-                          void* const* out, const void* const* bias, const int* N, int M, int K, int blocksize, int quant_type,
-                          hipStream_t stream);
-bool gemm_4bit_sm_serves(const float* absmax, const uint8_t* absmax8, int blocksize);
-bool gemm_4bit_sm_gated_supported(int dtype, const void* A, const uint8_t* B, int M, int N, int K, int blocksize);
-bool gemm_4bit_sm_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K,
-                        int blocksize, int quant_type, hipStream_t stream);
-bool gemm_4bit_sm_lora_supported(int dtype, const void* A, const uint8_t* B, int M, int N, int K, int blocksize, int r);
-bool gemm_4bit_sm_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
-                       const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r,
-                       int M, int N, int K, int blocksize, int quant_type, hipStream_t stream);
-bool gemv_4bit_stream_lora_ids(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
-                               const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, const float* scalings,
-                               const void* ids, int index_bytes, int A_n, int r, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream);
-bool gemm_4bit_sm_lora_ids(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
-                           const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, const float* scalings,
-                           const void* ids, int index_bytes, int A_n, int r, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream);
-extern thread_local TlsKnob g_mfma_knob0, g_mfma_knob1;
-// lora_shrink.hip
-bool lora_shrink_supported(int dtype, int M, int R, int K);
-bool lora_shrink(int dtype, const void* x, const void* lora_a, void* t, int M, int R, int K, const int* splits, int n_splits, hipStream_t stream);
-bool lora_shrink_ids_supported(int dtype, int M, int A_n, int R, int K);
-bool lora_shrink_ids(int dtype, const void* x, const void* lora_a, const void* ids, int index_bytes, void* t, int M, int A_n, int R, int K,
-                     const int* splits, int n_splits, hipStream_t stream);
-// gemm4_grad_input.hip
-bool gemm_4bit_grad_input_supported(int dtype, const void* G, const uint8_t* B, int M, int N, int K, int blocksize);
-size_t gemm_4bit_grad_input_workspace_bytes(int M, int N, int K);
-void quantize_8bit_set_variant(int variant);
-void quantize_absmax_nested(const float* code, const float* absmax, long n, float* partial, float* offset_out, uint8_t* out, float* absmax2, hipStream_t stream);
-void quantize_4bit_set_variant(int variant);
-void dequantize_4bit_set_variant(int variant);
-void dequantize_4bit_nested(int, const uint8_t*, const uint8_t*, const float*, const float*, const float*, void*, int, long, int, hipStream_t);
-void gemm_4bit_grad_input_set_slices(int ns);
-void gemm_4bit_grad_input(int dtype, const void* G, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
-                          const float* absmax_code, const float* absmax_offset, void* out, int M, int N, int K, int blocksize,
-                          int quant_type, void* workspace, size_t workspace_bytes, hipStream_t stream);
-
-// gemm4_experts.hip
-bool gemm_4bit_experts_supported(int dtype, long E, long N, long K, int blocksize);
-void gemm_4bit_experts(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
-                       const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes,
-                       void* out, long P, int S, int E, int N, int K, int blocksize, int quant_type, hipStream_t stream);
-bool gemm_4bit_experts_ffn_supported(int dtype, long E, long N, long K, int blocksize, int gated);
-void gemm_4bit_experts_ffn(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
-                           const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes,
-                           const void* row_scale, int row_scale_dtype, int gated, void* out, long P, int S, int E, int N, int K,
-                           int blocksize, int quant_type, hipStream_t stream);
 
 namespace {
+
+// The alignment of A / B / absmax is unknown to the shape-only queries: they assume the aligned (fast) case and pass this.
+const int kAlignedDummy[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
+const uint8_t* const kAlignedDummy8 = reinterpret_cast<const uint8_t*>(kAlignedDummy);
+
+// Error convention of the reference ABI (bnb_common.h): an entry point that cannot serve its call prints and terminates.
+void require_quant_type(const char* entry, int quant_type) {
+    if (quant_type != kFP4 && quant_type != kNF4) {
+        fprintf(stderr, "bitsandbytes_amd: %s: quant_type must be 1 (FP4) or 2 (NF4), got %d\n", entry, quant_type);
+        exit(1);
+    }
+}
 
 // M at or below which the streaming dot kernel is used (its activations live in registers: 32 fp32 per row and
 // lane); above it the MFMA kernels (when supported). MI355X-specific replacement for the reference's per-arch
@@ -142,10 +55,7 @@ void gemm_4bit_dispatch(int kernel, int dtype, const void* A, const uint8_t* B, 
                         int quant_type, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     if (M <= 0 || N <= 0)
         return;
-    if (quant_type != kFP4 && quant_type != kNF4) {
-        fprintf(stderr, "bitsandbytes_amd: gemm_4bit: quant_type must be 1 (FP4) or 2 (NF4), got %d\n", quant_type);
-        exit(1);
-    }
+    require_quant_type("gemm_4bit", quant_type);
     if (route_to_mfma(kernel, dtype, A, B, code16, M, N, K, blocksize, absmax8 == nullptr && aligned_to(absmax, 16)))
         gemm_4bit_mfma(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, code16, out, bias, M, N, K, blocksize,
                        quant_type, workspace, workspace_bytes, stream);
@@ -328,10 +238,7 @@ void* cget_managed_ptr(size_t bytes) {
 // ------------------------------------------------------------------ extensions
 void bnb_mi355x_quantize_4bit(const void* A, int dtype, float* absmax, unsigned char* out, int blocksize, long n,
                               int quant_type, bnb_stream_t s) {
-    if (quant_type != kFP4 && quant_type != kNF4) {
-        fprintf(stderr, "bitsandbytes_amd: quantize_4bit: quant_type must be 1 (FP4) or 2 (NF4)\n");
-        exit(1);
-    }
+    require_quant_type("quantize_4bit", quant_type);
     if (dtype == 0)
         quantize_4bit_f32(static_cast<const float*>(A), absmax, out, blocksize, n, quant_type, S(s));
     else if (dtype == 1)
@@ -348,10 +255,7 @@ void bnb_mi355x_dequantize_4bit_rows(int dtype, const unsigned char* A, const fl
 void bnb_mi355x_dequantize_4bit_nested(int dtype, const unsigned char* A, const unsigned char* absmax_8bit, const float* absmax2,
                                        const float* absmax_code, const float* absmax_offset, void* out, int blocksize, long n,
                                        int quant_type, bnb_stream_t s) {
-    if (quant_type != kFP4 && quant_type != kNF4) {
-        fprintf(stderr, "bitsandbytes_amd: dequantize_4bit_nested: quant_type must be 1 (FP4) or 2 (NF4)\n");
-        exit(1);
-    }
+    require_quant_type("dequantize_4bit_nested", quant_type);
     dequantize_4bit_nested(dtype, A, absmax_8bit, absmax2, absmax_code, absmax_offset, out, blocksize, n, quant_type, S(s));
 }
 void bnb_mi355x_quantize_8bit(const float* code, const void* A, int dtype, float* absmax, unsigned char* out,
@@ -402,15 +306,16 @@ void bnb_mi355x_gemm_4bit_grouped(int dtype, const void* A, int count, const uin
                                   int M, int K, int blocksize, int quant_type, bnb_stream_t s) {
     if (count <= 0 || M <= 0)
         return;
-    if (quant_type != kFP4 && quant_type != kNF4) {
-        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_grouped: quant_type must be 1 (FP4) or 2 (NF4), got %d\n", quant_type);
-        exit(1);
-    }
-    // "bit-identical to separate calls": every member runs the kernel FAMILY the single-matrix entry point would give it.
-    //  * every member routed to the streaming MFMA kernel (2 ... 16 rows, csrc/gemm4_mfma.hip: sm_selected): ONE launch of that
-    //    kernel over the members' rows (its summation order does not depend on the launch geometry) - round 6;
-    //  * no member routed to an MFMA kernel: ONE launch of the streaming kernel (M <= 4);
-    //  * anything else (mixed routes, M > 16, more than 8 matrices, odd K ...): matrix by matrix.
+    require_quant_type("gemm_4bit_grouped", quant_type);
+    // Tried in this order (bnb_mi355x_gemm_4bit_grouped_route answers the same question from shapes alone):
+    //  * up to 8 members that the single-matrix entry point would ALL route to the streaming MFMA kernel (2 ... 16 rows,
+    //    csrc/gemm4_mfma.hip: sm_selected): ONE launch of that kernel over the members' rows - bit-identical to separate calls (the
+    //    same kernel family, and its summation order does not depend on the launch geometry);
+    //  * a group of 17 ... 64 rows that grouped_sm_passes accepts (above): ONE launch of that kernel as well, in row passes of 32 or
+    //    16 - NOT bit-identical to separate calls, whose route at that many rows is another family;
+    //  * otherwise, when no member is routed to an MFMA kernel and gemv_4bit_grouped takes the group (M <= 4, up to 8 matrices,
+    //    K % 32 == 0, single-phase rows): ONE launch of the streaming kernel, bit-identical to separate calls;
+    //  * everything else (mixed routes, more than 8 matrices, a group either launcher refuses): matrix by matrix.
     bool any_mfma = false, all_sm = count <= 8;
     for (int i = 0; i < count; ++i) {
         any_mfma = any_mfma || route_to_mfma(0, dtype, A, B[i], nullptr, M, N[i], K, blocksize,
@@ -432,22 +337,20 @@ void bnb_mi355x_gemm_4bit_grouped(int dtype, const void* A, int count, const uin
 int bnb_mi355x_gemm_4bit_grouped_route(int dtype, int count, const int* N, int M, int K, int blocksize) {
     // what bnb_mi355x_gemm_4bit_grouped does with such a group, assuming aligned pointers and members of one kind of statistics:
     // 2 = one launch of the streaming MFMA kernel, 1 = one launch of the streaming kernel, 0 = matrix by matrix
-    static const int dummy_aligned[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
-    const void* a = dummy_aligned;
     if (count <= 0 || count > 8 || M <= 0 || blocksize <= 0 || K % blocksize != 0)
         return 0;
     bool any_mfma = false, all_sm = true;
     for (int i = 0; i < count; ++i) {
-        any_mfma = any_mfma || route_to_mfma(0, dtype, a, reinterpret_cast<const uint8_t*>(a), nullptr, M, N[i], K, blocksize, true);
+        any_mfma = any_mfma || route_to_mfma(0, dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N[i], K, blocksize, true);
         all_sm = all_sm && gemm_4bit_sm_routes(dtype, M, N[i], K, blocksize) &&
-                 gemm_4bit_sm_supported(dtype, a, reinterpret_cast<const uint8_t*>(a), nullptr, M, N[i], K, blocksize);
+                 gemm_4bit_sm_supported(dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N[i], K, blocksize);
     }
     if (all_sm)
         return 2;
     if (grouped_sm_passes(dtype, count, N, M, K, blocksize)) {
         bool ok = true;
         for (int i = 0; i < count; ++i)
-            ok = ok && gemm_4bit_sm_supported(dtype, a, reinterpret_cast<const uint8_t*>(a), nullptr, M, N[i], K, blocksize);
+            ok = ok && gemm_4bit_sm_supported(dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N[i], K, blocksize);
         if (ok)
             return 2;
     }
@@ -458,9 +361,7 @@ int bnb_mi355x_gemm_4bit_grouped_route(int dtype, int count, const int* N, int M
 }
 size_t bnb_mi355x_gemm_4bit_workspace_bytes(int kernel, int dtype, int M, int N, int K, int blocksize) {
     // alignment of A/B is unknown here; assume the aligned (fast) case, an unused workspace is harmless
-    static const int dummy_aligned[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
-    const void* a = dummy_aligned;
-    if (!route_to_mfma(kernel, dtype, a, reinterpret_cast<const uint8_t*>(a), nullptr, M, N, K, blocksize, true))
+    if (!route_to_mfma(kernel, dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N, K, blocksize, true))
         return 0;
     return gemm_4bit_mfma_workspace_bytes(M, N, K, blocksize);
 }
@@ -491,10 +392,7 @@ int bnb_mi355x_gemm_4bit_experts_ffn_supported(int dtype, int E, int N, int K, i
 // ------------------------------------------------------------------ gated gemm_4bit (dense FFN: silu(gate) * up as the epilogue)
 void bnb_mi355x_gemm_4bit_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N,
                                 int K, int blocksize, int quant_type, bnb_stream_t s) {
-    if (quant_type != kFP4 && quant_type != kNF4) {
-        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_gated: quant_type must be 1 (FP4) or 2 (NF4), got %d\n", quant_type);
-        exit(1);
-    }
+    require_quant_type("gemm_4bit_gated", quant_type);
     const int family = gated_family(dtype, A, B, absmax, M, N, K, blocksize);
     const bool ok = family == kKernelSm       ? gemm_4bit_sm_gated(dtype, A, B, absmax, out, bias, M, N, K, blocksize, quant_type, S(s))
                     : family == kKernelStream ? gemv_4bit_stream_gated(dtype, A, B, absmax, out, bias, M, N, K, blocksize, quant_type, S(s))
@@ -507,21 +405,14 @@ void bnb_mi355x_gemm_4bit_gated(int dtype, const void* A, const uint8_t* B, cons
 }
 int bnb_mi355x_gemm_4bit_gated_supported(int dtype, int M, int N, int K, int blocksize) {
     // (alignment of A / B / absmax is unknown here; the aligned case is assumed, as in the route query)
-    static const int dummy_aligned[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
-    return gated_family(dtype, dummy_aligned, reinterpret_cast<const uint8_t*>(dummy_aligned), reinterpret_cast<const float*>(dummy_aligned), M, N, K,
-                        blocksize) != kKernelNone
-               ? 1
-               : 0;
+    return gated_family(dtype, kAlignedDummy, kAlignedDummy8, reinterpret_cast<const float*>(kAlignedDummy), M, N, K, blocksize) != kKernelNone ? 1 : 0;
 }
 
 // ------------------------------------------------------------------ LoRA gemm_4bit (the adapter term as the decode kernels' epilogue)
 void bnb_mi355x_gemm_4bit_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit,
                                const float* absmax_code, const float* absmax_offset, void* out, const void* bias, const void* lora_t,
                                const void* lora_b, float scaling, int r, int M, int N, int K, int blocksize, int quant_type, bnb_stream_t s) {
-    if (quant_type != kFP4 && quant_type != kNF4) {
-        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_lora: quant_type must be 1 (FP4) or 2 (NF4), got %d\n", quant_type);
-        exit(1);
-    }
+    require_quant_type("gemm_4bit_lora", quant_type);
     const int family = lora_family(dtype, A, B, absmax, absmax_8bit, lora_t, lora_b, M, N, K, blocksize, r);
     const bool ok = family == kKernelSm ? gemm_4bit_sm_lora(dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, lora_t, lora_b, scaling, r,
                                                             M, N, K, blocksize, quant_type, S(s))
@@ -536,10 +427,8 @@ void bnb_mi355x_gemm_4bit_lora(int dtype, const void* A, const uint8_t* B, const
 }
 int bnb_mi355x_gemm_4bit_lora_supported(int dtype, int M, int N, int K, int blocksize, int nested, int r) {
     // (alignment is unknown here; the aligned case is assumed, as in the route query)
-    static const int dummy_aligned[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
-    const uint8_t* const d8 = reinterpret_cast<const uint8_t*>(dummy_aligned);
-    return lora_family(dtype, dummy_aligned, d8, reinterpret_cast<const float*>(dummy_aligned), nested ? d8 : nullptr, dummy_aligned, dummy_aligned, M, N, K,
-                       blocksize, r) != kKernelNone
+    return lora_family(dtype, kAlignedDummy, kAlignedDummy8, reinterpret_cast<const float*>(kAlignedDummy), nested ? kAlignedDummy8 : nullptr, kAlignedDummy,
+                       kAlignedDummy, M, N, K, blocksize, r) != kKernelNone
                ? 1
                : 0;
 }
@@ -549,10 +438,7 @@ void bnb_mi355x_gemm_4bit_lora_ids(int dtype, const void* A, const uint8_t* B, c
                                    const float* absmax_code, const float* absmax_offset, void* out, const void* bias, const void* lora_t,
                                    const void* lora_b, const float* scalings, const void* ids, int index_bytes, int A_n, int r, int M, int N, int K,
                                    int blocksize, int quant_type, bnb_stream_t s) {
-    if (quant_type != kFP4 && quant_type != kNF4) {
-        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_lora_ids: quant_type must be 1 (FP4) or 2 (NF4), got %d\n", quant_type);
-        exit(1);
-    }
+    require_quant_type("gemm_4bit_lora_ids", quant_type);
     const int family = lora_family(dtype, A, B, absmax, absmax_8bit, lora_t, lora_b, M, N, K, blocksize, r);
     const bool ok = family == kKernelSm ? gemm_4bit_sm_lora_ids(dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, lora_t, lora_b,
                                                                 scalings, ids, index_bytes, A_n, r, M, N, K, blocksize, quant_type, S(s))
@@ -636,10 +522,7 @@ int bnb_mi355x_gemv_4bit_peer(void* const* bufs, void* epoch_word, int world, in
                               const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, const void* bias,
                               void* out_local, int ns, int K, int blocksize, int quant_type, int mode, long max_values, int wg_limit,
                               int epoch_offset, bnb_stream_t s) {
-    if (quant_type != kFP4 && quant_type != kNF4) {
-        fprintf(stderr, "bitsandbytes_amd: gemv_4bit_peer: quant_type must be 1 (FP4) or 2 (NF4), got %d\n", quant_type);
-        exit(1);
-    }
+    require_quant_type("gemv_4bit_peer", quant_type);
     return gemv_4bit_peer(bufs, epoch_word, world, rank, dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, bias, out_local, ns, K,
                           blocksize, quant_type, mode, max_values, wg_limit, static_cast<uint32_t>(epoch_offset), peer_chain_spin_bound(), S(s))
                ? 1
@@ -656,24 +539,19 @@ void bnb_mi355x_peer_chain_read(void* const* bufs, void* epoch_word, int world, 
 }
 int bnb_mi355x_gemm_4bit_route(int kernel, int dtype, int M, int N, int K, int blocksize) {
     // (alignment of A / B is unknown here; the aligned - fast - case is assumed, as in the workspace query)
-    static const int dummy_aligned[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
-    return route_to_mfma(kernel, dtype, dummy_aligned, reinterpret_cast<const uint8_t*>(dummy_aligned), nullptr, M, N, K, blocksize, true) ? 1 : 0;
+    return route_to_mfma(kernel, dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N, K, blocksize, true) ? 1 : 0;
 }
 void bnb_mi355x_gemm_4bit_grad_input(int dtype, const void* grad_out, const uint8_t* B, const float* absmax,
                                      const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, void* grad_A,
                                      int M, int N, int K, int blocksize, int quant_type, void* workspace, size_t workspace_bytes,
                                      bnb_stream_t s) {
-    if (quant_type != kFP4 && quant_type != kNF4) {
-        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_grad_input: quant_type must be 1 (FP4) or 2 (NF4), got %d\n", quant_type);
-        exit(1);
-    }
+    require_quant_type("gemm_4bit_grad_input", quant_type);
     gemm_4bit_grad_input(dtype, grad_out, B, absmax, absmax_8bit, absmax_code, absmax_offset, grad_A, M, N, K, blocksize,
                          quant_type, workspace, workspace_bytes, S(s));
 }
 size_t bnb_mi355x_gemm_4bit_grad_input_workspace_bytes(int M, int N, int K) { return gemm_4bit_grad_input_workspace_bytes(M, N, K); }
 int bnb_mi355x_gemm_4bit_grad_input_supported(int dtype, int M, int N, int K, int blocksize) {
-    static const int dummy_aligned[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
-    return gemm_4bit_grad_input_supported(dtype, dummy_aligned, reinterpret_cast<const uint8_t*>(dummy_aligned), M, N, K, blocksize) ? 1 : 0;
+    return gemm_4bit_grad_input_supported(dtype, kAlignedDummy, kAlignedDummy8, M, N, K, blocksize) ? 1 : 0;
 }
 void bnb_mi355x_set_tuning(int reserved0, int reserved1, int mfma_knob0, int mfma_knob1) {
     quantize_8bit_set_variant(reserved0); // 1 / 2: force the cell-table / byte-table 8-bit encoder, anything else: by size

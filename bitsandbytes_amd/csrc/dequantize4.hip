@@ -11,7 +11,7 @@
 // keep several loads in flight. The 16-entry code table sits in LDS, one entry per bank, so a
 // gather by nibble is conflict-free by construction (equal nibbles broadcast, different nibbles
 // hit different banks).
-#include "bnb_common.h"
+#include "bnb_launchers.h"
 
 namespace bnb {
 

@@ -27,7 +27,7 @@
 //     the gate row and 2 c + 1 the up row of the tile's output column c, so only the local -> global row map (wave-uniform
 //     scalars) and the epilogue differ; every row's sum is formed exactly as in the plain form.
 //   * row scale: out[p, n] = T((acc + bias) * w[p]), w fp32 or T as it is in memory (the routing weight of the down projection).
-#include "bnb_common.h"
+#include "bnb_launchers.h"
 
 namespace bnb {
 

@@ -28,18 +28,11 @@
 //  * the wavefronts of a workgroup take different n blocks of the workgroup's N slice; their partial tiles are added through
 //    LDS in a fixed order at the end. N slices across workgroups fill the chip; fp32 slabs are added in slice order by
 //    gemm4_finalize: bit-reproducible.
-#include "bnb_common.h"
+#include "bnb_launchers.h"
 
 #include <atomic>
 
 namespace bnb {
-
-#ifdef BNB_PROFILING
-extern unsigned long long* g_dbg_buf;
-#endif
-
-// gemm4_mfma.hip
-void gemm_4bit_finalize(int dtype, const float* ws, const void* bias, void* out, int M, int N, int kslices, hipStream_t stream);
 
 namespace {
 

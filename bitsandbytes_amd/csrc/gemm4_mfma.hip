@@ -25,16 +25,13 @@
 // (weights straight to registers in fragment-shaped 32-byte pieces; a 16-column LDS-DMA kernel; a 128-column two-stage tile
 // with workgroup barriers; the same with a 4-deep ring) were measured and retired - what each taught is in DESIGN.md and their
 // sweep records in profiles/r1_sweep_mfma_variants.txt, profiles/r2_mfma_ab.txt.
-#include "bnb_common.h"
+#include "bnb_launchers.h"
 
 #include <mutex>
 #include <unordered_map>
 
 namespace bnb {
 
-#ifdef BNB_PROFILING
-extern unsigned long long* g_dbg_buf; // c_api.hip (profiling builds only)
-#endif
 // Sweep / test overrides (bnb_mi355x_set_tuning). Atomics, and every call takes ONE snapshot of them: a sweep thread can
 // never corrupt a concurrent launch, it can only change which (always correct) geometry that launch uses.
 thread_local TlsKnob g_mfma_knob0{0}; // reserved (was: A-image variants of the retired LDS-DMA kernel)
@@ -741,41 +738,6 @@ template <typename T> void dispatch_mfma(GemmArgs& p, float* ws, size_t ws_bytes
 }
 
 } // namespace
-
-// gemm4_mfma_rt.hip (the register-transposed kernel for small batches on small / medium matrices)
-bool gemm_4bit_rt_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize);
-size_t gemm_4bit_rt_workspace_bytes(int M, int N, int K, int force_ks);
-bool gemm_4bit_rt_serves(const float* absmax, const uint8_t* absmax8, int blocksize);
-void gemm_4bit_rt(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
-                  const float* absmax_code, const float* absmax_offset, void* out, const void* bias, int M, int N, int K,
-                  int blocksize, int quant_type, void* workspace, size_t workspace_bytes, int force_ks, int force_waves,
-                  int variant, hipStream_t stream);
-
-// gemm4_mfma_kq.hip (the K-quarter kernel: 32x32x16 MFMA, shares of a chunk copied to registers, 17 ... 64-row batches)
-bool gemm_4bit_kq_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize);
-size_t gemm_4bit_kq_workspace_bytes(int M, int N, int K, int force_ks);
-bool gemm_4bit_kq_serves(const float* absmax, const uint8_t* absmax8, int blocksize, int K);
-void gemm_4bit_kq(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
-                  const float* absmax_code, const float* absmax_offset, void* out, const void* bias, int M, int N, int K,
-                  int blocksize, int quant_type, void* workspace, size_t workspace_bytes, int force_ks, int ablate, hipStream_t stream);
-
-// gemv4_stream.hip (what a call outside every MFMA kernel's preconditions runs)
-void gemv_4bit_stream(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
-                      const float* absmax_code, const float* absmax_offset, const float* code16, void* out,
-                      const void* bias, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream);
-
-// gemm4_mfma_sm.hip (the streaming MFMA kernel: one persistent workgroup per CU, activations once per CU; 2 ... 16 rows)
-bool gemm_4bit_sm_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize);
-bool gemm_4bit_sm_serves(const float* absmax, const uint8_t* absmax8, int blocksize);
-void gemm_4bit_sm(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
-                  const float* absmax_code, const float* absmax_offset, void* out, const void* bias, int M, int N, int K,
-                  int blocksize, int quant_type, int variant, hipStream_t stream);
-
-// gemm4_mfma_tall.hip (128 x 128 tiles, pre-scaled operand decoded once per 128 rows: tall batches)
-bool gemm_4bit_tall_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize);
-void gemm_4bit_tall(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
-                    const float* absmax_offset, void* out, const void* bias, int M, int N, int K, int blocksize, int quant_type,
-                    int ablate, hipStream_t stream);
 
 // shared with gemm4_mfma_rt.hip: the slab finalize launch and the library-owned workspace
 void gemm_4bit_finalize(int dtype, const float* ws, const void* bias, void* out, int M, int N, int kslices, hipStream_t stream) {

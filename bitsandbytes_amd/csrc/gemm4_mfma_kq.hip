@@ -24,19 +24,11 @@
 //    wavefronts issue the same number of DMA instructions per chunk, interleaved with their MFMAs; waits are exact counts.
 //  * the four K quarters of a column group are added once, after the loop, in a fixed order through the (then free) LDS;
 //    K slices across workgroups write fp32 slabs that gemm4_finalize adds in slice order: bit-reproducible.
-#include "bnb_common.h"
+#include "bnb_launchers.h"
 
 #include <type_traits>
 
 namespace bnb {
-
-#ifdef BNB_PROFILING
-extern unsigned long long* g_dbg_buf;
-#endif
-
-// gemm4_mfma.hip
-void gemm_4bit_finalize(int dtype, const float* ws, const void* bias, void* out, int M, int N, int kslices, hipStream_t stream);
-float* gemm_4bit_internal_workspace(size_t bytes, hipStream_t stream);
 
 namespace {
 

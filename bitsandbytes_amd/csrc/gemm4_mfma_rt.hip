@@ -31,17 +31,9 @@
 //
 // Results are bit-reproducible: partial tiles are combined in wavefront order, K slices (only when N / 16 workgroups would
 // leave most of the chip idle) through fp32 slabs added in slice order by gemm4_finalize (gemm4_mfma.hip).
-#include "bnb_common.h"
+#include "bnb_launchers.h"
 
 namespace bnb {
-
-#ifdef BNB_PROFILING
-extern unsigned long long* g_dbg_buf;
-#endif
-
-// gemm4_mfma.hip
-void gemm_4bit_finalize(int dtype, const float* ws, const void* bias, void* out, int M, int N, int kslices, hipStream_t stream);
-float* gemm_4bit_internal_workspace(size_t bytes, hipStream_t stream);
 
 namespace {
 

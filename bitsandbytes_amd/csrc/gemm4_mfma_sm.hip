@@ -33,13 +33,9 @@
 //    statistics are reconstructed in-kernel with the two roundings of the host-side sequence (bnb_common.h nested_scale).
 //  * The wavefronts' partial tiles are combined once, through LDS, in FIXED order ((w0 + w1 + w2 + w3) + ... by four
 //    threads per output, then two DPP adds): bit-reproducible, no atomics, no second launch, no workspace.
-#include "bnb_common.h"
+#include "bnb_launchers.h"
 
 namespace bnb {
-
-#ifdef BNB_PROFILING
-extern unsigned long long* g_dbg_buf; // c_api.hip (profiling builds only)
-#endif
 
 namespace {
 
@@ -789,10 +785,19 @@ SmPlan sm_plan(int M, int N, bool gated = false) {
     return pl;
 }
 
+// The kernel's positional arguments: constant from the entry point down to the launch.
+struct SmCall {
+    const void* A;
+    const uint8_t* B;
+    const float* absmax;
+    const uint8_t* absmax8;
+    const float* code2;
+    int M, N, K, geom;
+};
+
 template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false, bool GATED = false, bool LORA = false,
           bool IDS = false>
-void sm_launch_one(const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* code2, int M, int N, int K, int geom,
-                   const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
+void sm_launch_one(const SmCall& c, const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
     constexpr int V = (ROWS < 16 && WAVES == 8) ? 2 : 1; // (accumulator sets per tile: the kernel's V)
     constexpr int RB = ROWS == 32 ? 2 : 1, SROWS = ROWS == 32 ? 16 : ROWS;
     constexpr size_t region = (SROWS * 512 + kSmScratch) > V * TT * RB * 1024 ? (SROWS * 512 + kSmScratch) : V * TT * RB * 1024;
@@ -800,92 +805,104 @@ void sm_launch_one(const void* A, const uint8_t* B, const float* absmax, const u
     auto kern = gemm4_mfma_sm_kernel<T, ROWS, WAVES, TT, NESTED, SINGLE, ORDER, GROUPED, GATED, LORA, IDS>;
     static LdsLimit lim;
     ensure_dynamic_lds(lim, reinterpret_cast<const void*>(kern), lds);
-    hipLaunchKernelGGL(kern, dim3(pl.grid_x, (M + 16 * RB - 1) / (16 * RB)), dim3(WAVES * 64), lds, stream, A, B, absmax, absmax8, code2, M, N, K, geom, a);
+    hipLaunchKernelGGL(kern, dim3(pl.grid_x, (c.M + 16 * RB - 1) / (16 * RB)), dim3(WAVES * 64), lds, stream, c.A, c.B, c.absmax, c.absmax8, c.code2, c.M, c.N,
+                       c.K, c.geom, a);
 }
 
-template <typename T, int ROWS, int WAVES, int TT>
-void sm_launch_kind(const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* code2, int M, int N, int K, int geom,
-                    const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
-    const bool nested = absmax8 != nullptr;
-    if constexpr (ROWS != 32) {
-        if (pl.gated) { // (fp32 absmax, one matrix: gemm_4bit_sm_gated checks)
-            if constexpr (TT == 1) {
-                if ((K + kSmChunk - 1) / kSmChunk <= WAVES)
-                    return sm_launch_one<T, ROWS, WAVES, 1, false, true, 0, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+// one item per wavefront at most: such a launch of ONE tile in row passes of 16 at most (TT == 1, ROWS != 32) runs the instance without the ring
+bool sm_single_item(int K, int waves) { return (K + kSmChunk - 1) / kSmChunk <= waves; }
+
+// The instance of ONE epilogue form (plain, GATED, LORA, LORA + IDS) for a call: single-item or ring, nested statistics or fp32
+// absmax - the same question with the same answer for every form, so a fused call runs the skeleton of the plain call on the same
+// matrix and rows. (GATED: fp32 absmax only, gemm_4bit_sm_gated checks; no nested gated instance exists.)
+template <typename T, int ROWS, int WAVES, int TT, bool GATED, bool LORA, bool IDS>
+void sm_launch_form(const SmCall& c, const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
+    const bool nested = !GATED && c.absmax8 != nullptr;
+    if constexpr (TT == 1 && ROWS != 32) {
+        if (sm_single_item(c.K, WAVES)) {
+            if constexpr (!GATED) {
+                if (nested)
+                    return sm_launch_one<T, ROWS, WAVES, 1, true, true, 0, false, GATED, LORA, IDS>(c, pl, a, stream);
             }
-            return sm_launch_one<T, ROWS, WAVES, TT, false, false, 0, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+            return sm_launch_one<T, ROWS, WAVES, 1, false, true, 0, false, GATED, LORA, IDS>(c, pl, a, stream);
         }
     }
-    if constexpr (ROWS != 32) {
-        if (pl.lora && pl.lora_ids) { // (the LoRA instances' skeletons, mixed-adapter epilogue)
-            if constexpr (TT == 1) {
-                if ((K + kSmChunk - 1) / kSmChunk <= WAVES) {
-                    if (nested)
-                        return sm_launch_one<T, ROWS, WAVES, 1, true, true, 0, false, false, true, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-                    return sm_launch_one<T, ROWS, WAVES, 1, false, true, 0, false, false, true, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-                }
-            }
-            if (nested)
-                return sm_launch_one<T, ROWS, WAVES, TT, true, false, 0, false, false, true, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-            return sm_launch_one<T, ROWS, WAVES, TT, false, false, 0, false, false, true, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-        }
-    }
-    if constexpr (ROWS != 32) {
-        if (pl.lora) { // (one matrix, both kinds of statistics: gemm_4bit_sm_lora checks)
-            if constexpr (TT == 1) {
-                if ((K + kSmChunk - 1) / kSmChunk <= WAVES) {
-                    if (nested)
-                        return sm_launch_one<T, ROWS, WAVES, 1, true, true, 0, false, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-                    return sm_launch_one<T, ROWS, WAVES, 1, false, true, 0, false, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-                }
-            }
-            if (nested)
-                return sm_launch_one<T, ROWS, WAVES, TT, true, false, 0, false, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-            return sm_launch_one<T, ROWS, WAVES, TT, false, false, 0, false, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-        }
-    }
-    if (pl.grouped) { // (ring instances only)
+    if constexpr (!GATED) {
         if (nested)
-            return sm_launch_one<T, ROWS, WAVES, TT, true, false, 0, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-        return sm_launch_one<T, ROWS, WAVES, TT, false, false, 0, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+            return sm_launch_one<T, ROWS, WAVES, TT, true, false, 0, false, GATED, LORA, IDS>(c, pl, a, stream);
+    }
+    return sm_launch_one<T, ROWS, WAVES, TT, false, false, 0, false, GATED, LORA, IDS>(c, pl, a, stream);
+}
+
+template <typename T, int ROWS, int WAVES, int TT> void sm_launch_kind(const SmCall& c, const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
+    if constexpr (ROWS != 32) { // (the fused forms' entry points refuse row passes of 32)
+        if (pl.gated)
+            return sm_launch_form<T, ROWS, WAVES, TT, true, false, false>(c, pl, a, stream);
+        if (pl.lora && pl.lora_ids)
+            return sm_launch_form<T, ROWS, WAVES, TT, false, true, true>(c, pl, a, stream);
+        if (pl.lora)
+            return sm_launch_form<T, ROWS, WAVES, TT, false, true, false>(c, pl, a, stream);
+    }
+    // what only the plain call has: grouped launches (ring instances only), the ORDER experiment (fp32 absmax, single item), ROWS = 32
+    if (pl.grouped) {
+        if (c.absmax8 != nullptr)
+            return sm_launch_one<T, ROWS, WAVES, TT, true, false, 0, true>(c, pl, a, stream);
+        return sm_launch_one<T, ROWS, WAVES, TT, false, false, 0, true>(c, pl, a, stream);
     }
     if constexpr (TT == 1 && ROWS != 32) {
-        if ((K + kSmChunk - 1) / kSmChunk <= WAVES) { // one item per wavefront at most: no ring
-            if (nested)
-                return sm_launch_one<T, ROWS, WAVES, 1, true, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-            if (pl.variant & 4)
-                return sm_launch_one<T, ROWS, WAVES, 1, false, true, 1>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-            return sm_launch_one<T, ROWS, WAVES, 1, false, true>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-        }
+        if ((pl.variant & 4) && c.absmax8 == nullptr && sm_single_item(c.K, WAVES))
+            return sm_launch_one<T, ROWS, WAVES, 1, false, true, 1>(c, pl, a, stream);
     }
-    if (nested)
-        return sm_launch_one<T, ROWS, WAVES, TT, true, false>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-    return sm_launch_one<T, ROWS, WAVES, TT, false, false>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+    sm_launch_form<T, ROWS, WAVES, TT, false, false, false>(c, pl, a, stream);
 }
 
 // 16 wavefronts per workgroup, 8 where 128 registers (three or four tiles' accumulators and item bodies beside the fragments and the ring) or the LDS
 // (8-KiB staging areas at ROWS = 16) do not allow them
-template <typename T, int ROWS>
-void sm_launch_tt(const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* code2, int M, int N, int K, int geom,
-                  const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
+template <typename T, int ROWS> void sm_launch_tt(const SmCall& c, const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
     constexpr int W = ROWS >= 16 ? 8 : 16;
     switch (pl.tt) {
-    case 1: return sm_launch_kind<T, ROWS, W, 1>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-    case 2: return sm_launch_kind<T, ROWS, W, 2>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-    case 3: return sm_launch_kind<T, ROWS, 8, 3>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-    default: return sm_launch_kind<T, ROWS, 8, 4>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+    case 1: return sm_launch_kind<T, ROWS, W, 1>(c, pl, a, stream);
+    case 2: return sm_launch_kind<T, ROWS, W, 2>(c, pl, a, stream);
+    case 3: return sm_launch_kind<T, ROWS, 8, 3>(c, pl, a, stream);
+    default: return sm_launch_kind<T, ROWS, 8, 4>(c, pl, a, stream);
     }
 }
 
-template <typename T>
-void sm_launch_rows(const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* code2, int M, int N, int K, int geom,
-                    const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
+template <typename T> void sm_launch_rows(const SmCall& c, const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
     switch (pl.rows) {
-    case 4: return sm_launch_tt<T, 4>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-    case 8: return sm_launch_tt<T, 8>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-    case 16: return sm_launch_tt<T, 16>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
-    default: return sm_launch_tt<T, 32>(A, B, absmax, absmax8, code2, M, N, K, geom, pl, a, stream);
+    case 4: return sm_launch_tt<T, 4>(c, pl, a, stream);
+    case 8: return sm_launch_tt<T, 8>(c, pl, a, stream);
+    case 16: return sm_launch_tt<T, 16>(c, pl, a, stream);
+    default: return sm_launch_tt<T, 32>(c, pl, a, stream);
     }
+}
+
+// dtype: 1 = f16, 2 = bf16
+void sm_launch(int dtype, const SmCall& c, const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
+    if (dtype == 2)
+        sm_launch_rows<bf16>(c, pl, a, stream);
+    else
+        sm_launch_rows<f16>(c, pl, a, stream);
+    BNB_CHECK_LAUNCH();
+}
+
+// the kernel's geometry word: rows per workgroup, the code table, the blocksize and (grouped launches) the member count
+int sm_geom(const SmPlan& pl, int quant_type, int blocksize, int count = 0) {
+    return pl.R | ((quant_type == kFP4) ? (1 << 16) : 0) | (ilog2(blocksize) << 20) | (count << 25);
+}
+
+// the fields every form fills; dbg (profiling builds): the stamp buffer for the plain and the grouped call, nullptr for every other form
+SmArgs sm_args(const float* absmax_offset, void* out, const void* bias, unsigned long long* dbg) {
+    SmArgs a{};
+#ifdef BNB_PROFILING
+    a.dbg = dbg;
+#else
+    (void)dbg;
+#endif
+    a.absmax_offset = absmax_offset;
+    a.out = out;
+    a.bias = bias;
+    return a;
 }
 
 } // namespace
@@ -914,19 +931,8 @@ void gemm_4bit_sm(int dtype, const void* A, const uint8_t* B, const float* absma
     pl.variant = variant;
     if ((variant & 16) && pl.rows == 32) // (A/B: row passes of 16, as before the 32-row instances)
         pl.rows = 16;
-    SmArgs a{};
-#ifdef BNB_PROFILING
-    a.dbg = g_dbg_buf;
-#endif
-    a.absmax_offset = absmax_offset;
-    a.out = out;
-    a.bias = bias;
-    const int geom = pl.R | ((quant_type == kFP4) ? (1 << 16) : 0) | (ilog2(blocksize) << 20);
-    if (dtype == 2)
-        sm_launch_rows<bf16>(A, B, absmax, absmax8, absmax_code, M, N, K, geom, pl, a, stream);
-    else
-        sm_launch_rows<f16>(A, B, absmax, absmax8, absmax_code, M, N, K, geom, pl, a, stream);
-    BNB_CHECK_LAUNCH();
+    sm_launch(dtype, SmCall{A, B, absmax, absmax8, absmax_code, M, N, K, sm_geom(pl, quant_type, blocksize)}, pl,
+              sm_args(absmax_offset, out, bias, stamp_buffer()), stream);
 }
 
 // Gated form (see the kernel's GATED): B [N = 2 F, K] interleaved, bias [N], out [M, F]. 2 <= ... M <= 16 (the 4-, 8- and 16-row
@@ -941,19 +947,7 @@ bool gemm_4bit_sm_gated(int dtype, const void* A, const uint8_t* B, const float*
     const SmPlan pl = sm_plan(M, N, true);
     if (pl.rows > 16 || (pl.R & 1) || pl.tt > kSmMaxTiles)
         return false;
-    SmArgs a{};
-#ifdef BNB_PROFILING
-    a.dbg = nullptr;
-#endif
-    a.absmax_offset = nullptr;
-    a.out = out;
-    a.bias = bias;
-    const int geom = pl.R | ((quant_type == kFP4) ? (1 << 16) : 0) | (ilog2(blocksize) << 20);
-    if (dtype == 2)
-        sm_launch_rows<bf16>(A, B, absmax, nullptr, nullptr, M, N, K, geom, pl, a, stream);
-    else
-        sm_launch_rows<f16>(A, B, absmax, nullptr, nullptr, M, N, K, geom, pl, a, stream);
-    BNB_CHECK_LAUNCH();
+    sm_launch(dtype, SmCall{A, B, absmax, nullptr, nullptr, M, N, K, sm_geom(pl, quant_type, blocksize)}, pl, sm_args(nullptr, out, bias, nullptr), stream);
     g_last_gemm_kernel = kKernelSm;
     return true;
 }
@@ -965,76 +959,47 @@ bool gemm_4bit_sm_lora_supported(int dtype, const void* A, const uint8_t* B, int
     return M <= 16 && r >= 8 && r <= 128 && (r % 8) == 0 && static_cast<long long>(N) * r < (1LL << 29) &&
            gemm_4bit_sm_supported(dtype, A, B, nullptr, M, N, K, blocksize);
 }
-bool gemm_4bit_sm_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
-                       const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r,
-                       int M, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
+// (both LoRA entry points; ids: the mixed-adapter block - see the kernel's IDS -, nullptr for the uniform call, whose `scaling` it replaces)
+static bool sm_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                    const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, const LoraIds* ids,
+                    int r, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
     if (!gemm_4bit_sm_lora_supported(dtype, A, B, M, N, K, blocksize, r) || !gemm_4bit_sm_serves(absmax, absmax8, blocksize) || !aligned_to(lora_t, 16) ||
-        !aligned_to(lora_b, 16) || (absmax8 != nullptr && (absmax_code == nullptr || absmax_offset == nullptr)))
+        !aligned_to(lora_b, 16) || (absmax8 != nullptr && (absmax_code == nullptr || absmax_offset == nullptr)) || (ids != nullptr && !ids->valid()))
         return false;
     SmPlan pl = sm_plan(M, N);
     if (pl.rows > 16 || pl.tt > kSmMaxTiles)
         return false;
     pl.lora = true;
-    SmArgs a{};
-#ifdef BNB_PROFILING
-    a.dbg = nullptr;
-#endif
-    a.absmax_offset = absmax_offset;
-    a.out = out;
-    a.bias = bias;
+    pl.lora_ids = ids != nullptr;
+    SmArgs a = sm_args(absmax_offset, out, bias, nullptr);
     a.lora_t = lora_t;
     a.lora_b = lora_b;
     a.lora_r = r;
-    a.lora_scaling = scaling;
-    const int geom = pl.R | ((quant_type == kFP4) ? (1 << 16) : 0) | (ilog2(blocksize) << 20);
-    if (dtype == 2)
-        sm_launch_rows<bf16>(A, B, absmax, absmax8, absmax_code, M, N, K, geom, pl, a, stream);
-    else
-        sm_launch_rows<f16>(A, B, absmax, absmax8, absmax_code, M, N, K, geom, pl, a, stream);
-    BNB_CHECK_LAUNCH();
+    a.lora_scaling = ids ? 0.0f : scaling;
+    if (ids) {
+        a.lora_ids = ids->ids;
+        a.lora_scalings = ids->scalings;
+        a.lora_an = ids->A_n;
+        a.lora_idx64 = ids->index_bytes == 8 ? 1 : 0;
+    }
+    sm_launch(dtype, SmCall{A, B, absmax, absmax8, absmax_code, M, N, K, sm_geom(pl, quant_type, blocksize)}, pl, a, stream);
     g_last_gemm_kernel = kKernelSm;
     return true;
 }
-
-// Mixed-adapter LoRA form (see the kernel's IDS): the LoRA form's plan and instance skeleton; lora_b [A_n, N, r], scalings [A_n] fp32
-// and ids [M] (int32 / int64) on the device. The kernel rebases lora_b's buffer resource per adapter with 64-bit arithmetic, so the
-// preconditions carry no bound on A_n N r. false - nothing launched - outside the preconditions.
+bool gemm_4bit_sm_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                       const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r,
+                       int M, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
+    return sm_lora(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, lora_t, lora_b, scaling, nullptr, r, M, N, K, blocksize, quant_type,
+                   stream);
+}
+// Mixed-adapter LoRA form: the LoRA form's plan and instance skeleton. The kernel rebases lora_b's buffer resource per adapter with
+// 64-bit arithmetic, so the preconditions carry no bound on A_n N r.
 bool gemm_4bit_sm_lora_ids(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
                            const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, const float* scalings,
                            const void* ids, int index_bytes, int A_n, int r, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
-    if (!gemm_4bit_sm_lora_supported(dtype, A, B, M, N, K, blocksize, r) || !gemm_4bit_sm_serves(absmax, absmax8, blocksize) || !aligned_to(lora_t, 16) ||
-        !aligned_to(lora_b, 16) || (absmax8 != nullptr && (absmax_code == nullptr || absmax_offset == nullptr)) || A_n < 1 || A_n > 64 ||
-        (index_bytes != 4 && index_bytes != 8) || ids == nullptr || scalings == nullptr || !aligned_to(ids, static_cast<size_t>(index_bytes)) ||
-        !aligned_to(scalings, 4))
-        return false;
-    SmPlan pl = sm_plan(M, N);
-    if (pl.rows > 16 || pl.tt > kSmMaxTiles)
-        return false;
-    pl.lora = true;
-    pl.lora_ids = true;
-    SmArgs a{};
-#ifdef BNB_PROFILING
-    a.dbg = nullptr;
-#endif
-    a.absmax_offset = absmax_offset;
-    a.out = out;
-    a.bias = bias;
-    a.lora_t = lora_t;
-    a.lora_b = lora_b;
-    a.lora_r = r;
-    a.lora_scaling = 0.0f;
-    a.lora_ids = ids;
-    a.lora_scalings = scalings;
-    a.lora_an = A_n;
-    a.lora_idx64 = index_bytes == 8 ? 1 : 0;
-    const int geom = pl.R | ((quant_type == kFP4) ? (1 << 16) : 0) | (ilog2(blocksize) << 20);
-    if (dtype == 2)
-        sm_launch_rows<bf16>(A, B, absmax, absmax8, absmax_code, M, N, K, geom, pl, a, stream);
-    else
-        sm_launch_rows<f16>(A, B, absmax, absmax8, absmax_code, M, N, K, geom, pl, a, stream);
-    BNB_CHECK_LAUNCH();
-    g_last_gemm_kernel = kKernelSm;
-    return true;
+    const LoraIds block{scalings, ids, index_bytes, A_n};
+    return sm_lora(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, lora_t, lora_b, 0.0f, &block, r, M, N, K, blocksize, quant_type,
+                   stream);
 }
 
 // Several weight matrices that share the activations (Q/K/V, gate/up; reference: one gemm_4bit per Linear4bit, nn/modules.py:609-637)
@@ -1063,7 +1028,6 @@ bool gemm_4bit_sm_grouped(int dtype, const void* A, int count, const uint8_t* co
     SmPlan pl = sm_plan(M, static_cast<int>(total));
     // rows per workgroup: every member rounds its own share up - not more workgroups than the plan's whole rounds of the chip
     const long limit = static_cast<long>(pl.grid_x) > sm_cu_count() ? static_cast<long>(pl.grid_x) : sm_cu_count();
-    SmArgs a{};
     for (;; ++pl.R) {
         long blocks = 0;
         for (int i = 0; i < count; ++i)
@@ -1075,12 +1039,7 @@ bool gemm_4bit_sm_grouped(int dtype, const void* A, int count, const uint8_t* co
     }
     pl.tt = (pl.R + 15) / 16;
     pl.grouped = true;
-#ifdef BNB_PROFILING
-    a.dbg = g_dbg_buf;
-#endif
-    a.absmax_offset = nested ? absmax_offset[0] : nullptr;
-    a.out = out[0];
-    a.bias = bias ? bias[0] : nullptr;
+    SmArgs a = sm_args(nested ? absmax_offset[0] : nullptr, out[0], bias ? bias[0] : nullptr, stamp_buffer());
     a.start[0] = 0;
     for (int i = 0; i < kSmMaxGroup; ++i) {
         const int j = i < count ? i : 0;
@@ -1095,12 +1054,7 @@ bool gemm_4bit_sm_grouped(int dtype, const void* A, int count, const uint8_t* co
         a.gbias[i] = bias ? bias[j] : nullptr;
     }
     g_last_gemm_kernel = kKernelSm;
-    const int geom = pl.R | ((quant_type == kFP4) ? (1 << 16) : 0) | (ilog2(blocksize) << 20) | (count << 25);
-    if (dtype == 2)
-        sm_launch_rows<bf16>(A, B[0], absmax[0], a.gabsmax8[0], a.gcode2[0], M, N[0], K, geom, pl, a, stream);
-    else
-        sm_launch_rows<f16>(A, B[0], absmax[0], a.gabsmax8[0], a.gcode2[0], M, N[0], K, geom, pl, a, stream);
-    BNB_CHECK_LAUNCH();
+    sm_launch(dtype, SmCall{A, B[0], absmax[0], a.gabsmax8[0], a.gcode2[0], M, N[0], K, sm_geom(pl, quant_type, blocksize, count)}, pl, a, stream);
     return true;
 }
 

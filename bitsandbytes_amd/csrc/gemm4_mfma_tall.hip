@@ -23,7 +23,7 @@
 //  * one s_barrier per step.
 // Arithmetic = dequantize_4bit's (fp32 product rounded once to T) followed by a T x T -> fp32 matrix product: what the unfused
 // path (dequantize + library GEMM) computes, up to the order of the fp32 sums.
-#include "bnb_common.h"
+#include "bnb_launchers.h"
 
 namespace bnb {
 

@@ -31,15 +31,11 @@
 //
 // Grouped launches (bnb_mi355x_gemm_4bit_grouped): several weight matrices that share the activations (Q/K/V,
 // gate/up) are one launch over the concatenated row space - one boundary, one table build, one activation copy.
-#include "bnb_common.h"
+#include "bnb_launchers.h"
 
 #include <type_traits>
 
 namespace bnb {
-
-#ifdef BNB_PROFILING
-extern unsigned long long* g_dbg_buf; // c_api.hip (profiling builds)
-#endif
 
 namespace {
 
@@ -1225,6 +1221,64 @@ template <typename T, int MB, int WAVES, int FLAGS> void launch_tuned(const Stre
     launch_one<T, MB, WAVES, ring_depth(MB, WAVES), FLAGS | kNT>(a, stream);
 }
 
+// Which (MB, WAVES) M rows on K columns of tbytes-wide activations run: THE answer, for the plain call and for every fused form
+// of it, for the launch and for the host layer's queries. Rows of A held in registers per pass: 1, 2 or 4 (M = 3 runs the 4-row
+// instance, its fourth row a duplicate that is never stored); larger M - only reached for shapes the MFMA kernels do not take -
+// loops passes of 4 over grid.y. waves_knob: the `waves` tuning knob as the plain call honours it (8 = the 8-wavefront instances);
+// the fused forms pass 0 - they never honoured it.
+// It rests on ONE fact about make_geometry: SW, and hence P, depends only on K, mb, waves, tbytes and tune_sw - `fixed` and R are
+// computed after sw and never feed back into it - so rows_total, grouped and pairs need not be the caller's here.
+struct RowsWaves {
+    int mb, waves;
+};
+RowsWaves rows_waves(int M, int K, int tbytes, int waves_knob) {
+    // One row: 16 wavefronts (ring of 2) for every call. Round 2 routed long row lists (>= 64 items per CU, 8 % S == 0) to the 8-wavefront
+    // instance (ring of 4, decoded two stages at a time) on single timings in a fixed order - 8192^2 9.5 vs 10.7 us, 14336 x 4096 8.8
+    // vs 9.8. Round 5, round-robin medians on two boxes (profiles/r5_stream_prologue_ab.txt): 16 wavefronts are level or ahead on
+    // EVERY shape - 8192^2 8.54 / 8.81 vs 8.69 / 8.79 us, 11008 x 4096 6.42 / 6.56 vs 7.21 / 7.22, 14336 x 4096 7.54 / 7.81 vs 7.93 /
+    // 8.11, 28672 x 8192 22.8 / 23.8 vs 23.6 / 24.4, 4096 x 11008 7.44 / 7.41 vs 8.10 / 8.17 - and that harness showed what single
+    // timings carry: an 8 % first-measured penalty. The 8-wavefront instance stays for the tuning knob (A/B runs).
+    if (M == 1)
+        return {1, waves_knob == 8 ? 8 : 16};
+    // two rows still fit the 128-register budget of 16 wavefronts when the row is one phase long (measured: equal at
+    // 4096^2, 13 % faster at 8192^2 and 11008 x 4096); the multi-phase form spills there and keeps 8 wavefronts
+    if (M == 2)
+        return {2, (waves_knob != 8 && make_geometry(1, K, 2, 16, tbytes, false, 0, 0).P == 1) ? 16 : 8};
+    return {4, 8};
+}
+// ... as template arguments: f(MB, WAVES) as integral constants. KNOB: the caller honours the `waves` knob, which alone selects
+// 1 x 8 - no fused 1 x 8 instance exists.
+template <int V> using Const = std::integral_constant<int, V>;
+template <bool KNOB, typename F> void with_rows_waves(RowsWaves rw, F&& f) {
+    if constexpr (KNOB) {
+        if (rw.mb == 1 && rw.waves == 8)
+            return f(Const<1>{}, Const<8>{});
+    }
+    if (rw.mb == 1)
+        return f(Const<1>{}, Const<16>{});
+    if (rw.mb == 2 && rw.waves == 16)
+        return f(Const<2>{}, Const<16>{});
+    if (rw.mb == 2)
+        return f(Const<2>{}, Const<8>{});
+    f(Const<4>{}, Const<8>{});
+}
+// nested statistics x FP4 as template flags on top of BASE: f(FLAGS). NESTED_OK = false compiles the nested instances out (gated:
+// fp32 absmax only).
+template <int BASE, bool NESTED_OK, typename F> void with_quant_flags(bool nested, bool fp4, F&& f) {
+    if constexpr (NESTED_OK) {
+        if (nested && fp4)
+            return f(Const<BASE | kFp4 | kNested>{});
+        if (nested)
+            return f(Const<BASE | kNested>{});
+    }
+    if (fp4)
+        return f(Const<BASE | kFp4>{});
+    f(Const<BASE>{});
+}
+template <typename T> struct TypeTag {
+    using type = T;
+};
+
 template <typename T, int MB, int WAVES> void launch_flags(const StreamArgs& a, int quant_type, bool grouped, hipStream_t stream) {
     const bool nested = a.mat[0].absmax8 != nullptr;
     const bool fp4 = quant_type == kFP4;
@@ -1237,44 +1291,38 @@ template <typename T, int MB, int WAVES> void launch_flags(const StreamArgs& a, 
         fprintf(stderr, "bitsandbytes_amd: gemv_4bit: a caller-supplied code table needs fp32 absmax\n");
         exit(1);
     }
-    const int sel = (nested ? 1 : 0) | (fp4 ? 2 : 0) | (grouped ? 4 : 0);
-    switch (sel) {
-    case 0: return launch_tuned<T, MB, WAVES, 0>(a, stream);
-    case 1: return launch_tuned<T, MB, WAVES, kNested>(a, stream);
-    case 2: return launch_tuned<T, MB, WAVES, kFp4>(a, stream);
-    case 3: return launch_tuned<T, MB, WAVES, kFp4 | kNested>(a, stream);
-    case 4: return launch_tuned<T, MB, WAVES, kGrouped>(a, stream);
-    case 5: return launch_tuned<T, MB, WAVES, kGrouped | kNested>(a, stream);
-    case 6: return launch_tuned<T, MB, WAVES, kGrouped | kFp4>(a, stream);
-    default: return launch_tuned<T, MB, WAVES, kGrouped | kFp4 | kNested>(a, stream);
-    }
+    const auto go = [&](auto flags) { launch_tuned<T, MB, WAVES, decltype(flags)::value>(a, stream); };
+    if (grouped)
+        return with_quant_flags<kGrouped, true>(nested, fp4, go);
+    with_quant_flags<0, true>(nested, fp4, go);
 }
 
+// the plain call (single matrix or grouped): the one path that honours the `waves` tuning knob and has the sweep variants of launch_tuned
 template <typename T> void launch_mb(const StreamArgs& a, int quant_type, bool grouped, hipStream_t stream) {
-    // rows of A held in registers per pass: 1, 2 or 4 (M = 3 runs the 4-row instance, its fourth row a duplicate
-    // that is never stored); larger M - only reached for shapes the MFMA kernels do not take - loops passes of 4
-    // over grid.y. A caller-supplied code table (legacy op) always runs row by row.
-    if (a.M == 1 || a.code16 != nullptr) {
-        // 16 wavefronts (ring of 2) for every call. Round 2 routed long row lists (>= 64 items per CU, 8 % S == 0) to the 8-wavefront
-        // instance (ring of 4, decoded two stages at a time) on single timings in a fixed order - 8192^2 9.5 vs 10.7 us, 14336 x 4096 8.8
-        // vs 9.8. Round 5, round-robin medians on two boxes (profiles/r5_stream_prologue_ab.txt): 16 wavefronts are level or ahead on
-        // EVERY shape - 8192^2 8.54 / 8.81 vs 8.69 / 8.79 us, 11008 x 4096 6.42 / 6.56 vs 7.21 / 7.22, 14336 x 4096 7.54 / 7.81 vs 7.93 /
-        // 8.11, 28672 x 8192 22.8 / 23.8 vs 23.6 / 24.4, 4096 x 11008 7.44 / 7.41 vs 8.10 / 8.17 - and that harness showed what single
-        // timings carry: an 8 % first-measured penalty. The 8-wavefront instance stays for the tuning knob (A/B runs).
-        const bool eight = g_tune.waves.load(std::memory_order_relaxed) == 8;
-        if (eight)
-            return launch_flags<T, 1, 8>(a, quant_type, grouped, stream);
-        return launch_flags<T, 1, 16>(a, quant_type, grouped, stream);
-    }
-    if (a.M == 2) {
-        // two rows still fit the 128-register budget of 16 wavefronts when the row is one phase long (measured: equal at
-        // 4096^2, 13 % faster at 8192^2 and 11008 x 4096); the multi-phase form spills there and keeps 8 wavefronts
-        if (g_tune.waves.load(std::memory_order_relaxed) != 8 &&
-            make_geometry(a.rows_total, a.K, 2, 16, TypeInfo<T>::bytes, grouped, 0, 0).P == 1)
-            return launch_flags<T, 2, 16>(a, quant_type, grouped, stream);
-        return launch_flags<T, 2, 8>(a, quant_type, grouped, stream);
-    }
-    return launch_flags<T, 4, 8>(a, quant_type, grouped, stream);
+    // (a caller-supplied code table - legacy op - always runs row by row)
+    const RowsWaves rw = rows_waves(a.code16 != nullptr ? 1 : a.M, a.K, TypeInfo<T>::bytes, g_tune.waves.load(std::memory_order_relaxed));
+    with_rows_waves<true>(rw, [&](auto mb, auto waves) { launch_flags<T, decltype(mb)::value, decltype(waves)::value>(a, quant_type, grouped, stream); });
+}
+
+// A fused call (BASE = kNT | its epilogue's flags; 16-bit activations): the instance the plain call on the same matrix and rows
+// runs - rows_waves without the knob -, production ring, literal table, with the epilogue compiled in. That is what makes the fused
+// result the plain result plus the epilogue, bit for bit.
+template <int BASE, bool NESTED_OK> void launch_fused(int dtype, const StreamArgs& a, int quant_type, hipStream_t stream) {
+    const RowsWaves rw = rows_waves(a.M, a.K, 2, 0);
+    const auto typed = [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        with_quant_flags<BASE, NESTED_OK>(a.mat[0].absmax8 != nullptr, quant_type == kFP4, [&](auto flags) {
+            with_rows_waves<false>(rw, [&](auto mb, auto waves) {
+                launch_one<T, decltype(mb)::value, decltype(waves)::value, kRing, decltype(flags)::value>(a, stream);
+            });
+        });
+    };
+    if (dtype == 2)
+        typed(TypeTag<bf16>{});
+    else
+        typed(TypeTag<f16>{});
+    BNB_CHECK_LAUNCH();
+    g_last_gemm_kernel = kKernelStream;
 }
 
 template <typename T> void launch_generic(const GenericArgs& p, hipStream_t stream) {
@@ -1297,6 +1345,34 @@ bool stream_ok(const void* A, int M, int K, int blocksize) {
 // without a generic twin (gated, LoRA, grouped) answer "not supported".
 bool stream_size_ok(long N, long K) { return N * K < (1L << 32); }
 
+// The fields every launch fills. dbg (profiling builds): the stamp buffer for the plain single-matrix call and the peer chain,
+// nullptr for every other form.
+StreamArgs stream_args(const void* A, const float* code16, int M, int K, int blocksize, unsigned long long* dbg) {
+    StreamArgs a;
+#ifdef BNB_PROFILING
+    a.dbg = dbg;
+#else
+    (void)dbg;
+#endif
+    a.A = A;
+    a.code16 = code16;
+    a.M = M;
+    a.K = K;
+    a.bs_shift = ilog2(blocksize);
+    return a;
+}
+// ... of a single-matrix launch: its N rows are the row space, and the unused slots repeat the matrix out of every row's reach
+StreamArgs stream_args(const void* A, const float* code16, int M, int K, int blocksize, const StreamMat& m, unsigned long long* dbg) {
+    StreamArgs a = stream_args(A, code16, M, K, blocksize, dbg);
+    a.rows_total = m.N;
+    a.nmat = 1;
+    for (int i = 0; i < kMaxGroup; ++i) {
+        a.mat[i] = m;
+        a.mat[i].row_start = i == 0 ? 0 : 0x7FFFFFFF;
+    }
+    return a;
+}
+
 void launch_stream_any(int dtype, const StreamArgs& a, int quant_type, bool grouped, hipStream_t stream) {
     if (dtype == 2)
         launch_mb<bf16>(a, quant_type, grouped, stream);
@@ -1318,13 +1394,7 @@ template <typename T, int FLAGS> void launch_peer(const StreamArgs& a, const Geo
                        ge.R | (ge.SW << 16) | (ge.G << 21), (256 + ge.SW - 1) / ge.SW, a);
 }
 template <typename T> void launch_peer_flags(const StreamArgs& a, const Geometry& ge, int quant_type, hipStream_t stream) {
-    const int sel = (a.mat[0].absmax8 != nullptr ? 1 : 0) | (quant_type == kFP4 ? 2 : 0);
-    switch (sel) {
-    case 0: return launch_peer<T, 0>(a, ge, stream);
-    case 1: return launch_peer<T, kNested>(a, ge, stream);
-    case 2: return launch_peer<T, kFp4>(a, ge, stream);
-    default: return launch_peer<T, kFp4 | kNested>(a, ge, stream);
-    }
+    with_quant_flags<0, true>(a.mat[0].absmax8 != nullptr, quant_type == kFP4, [&](auto flags) { launch_peer<T, decltype(flags)::value>(a, ge, stream); });
 }
 
 // (peer chain) the current exchange as a plain [nvalues] tensor: one granule per lane, re-fetched until its tag is there
@@ -1437,10 +1507,7 @@ bool gemv_4bit_peer(void* const* bufs, void* epoch_word, int world, int rank, in
     if (!(mode & 2) && out_local == nullptr)
         return false;
 
-    StreamArgs a;
-#ifdef BNB_PROFILING
-    a.dbg = g_dbg_buf;
-#endif
+    StreamArgs a = stream_args(A, nullptr, 1, K, blocksize, StreamMat{B, absmax, absmax8, absmax_code, absmax_offset, out_local, bias, ns, 0}, stamp_buffer());
     for (int r = 0; r < 8; ++r)
         a.peer.base[r] = static_cast<unsigned char*>(r < world ? bufs[r] : nullptr);
     a.peer.local = a.peer.base[rank];
@@ -1452,17 +1519,8 @@ bool gemv_4bit_peer(void* const* bufs, void* epoch_word, int world, int rank, in
     a.peer.epoch_offset = epoch_offset;
     a.peer.mode = (mode & 3) | (quads ? 4 : 0) | (mode & 8);
     // (x from the exchange: the preloaded pointer slot carries the address of the exchange's region - its position in the chain)
-    a.A = (mode & 1) ? static_cast<const void*>(a.peer.local + kChainDataOffset +
-                                                 static_cast<size_t>(epoch_offset & (kChainRegions - 1u)) * a.peer.max_granules * 8u)
-                     : A;
-    a.code16 = nullptr;
-    a.M = 1;
-    a.K = K;
-    a.bs_shift = ilog2(blocksize);
-    a.rows_total = ns;
-    a.nmat = 1;
-    for (int i = 0; i < kMaxGroup; ++i)
-        a.mat[i] = StreamMat{B, absmax, absmax8, absmax_code, absmax_offset, out_local, bias, ns, i == 0 ? 0 : 0x7FFFFFFF};
+    if (mode & 1)
+        a.A = a.peer.local + kChainDataOffset + static_cast<size_t>(epoch_offset & (kChainRegions - 1u)) * a.peer.max_granules * 8u;
     if (dtype == 2)
         launch_peer_flags<bf16>(a, ge, quant_type, stream);
     else
@@ -1524,19 +1582,8 @@ void gemv_4bit_stream(int dtype, const void* A, const uint8_t* B, const float* a
     if (M <= 0 || N <= 0 || K <= 0)
         return;
     if (stream_ok(A, M, K, blocksize) && stream_size_ok(N, K) && aligned_to(B, 16)) {
-        StreamArgs a;
-#ifdef BNB_PROFILING
-        a.dbg = g_dbg_buf;
-#endif
-        a.A = A;
-        a.code16 = code16;
-        a.M = M;
-        a.K = K;
-        a.bs_shift = ilog2(blocksize);
-        a.rows_total = N;
-        a.nmat = 1;
-        for (int i = 0; i < kMaxGroup; ++i)
-            a.mat[i] = StreamMat{B, absmax, absmax8, absmax_code, absmax_offset, out, bias, N, i == 0 ? 0 : 0x7FFFFFFF};
+        const StreamArgs a =
+            stream_args(A, code16, M, K, blocksize, StreamMat{B, absmax, absmax8, absmax_code, absmax_offset, out, bias, N, 0}, stamp_buffer());
         launch_stream_any(dtype, a, quant_type, false, stream);
         g_last_gemm_kernel = kKernelStream;
         return;
@@ -1553,162 +1600,71 @@ void gemv_4bit_stream(int dtype, const void* A, const uint8_t* B, const float* a
 }
 
 // Gated form (dense FFN, bnb_mi355x_gemm_4bit_gated): ONE interleaved matrix B [N = 2 F, K] - row 2 i = gate row i, row 2 i + 1 = up
-// row i -, bias [N] in the same layout, out [M, F] = silu(gate) * up. The instances the plain call of the same shape runs (launch_mb:
-// one row -> 16 wavefronts, two -> 16 or 8, more -> passes of four on 8), production ring, non-temporal loads, with the gated
+// row i -, bias [N] in the same layout, out [M, F] = silu(gate) * up. The plain call's instance (launch_fused) with the gated
 // epilogue; 16-bit activations and fp32 absmax only. The shape half of the preconditions, shared with the host layer's query:
-static int gated_mb(int M) { return M == 1 ? 1 : M == 2 ? 2 : 4; }
-static int gated_waves(int M, int N, int K) { return M == 1 ? 16 : (M == 2 && make_geometry(N, K, 2, 16, 2, false, 0, 0, true).P == 1) ? 16 : 8; }
 bool gemv_4bit_stream_gated_supported(int dtype, int M, int N, int K, int blocksize) {
     if ((dtype != 1 && dtype != 2) || M < 1 || N < 2 || (N & 1) || K <= 0 || (K % 32) != 0 || K > 511 * kSegK || blocksize < 32 || !is_pow2(blocksize) ||
         !stream_size_ok(N, K))
         return false;
-    const Geometry ge = make_geometry(N, K, gated_mb(M), gated_waves(M, N, K), 2, false, g_tune.sw.load(std::memory_order_relaxed),
-                                      g_tune.rows.load(std::memory_order_relaxed), true);
+    const RowsWaves rw = rows_waves(M, K, 2, 0);
+    const Geometry ge = make_geometry(N, K, rw.mb, rw.waves, 2, false, g_tune.sw.load(std::memory_order_relaxed), g_tune.rows.load(std::memory_order_relaxed), true);
     return ge.R >= 2 && !(ge.R & 1);
-}
-template <typename T, int FLAGS> static void launch_gated(const StreamArgs& a, hipStream_t stream) {
-    if (a.M == 1)
-        return launch_one<T, 1, 16, kRing, FLAGS>(a, stream);
-    if (a.M == 2 && gated_waves(2, a.rows_total, a.K) == 16)
-        return launch_one<T, 2, 16, kRing, FLAGS>(a, stream);
-    if (a.M == 2)
-        return launch_one<T, 2, 8, kRing, FLAGS>(a, stream);
-    launch_one<T, 4, 8, kRing, FLAGS>(a, stream);
 }
 // false - nothing launched - when the call is outside the form's preconditions
 bool gemv_4bit_stream_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K,
                             int blocksize, int quant_type, hipStream_t stream) {
     if (!gemv_4bit_stream_gated_supported(dtype, M, N, K, blocksize) || !stream_ok(A, M, K, blocksize) || !aligned_to(B, 16) || !aligned_to(absmax, 4))
         return false;
-    StreamArgs a;
-#ifdef BNB_PROFILING
-    a.dbg = nullptr;
-#endif
-    a.A = A;
-    a.code16 = nullptr;
-    a.M = M;
-    a.K = K;
-    a.bs_shift = ilog2(blocksize);
-    a.rows_total = N;
-    a.nmat = 1;
-    for (int i = 0; i < kMaxGroup; ++i)
-        a.mat[i] = StreamMat{B, absmax, nullptr, nullptr, nullptr, out, bias, N, i == 0 ? 0 : 0x7FFFFFFF};
-    const bool fp4 = quant_type == kFP4;
-    if (dtype == 2)
-        fp4 ? launch_gated<bf16, kNT | kGated | kFp4>(a, stream) : launch_gated<bf16, kNT | kGated>(a, stream);
-    else
-        fp4 ? launch_gated<f16, kNT | kGated | kFp4>(a, stream) : launch_gated<f16, kNT | kGated>(a, stream);
-    BNB_CHECK_LAUNCH();
-    g_last_gemm_kernel = kKernelStream;
+    const StreamArgs a = stream_args(A, nullptr, M, K, blocksize, StreamMat{B, absmax, nullptr, nullptr, nullptr, out, bias, N, 0}, nullptr);
+    launch_fused<kNT | kGated, false>(dtype, a, quant_type, stream);
     return true;
 }
 
-// LoRA form (bnb_mi355x_gemm_4bit_lora): the plain call's instance (launch_mb: one row -> 16 wavefronts, two -> 16 or 8, more ->
-// passes of four on 8; production ring, non-temporal loads, literal table, fp32 absmax or nested statistics) with the adapter term
-// out[m, n] = T((acc + bias[n]) + scaling * sum_j t[m, j] * B_l[n, j]) as its epilogue. 16-bit activations. The shape half of the
+// LoRA form (bnb_mi355x_gemm_4bit_lora): the plain call's instance (launch_fused; fp32 absmax or nested statistics) with the adapter
+// term out[m, n] = T((acc + bias[n]) + scaling * sum_j t[m, j] * B_l[n, j]) as its epilogue. 16-bit activations. The shape half of the
 // preconditions, shared with the host layer's query:
 bool gemv_4bit_stream_lora_supported(int dtype, int M, int N, int K, int blocksize, int r) {
     return (dtype == 1 || dtype == 2) && M >= 1 && M <= 65535 && N >= 1 && K > 0 && (K % 32) == 0 && K <= 511 * kSegK && blocksize >= 32 && is_pow2(blocksize) &&
            r >= 8 && r <= 128 && (r % 8) == 0 && stream_size_ok(N, K);
 }
-template <typename T, int FLAGS> static void launch_lora(const StreamArgs& a, hipStream_t stream) {
-    if (a.M == 1)
-        return launch_one<T, 1, 16, kRing, FLAGS>(a, stream);
-    if (a.M == 2 && make_geometry(a.rows_total, a.K, 2, 16, 2, false, 0, 0).P == 1) // (launch_mb's question)
-        return launch_one<T, 2, 16, kRing, FLAGS>(a, stream);
-    if (a.M == 2)
-        return launch_one<T, 2, 8, kRing, FLAGS>(a, stream);
-    launch_one<T, 4, 8, kRing, FLAGS>(a, stream);
-}
-template <typename T> static void launch_lora_flags(const StreamArgs& a, int quant_type, hipStream_t stream) {
-    const int sel = (a.mat[0].absmax8 != nullptr ? 1 : 0) | (quant_type == kFP4 ? 2 : 0);
-    switch (sel) {
-    case 0: return launch_lora<T, kNT | kLora>(a, stream);
-    case 1: return launch_lora<T, kNT | kLora | kNested>(a, stream);
-    case 2: return launch_lora<T, kNT | kLora | kFp4>(a, stream);
-    default: return launch_lora<T, kNT | kLora | kFp4 | kNested>(a, stream);
+// (both LoRA entry points; ids: the mixed-adapter block - kLoraIds -, nullptr for the uniform call, whose `scaling` it replaces)
+static bool stream_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                        const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, const LoraIds* ids,
+                        int r, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
+    if (!gemv_4bit_stream_lora_supported(dtype, M, N, K, blocksize, r) || !stream_ok(A, M, K, blocksize) || !aligned_to(B, 16) || !aligned_to(absmax, 4) ||
+        !aligned_to(lora_t, 16) || !aligned_to(lora_b, 16) || (absmax8 != nullptr && (absmax_code == nullptr || absmax_offset == nullptr)) ||
+        (ids != nullptr && !ids->valid()))
+        return false;
+    StreamArgs a = stream_args(A, nullptr, M, K, blocksize, StreamMat{B, absmax, absmax8, absmax_code, absmax_offset, out, bias, N, 0}, nullptr);
+    a.lora_t = lora_t;
+    a.lora_b = lora_b;
+    a.lora_r = r;
+    a.lora_scaling = ids ? 0.0f : scaling;
+    if (ids) {
+        a.lora_ids = ids->ids;
+        a.lora_scalings = ids->scalings;
+        a.lora_an = ids->A_n;
+        a.lora_idx64 = ids->index_bytes == 8 ? 1 : 0;
+        launch_fused<kNT | kLora | kLoraIds, true>(dtype, a, quant_type, stream);
+    } else {
+        launch_fused<kNT | kLora, true>(dtype, a, quant_type, stream);
     }
+    return true;
 }
 // false - nothing launched - when the call is outside the form's preconditions
 bool gemv_4bit_stream_lora(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
                            const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, float scaling, int r,
                            int M, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
-    if (!gemv_4bit_stream_lora_supported(dtype, M, N, K, blocksize, r) || !stream_ok(A, M, K, blocksize) || !aligned_to(B, 16) || !aligned_to(absmax, 4) ||
-        !aligned_to(lora_t, 16) || !aligned_to(lora_b, 16) || (absmax8 != nullptr && (absmax_code == nullptr || absmax_offset == nullptr)))
-        return false;
-    StreamArgs a;
-#ifdef BNB_PROFILING
-    a.dbg = nullptr;
-#endif
-    a.A = A;
-    a.code16 = nullptr;
-    a.M = M;
-    a.K = K;
-    a.bs_shift = ilog2(blocksize);
-    a.rows_total = N;
-    a.nmat = 1;
-    for (int i = 0; i < kMaxGroup; ++i)
-        a.mat[i] = StreamMat{B, absmax, absmax8, absmax_code, absmax_offset, out, bias, N, i == 0 ? 0 : 0x7FFFFFFF};
-    a.lora_t = lora_t;
-    a.lora_b = lora_b;
-    a.lora_r = r;
-    a.lora_scaling = scaling;
-    if (dtype == 2)
-        launch_lora_flags<bf16>(a, quant_type, stream);
-    else
-        launch_lora_flags<f16>(a, quant_type, stream);
-    BNB_CHECK_LAUNCH();
-    g_last_gemm_kernel = kKernelStream;
-    return true;
+    return stream_lora(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, lora_t, lora_b, scaling, nullptr, r, M, N, K, blocksize,
+                       quant_type, stream);
 }
-
-// Mixed-adapter LoRA form (bnb_mi355x_gemm_4bit_lora_ids): the LoRA form's instance skeleton with kLoraIds - lora_b [A_n, N, r],
-// scalings [A_n] fp32 and ids [M] (int32 / int64) on the device. false - nothing launched - outside the preconditions.
-template <typename T> static void launch_lora_ids_flags(const StreamArgs& a, int quant_type, hipStream_t stream) {
-    const int sel = (a.mat[0].absmax8 != nullptr ? 1 : 0) | (quant_type == kFP4 ? 2 : 0);
-    switch (sel) {
-    case 0: return launch_lora<T, kNT | kLora | kLoraIds>(a, stream);
-    case 1: return launch_lora<T, kNT | kLora | kLoraIds | kNested>(a, stream);
-    case 2: return launch_lora<T, kNT | kLora | kLoraIds | kFp4>(a, stream);
-    default: return launch_lora<T, kNT | kLora | kLoraIds | kFp4 | kNested>(a, stream);
-    }
-}
+// Mixed-adapter LoRA form (bnb_mi355x_gemm_4bit_lora_ids): lora_b [A_n, N, r], scalings [A_n] fp32 and ids [M] (int32 / int64) on the device.
 bool gemv_4bit_stream_lora_ids(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
                                const float* absmax_offset, void* out, const void* bias, const void* lora_t, const void* lora_b, const float* scalings,
                                const void* ids, int index_bytes, int A_n, int r, int M, int N, int K, int blocksize, int quant_type, hipStream_t stream) {
-    if (!gemv_4bit_stream_lora_supported(dtype, M, N, K, blocksize, r) || !stream_ok(A, M, K, blocksize) || !aligned_to(B, 16) || !aligned_to(absmax, 4) ||
-        !aligned_to(lora_t, 16) || !aligned_to(lora_b, 16) || (absmax8 != nullptr && (absmax_code == nullptr || absmax_offset == nullptr)) || A_n < 1 ||
-        A_n > 64 || (index_bytes != 4 && index_bytes != 8) || ids == nullptr || scalings == nullptr || !aligned_to(ids, static_cast<size_t>(index_bytes)) ||
-        !aligned_to(scalings, 4))
-        return false;
-    StreamArgs a;
-#ifdef BNB_PROFILING
-    a.dbg = nullptr;
-#endif
-    a.A = A;
-    a.code16 = nullptr;
-    a.M = M;
-    a.K = K;
-    a.bs_shift = ilog2(blocksize);
-    a.rows_total = N;
-    a.nmat = 1;
-    for (int i = 0; i < kMaxGroup; ++i)
-        a.mat[i] = StreamMat{B, absmax, absmax8, absmax_code, absmax_offset, out, bias, N, i == 0 ? 0 : 0x7FFFFFFF};
-    a.lora_t = lora_t;
-    a.lora_b = lora_b;
-    a.lora_r = r;
-    a.lora_scaling = 0.0f;
-    a.lora_ids = ids;
-    a.lora_scalings = scalings;
-    a.lora_an = A_n;
-    a.lora_idx64 = index_bytes == 8 ? 1 : 0;
-    if (dtype == 2)
-        launch_lora_ids_flags<bf16>(a, quant_type, stream);
-    else
-        launch_lora_ids_flags<f16>(a, quant_type, stream);
-    BNB_CHECK_LAUNCH();
-    g_last_gemm_kernel = kKernelStream;
-    return true;
+    const LoraIds block{scalings, ids, index_bytes, A_n};
+    return stream_lora(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, lora_t, lora_b, 0.0f, &block, r, M, N, K, blocksize, quant_type,
+                       stream);
 }
 
 // Grouped launch: `count` weight matrices (same K, blocksize, quant_type, nested-ness) applied to the same
@@ -1720,15 +1676,7 @@ bool gemv_4bit_grouped(int dtype, const void* A, int count, const uint8_t* const
                        hipStream_t stream) {
     if (count < 1 || count > kMaxGroup || M < 1 || M > 4 || K <= 0 || !stream_ok(A, M, K, blocksize))
         return false;
-    StreamArgs a;
-#ifdef BNB_PROFILING
-    a.dbg = nullptr;
-#endif
-    a.A = A;
-    a.code16 = nullptr;
-    a.M = M;
-    a.K = K;
-    a.bs_shift = ilog2(blocksize);
+    StreamArgs a = stream_args(A, nullptr, M, K, blocksize, nullptr);
     a.nmat = count;
     long rows = 0;
     const bool nested = absmax8 != nullptr && absmax8[0] != nullptr;
@@ -1748,10 +1696,14 @@ bool gemv_4bit_grouped(int dtype, const void* A, int count, const uint8_t* const
         a.mat[i].row_start = 0x7FFFFFFF;
     }
     a.rows_total = static_cast<int>(rows);
-    const int mb = M >= 3 ? 4 : M;
-    if (make_geometry(a.rows_total, K, mb, mb <= 2 ? 16 : 8, dtype == 0 ? 4 : 2, true, 0, 0).P > 1 ||
-        make_geometry(a.rows_total, K, mb, 8, dtype == 0 ? 4 : 2, true, 0, 0).P > 1)
-        return false; // rows longer than one workgroup's segment columns: the single-matrix path has the phase loop
+    // rows longer than one workgroup's segment columns: the single-matrix path has the phase loop. Asked for the instance the launch
+    // picks with the `waves` knob at rest and with it at 8: whether a group is served does not depend on the knob.
+    const int tbytes = dtype == 0 ? 4 : 2;
+    for (int knob = 0; knob <= 8; knob += 8) {
+        const RowsWaves rw = rows_waves(M, K, tbytes, knob);
+        if (make_geometry(a.rows_total, K, rw.mb, rw.waves, tbytes, true, 0, 0).P > 1)
+            return false;
+    }
     launch_stream_any(dtype, a, quant_type, true, stream);
     g_last_gemm_kernel = kKernelStream;
     return true;

@@ -23,7 +23,7 @@
 // Mixed-adapter form (lora_shrink_ids_kernel): A is a stack [A_n, R, K], every row of x names its adapter by an id
 // on the device, the grid gets a second dimension (adapter), and the tile body below runs with the rows of other adapters masked
 // out of the x operand - same steps, same order, so a row has the bits of the uniform kernel's call with its adapter.
-#include "bnb_common.h"
+#include "bnb_launchers.h"
 
 namespace bnb {
 namespace {

@@ -33,7 +33,7 @@
 //   * special case (inf/NaN in the block) and the division of the ragged tail block keep the plain
 //     compare tree - they are wave-uniform branches that normal data never takes;
 //   * each lane emits one packed dword per chunk (a wavefront writes 256 B contiguous).
-#include "bnb_common.h"
+#include "bnb_launchers.h"
 
 namespace bnb {
 
