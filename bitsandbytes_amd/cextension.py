@@ -128,6 +128,8 @@ def _declare(dll: ct.CDLL) -> None:
     sig(["bnb_mi355x_peer_chain_read"], [_VOID_P, _VOID_P, _I32, _I32, _I32, _VOID_P, _I32, ct.c_long, _I32, _VOID_P])
     sig(["bnb_mi355x_set_stream_tuning"], [_I32] * 5)
     sig(["bnb_mi355x_gemv_4bit_stream_exact"], [_I32] * 6, _I32)
+    # (form, dtype, M, rows, K, blocksize, out8: int32[8] on the host)
+    sig(["bnb_mi355x_stream_geometry"], [_I32] * 3 + [ct.c_long, _I32, _I32, _VOID_P], _I32)
     sig(["bnb_mi355x_set_tuning"], [_I32] * 4)
     sig(["bnb_mi355x_set_stamp_buffer"], [_VOID_P])
     sig(["bnb_mi355x_version"], [], ct.c_char_p)
@@ -170,5 +172,5 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_peer_close", "bnb_mi355x_peer_allgather", "bnb_mi355x_peer_status",
        "bnb_mi355x_peer_chain_buffer_bytes", "bnb_mi355x_peer_chain_alloc", "bnb_mi355x_gemv_4bit_peer_serves", "bnb_mi355x_gemv_4bit_peer",
        "bnb_mi355x_peer_chain_read",
-       "bnb_mi355x_set_stream_tuning", "bnb_mi355x_gemv_4bit_stream_exact", "bnb_mi355x_set_tuning", "bnb_mi355x_set_stamp_buffer", "bnb_mi355x_version"]
+       "bnb_mi355x_set_stream_tuning", "bnb_mi355x_gemv_4bit_stream_exact", "bnb_mi355x_stream_geometry", "bnb_mi355x_set_tuning", "bnb_mi355x_set_stamp_buffer", "bnb_mi355x_version"]
 )

@@ -43,6 +43,7 @@ bool gemv_4bit_grouped(int dtype, const void* A, int count, const uint8_t* const
                        int M, int K, int blocksize, int quant_type, hipStream_t stream);
 void gemv_4bit_stream_tuning(int ns, int sw, int rows_per_wg, int nt, int waves);
 bool gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, bool nested);
+bool gemv_4bit_stream_geometry(int form, int dtype, int M, long rows, int K, int blocksize, int* out8);
 bool gemv_4bit_stream_size_ok(long N, long K);
 bool gemv_4bit_stream_gated_supported(int dtype, int M, int N, int K, int blocksize);
 bool gemv_4bit_stream_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N, int K,

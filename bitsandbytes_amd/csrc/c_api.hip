@@ -569,6 +569,9 @@ void bnb_mi355x_set_stream_tuning(int ring_depth, int segments, int rows_per_wor
 int bnb_mi355x_gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, int nested) {
     return gemv_4bit_stream_exact(dtype, M, N, K, blocksize, nested != 0) ? 1 : 0;
 }
+int bnb_mi355x_stream_geometry(int form, int dtype, int M, long rows, int K, int blocksize, int* out8) {
+    return gemv_4bit_stream_geometry(form, dtype, M, rows, K, blocksize, out8) ? 1 : 0;
+}
 void bnb_mi355x_set_stamp_buffer(void* device_u64_buffer) {
 #ifdef BNB_PROFILING
     g_dbg_buf = static_cast<unsigned long long*>(device_u64_buffer);

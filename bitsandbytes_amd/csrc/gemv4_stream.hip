@@ -1109,9 +1109,10 @@ Geometry make_geometry(int rows_total, int K, int mb, int waves, int tbytes, boo
     if (R < 1)
         R = 1;
     // (gated launches) rows come in (gate, up) pairs: an even row count per workgroup - so every workgroup starts on a gate row -,
-    // rounded UP where the row split gave an odd one, down where the partial-sum slots clamp it (R = 1 then: the caller refuses)
+    // rounded UP where the row split gave an odd one, down where the partial-sum slots clamp it. R = 1 under a clamp to one row stays 1
+    // - never 0: grid_x below divides by it - and the caller refuses (gemv_4bit_stream_gated_supported; launch_one's backstop)
     if (pairs && (R & 1))
-        R = (R + 1 <= r_cap && R + 1 <= 0xFFFF) ? R + 1 : R - 1;
+        R = (R + 1 <= r_cap && R + 1 <= 0xFFFF) ? R + 1 : (R > 1 ? R - 1 : 1);
     ge.R = R;
     ge.P = (S + sw - 1) / sw;
     ge.grid_x = (rows_total + R - 1) / R;
@@ -1124,10 +1125,29 @@ struct StreamTuning {
 };
 thread_local StreamTuning g_tune;
 
+// The geometry of a launch: make_geometry under the calling thread's `segments` and `rows_per_workgroup` knobs. The launch, the
+// predicates that depend on the geometry and the host query (gemv_4bit_stream_geometry) all ask here.
+Geometry tuned_geometry(int rows_total, int K, int mb, int waves, int tbytes, bool grouped, bool pairs) {
+    return make_geometry(rows_total, K, mb, waves, tbytes, grouped, g_tune.sw.load(std::memory_order_relaxed), g_tune.rows.load(std::memory_order_relaxed),
+                         pairs);
+}
+
 // Production ring depth: 2 stages with 16 wavefronts per CU (2 KiB x 16 in flight already cover bandwidth x latency;
 // deeper rings only add refill work at the end of a row list), 4 stages - decoded two at a time - with 8.
 constexpr int kRing = 2;
 constexpr int ring_depth(int mb, int waves) { return (mb == 1 && waves == 8) ? 4 : kRing; }
+// Instances that exist single-phase only - the sweep ring depths and the 16-wavefront two-row form (rows_waves) -: a multi-phase
+// geometry on one of them (the `segments` knob can make one) runs the production instance of multi_phase_waves(mb) wavefronts.
+constexpr bool single_phase_only(int mb, int waves, int ns) { return ns != ring_depth(mb, waves) || (mb == 2 && waves == 16); }
+constexpr int multi_phase_waves(int mb) { return mb == 1 ? 16 : 8; }
+// The ring depth of the sweep instance that the `ring_depth` knob selects at this wavefront count (bf16, one row, fp32 absmax, NF4:
+// launch_tuned), 0 = none.
+int sweep_ring(int waves) {
+    const int ns = g_tune.ns.load(std::memory_order_relaxed);
+    if (waves == 8)
+        return ns == 2 ? 2 : 0;
+    return (ns == 3 || ns == 4 || ns == 6) ? ns : 0;
+}
 
 // The exact-geometry instance (kExact) serves a launch whose geometry has nothing to decide at run time: one activation row, one
 // phase, K = 2 x 2048 in two segment columns (SW = 2, G = 8), every workgroup full (rows_total % R == 0), every row group with
@@ -1152,8 +1172,7 @@ template <typename T, int MB, int WAVES, int NS, int FLAGS> constexpr bool has_e
 constexpr int kTuneGeneral = 2, kTuneLateArgs = 3;
 
 template <typename T, int MB, int WAVES, int NS, int FLAGS> void launch_one(const StreamArgs& a, hipStream_t stream) {
-    const Geometry ge = make_geometry(a.rows_total, a.K, MB, WAVES, TypeInfo<T>::bytes, (FLAGS & kGrouped) != 0, g_tune.sw.load(std::memory_order_relaxed),
-                                      g_tune.rows.load(std::memory_order_relaxed), (FLAGS & kGated) != 0);
+    const Geometry ge = tuned_geometry(a.rows_total, a.K, MB, WAVES, TypeInfo<T>::bytes, (FLAGS & kGrouped) != 0, (FLAGS & kGated) != 0);
     if constexpr ((FLAGS & kGated) != 0) {
         if (ge.R < 2 || (ge.R & 1) || (a.rows_total & 1)) { // (gemv_4bit_stream_gated_supported asks the same question)
             fprintf(stderr, "bitsandbytes_amd: gemm_4bit_gated: internal error, odd rows per workgroup\n");
@@ -1182,14 +1201,14 @@ template <typename T, int MB, int WAVES, int NS, int FLAGS> void launch_one(cons
                 return go(gemv4_stream_kernel<T, MB, WAVES, NS, FLAGS | kExact>);
         }
     }
-    if constexpr (!(FLAGS & kGrouped) && NS == ring_depth(MB, WAVES) && !(MB == 2 && WAVES == 16)) {
+    if constexpr (!(FLAGS & kGrouped) && !single_phase_only(MB, WAVES, NS)) {
         if (ge.P > 1)
             return go(gemv4_stream_kernel<T, MB, WAVES, NS, FLAGS | kMulti>);
     }
     if (ge.P > 1) {
         // sweep-only instances exist single-phase only; grouped launches are refused earlier (grouped_fits)
-        if constexpr (!(FLAGS & kGrouped) && (NS != ring_depth(MB, WAVES) || (MB == 2 && WAVES == 16)))
-            return launch_one<T, MB, (MB == 1 ? 16 : 8), kRing, FLAGS | kNT>(a, stream);
+        if constexpr (!(FLAGS & kGrouped) && single_phase_only(MB, WAVES, NS))
+            return launch_one<T, MB, multi_phase_waves(MB), kRing, FLAGS | kNT>(a, stream);
         fprintf(stderr, "bitsandbytes_amd: gemv_4bit: internal error, multi-phase geometry on a single-phase instance\n");
         exit(1);
     }
@@ -1200,7 +1219,7 @@ template <typename T, int MB, int WAVES, int NS, int FLAGS> void launch_one(cons
 // row, fp32 absmax, literal NF4 table - so that tools/ can A/B them without multiplying the instance count of the library.
 template <typename T, int MB, int WAVES, int FLAGS> void launch_tuned(const StreamArgs& a, hipStream_t stream) {
     if constexpr (std::is_same<T, bf16>::value && MB == 1 && FLAGS == 0) {
-        const int ns = g_tune.ns.load(std::memory_order_relaxed);
+        const int ns = sweep_ring(WAVES);
         const int nt = g_tune.nt.load(std::memory_order_relaxed);
         if constexpr (WAVES == 8) {
             if (ns == 2)
@@ -1245,6 +1264,24 @@ RowsWaves rows_waves(int M, int K, int tbytes, int waves_knob) {
     if (M == 2)
         return {2, (waves_knob != 8 && make_geometry(1, K, 2, 16, tbytes, false, 0, 0).P == 1) ? 16 : 8};
     return {4, 8};
+}
+// The instance a call selects first, per path: the plain call (launch_mb) honours the `waves` knob, a fused call (launch_fused, 16-bit
+// activations) never did. The launch paths, the gated predicate and the host query (gemv_4bit_stream_geometry) all ask here.
+RowsWaves plain_rows_waves(int M, int K, int tbytes) { return rows_waves(M, K, tbytes, g_tune.waves.load(std::memory_order_relaxed)); }
+RowsWaves fused_rows_waves(int M, int K) { return rows_waves(M, K, 2, 0); }
+// The instance and the geometry a launch ENDS with, given the instance (rw, ring depth ns) its path selects first: launch_one steps
+// from a single-phase-only instance to the production one when the geometry has several phases, and the geometry follows the wavefronts.
+struct LaunchPlan {
+    RowsWaves rw;
+    Geometry ge;
+};
+LaunchPlan launch_plan(RowsWaves rw, int ns, int rows_total, int K, int tbytes, bool grouped, bool pairs) {
+    Geometry ge = tuned_geometry(rows_total, K, rw.mb, rw.waves, tbytes, grouped, pairs);
+    if (ge.P > 1 && !grouped && single_phase_only(rw.mb, rw.waves, ns)) {
+        rw.waves = multi_phase_waves(rw.mb);
+        ge = tuned_geometry(rows_total, K, rw.mb, rw.waves, tbytes, grouped, pairs);
+    }
+    return {rw, ge};
 }
 // ... as template arguments: f(MB, WAVES) as integral constants. KNOB: the caller honours the `waves` knob, which alone selects
 // 1 x 8 - no fused 1 x 8 instance exists.
@@ -1300,7 +1337,7 @@ template <typename T, int MB, int WAVES> void launch_flags(const StreamArgs& a, 
 // the plain call (single matrix or grouped): the one path that honours the `waves` tuning knob and has the sweep variants of launch_tuned
 template <typename T> void launch_mb(const StreamArgs& a, int quant_type, bool grouped, hipStream_t stream) {
     // (a caller-supplied code table - legacy op - always runs row by row)
-    const RowsWaves rw = rows_waves(a.code16 != nullptr ? 1 : a.M, a.K, TypeInfo<T>::bytes, g_tune.waves.load(std::memory_order_relaxed));
+    const RowsWaves rw = plain_rows_waves(a.code16 != nullptr ? 1 : a.M, a.K, TypeInfo<T>::bytes);
     with_rows_waves<true>(rw, [&](auto mb, auto waves) { launch_flags<T, decltype(mb)::value, decltype(waves)::value>(a, quant_type, grouped, stream); });
 }
 
@@ -1308,7 +1345,7 @@ template <typename T> void launch_mb(const StreamArgs& a, int quant_type, bool g
 // runs - rows_waves without the knob -, production ring, literal table, with the epilogue compiled in. That is what makes the fused
 // result the plain result plus the epilogue, bit for bit.
 template <int BASE, bool NESTED_OK> void launch_fused(int dtype, const StreamArgs& a, int quant_type, hipStream_t stream) {
-    const RowsWaves rw = rows_waves(a.M, a.K, 2, 0);
+    const RowsWaves rw = fused_rows_waves(a.M, a.K);
     const auto typed = [&](auto tag) {
         using T = typename decltype(tag)::type;
         with_quant_flags<BASE, NESTED_OK>(a.mat[0].absmax8 != nullptr, quant_type == kFP4, [&](auto flags) {
@@ -1331,6 +1368,19 @@ template <typename T> void launch_generic(const GenericArgs& p, hipStream_t stre
         hipLaunchKernelGGL((gemv4_generic_kernel<T, true>), grid, dim3(256), 0, stream, p);
     else
         hipLaunchKernelGGL((gemv4_generic_kernel<T, false>), grid, dim3(256), 0, stream, p);
+}
+
+// Grouped launches exist single-phase only - rows longer than one workgroup's segment columns go matrix by matrix, through the
+// single-matrix path's phase loop. Asked for the instance the launch picks with the `waves` knob at rest and with it at 8: whether a
+// group is served does not depend on that knob. It does depend on the `segments` knob, which the launch's geometry honours: fewer
+// segment columns can turn a one-phase row into several.
+bool grouped_fits(int rows_total, int M, int K, int tbytes) {
+    for (int knob = 0; knob <= 8; knob += 8) {
+        const RowsWaves rw = rows_waves(M, K, tbytes, knob);
+        if (tuned_geometry(rows_total, K, rw.mb, rw.waves, tbytes, true, false).P > 1)
+            return false;
+    }
+    return true;
 }
 
 bool stream_ok(const void* A, int M, int K, int blocksize) {
@@ -1574,6 +1624,41 @@ void gemv_4bit_stream_tuning(int ns, int sw, int rows_per_wg, int nt, int waves)
     g_tune.waves.store(waves, std::memory_order_relaxed);
 }
 
+// The launch geometry of a streaming-kernel call, without the call (bnb_mi355x_stream_geometry: tests and tools). form: 0 = plain
+// single matrix, 1 = grouped (rows = the group's rows, taken as one matrix for the size predicate), 2 = gated, 3 = LoRA, 4 = LoRA with
+// adapter ids (r = 8 for the rank predicate: the geometry does not depend on r). false where the form's own predicates - the ones its
+// entry point above asks, aligned pointers assumed - refuse the call. Otherwise out8 = {R, SW, G, P, grid_x, lds bytes, mb, waves} of the
+// instance that launches: plain_rows_waves / fused_rows_waves as launch_mb / launch_fused call them, and launch_plan - tuned_geometry with
+// launch_one's step from a single-phase-only instance to the production one. The `ring_depth` knob's sweep instances exist for one
+// configuration (launch_tuned); a plain bf16 one-row query answers for that configuration (NF4, fp32 absmax). The legacy call with a
+// caller-supplied code table runs row by row whatever its M: ask with M = 1.
+bool gemv_4bit_stream_geometry(int form, int dtype, int M, long rows, int K, int blocksize, int* out8) {
+    if (form < 0 || form > 4 || dtype < 0 || dtype > 2 || M < 1 || rows < 1 || rows > 0x7FFFFFFF || K <= 0 || out8 == nullptr)
+        return false;
+    const int N = static_cast<int>(rows);
+    const int tbytes = dtype == 0 ? 4 : 2;
+    const bool grouped = form == 1, gated = form == 2, fused = form >= 2;
+    const void* const aligned = reinterpret_cast<const void*>(uintptr_t(4096));
+    if (!stream_ok(aligned, M, K, blocksize) || !stream_size_ok(N, K))
+        return false;
+    if (grouped && (M > 4 || !grouped_fits(N, M, K, tbytes)))
+        return false;
+    if (gated && !gemv_4bit_stream_gated_supported(dtype, M, N, K, blocksize))
+        return false;
+    if (form >= 3 && !gemv_4bit_stream_lora_supported(dtype, M, N, K, blocksize, 8))
+        return false;
+    const RowsWaves rw = fused ? fused_rows_waves(M, K) : plain_rows_waves(M, K, tbytes);
+    int ns = fused ? kRing : ring_depth(rw.mb, rw.waves);
+    if (form == 0 && dtype == 2 && rw.mb == 1 && sweep_ring(rw.waves) != 0)
+        ns = sweep_ring(rw.waves);
+    const LaunchPlan pl = launch_plan(rw, ns, N, K, tbytes, grouped, gated);
+    const Geometry& ge = pl.ge;
+    const int v[8] = {ge.R, ge.SW, ge.G, ge.P, ge.grid_x, static_cast<int>(ge.lds), pl.rw.mb, pl.rw.waves};
+    for (int i = 0; i < 8; ++i)
+        out8[i] = v[i];
+    return true;
+}
+
 // Entry used by c_api.hip. dtype: 0 = f32, 1 = f16, 2 = bf16. The streaming kernel whenever its preconditions hold
 // (K % 32 == 0, 16-byte aligned A and B, blocksize a power of two >= 32), else the generic one. Any M >= 1.
 void gemv_4bit_stream(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
@@ -1606,8 +1691,8 @@ bool gemv_4bit_stream_gated_supported(int dtype, int M, int N, int K, int blocks
     if ((dtype != 1 && dtype != 2) || M < 1 || N < 2 || (N & 1) || K <= 0 || (K % 32) != 0 || K > 511 * kSegK || blocksize < 32 || !is_pow2(blocksize) ||
         !stream_size_ok(N, K))
         return false;
-    const RowsWaves rw = rows_waves(M, K, 2, 0);
-    const Geometry ge = make_geometry(N, K, rw.mb, rw.waves, 2, false, g_tune.sw.load(std::memory_order_relaxed), g_tune.rows.load(std::memory_order_relaxed), true);
+    const RowsWaves rw = fused_rows_waves(M, K);
+    const Geometry ge = launch_plan(rw, kRing, N, K, 2, false, true).ge;
     return ge.R >= 2 && !(ge.R & 1);
 }
 // false - nothing launched - when the call is outside the form's preconditions
@@ -1696,14 +1781,8 @@ bool gemv_4bit_grouped(int dtype, const void* A, int count, const uint8_t* const
         a.mat[i].row_start = 0x7FFFFFFF;
     }
     a.rows_total = static_cast<int>(rows);
-    // rows longer than one workgroup's segment columns: the single-matrix path has the phase loop. Asked for the instance the launch
-    // picks with the `waves` knob at rest and with it at 8: whether a group is served does not depend on the knob.
-    const int tbytes = dtype == 0 ? 4 : 2;
-    for (int knob = 0; knob <= 8; knob += 8) {
-        const RowsWaves rw = rows_waves(M, K, tbytes, knob);
-        if (make_geometry(a.rows_total, K, rw.mb, rw.waves, tbytes, true, 0, 0).P > 1)
-            return false;
-    }
+    if (!grouped_fits(a.rows_total, M, K, dtype == 0 ? 4 : 2))
+        return false;
     launch_stream_any(dtype, a, quant_type, true, stream);
     g_last_gemm_kernel = kKernelStream;
     return true;

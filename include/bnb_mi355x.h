@@ -362,6 +362,17 @@ void bnb_mi355x_set_stream_tuning(int ring_depth, int segments, int rows_per_wor
  * epilogue's pointers loaded late (A/B runs: tools/stream_fixed_cost_ab.py). */
 int bnb_mi355x_gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, int nested);
 
+/* Test and tool infrastructure: the launch geometry of a streaming-kernel call (csrc/gemv4_stream.hip), without the call. Host logic
+ * only - no device pointer, no HIP call beyond the CU count of the current device (256 without one) -, under the calling thread's
+ * stream tuning, computed by the functions the launch itself calls. form: 0 = bnb_mi355x_gemm_4bit (single matrix), 1 = the grouped
+ * call (rows = the rows of the whole group), 2 = gated (rows = 2 F), 3 = LoRA, 4 = LoRA with adapter ids. dtype: 0 = fp32, 1 = fp16,
+ * 2 = bf16. Returns 0, out8 untouched, where the streaming kernel's own predicates refuse that form of the call (K % 32, K > 511 * 2048,
+ * rows * K >= 2^32, fp32 on a fused form, a grouped row of several phases, a gated call whose workgroups cannot hold row pairs ...);
+ * it does NOT ask the router - whether bnb_mi355x_gemm_4bit sends the shape to this kernel is bnb_mi355x_gemm_4bit_route's answer.
+ * Returns 1 and out8 = {R rows per workgroup, SW segment columns, G row groups, P phases, grid_x workgroups, dynamic LDS bytes,
+ * mb activation rows per pass, waves wavefronts per workgroup}. */
+int bnb_mi355x_stream_geometry(int form, int dtype, int M, long rows, int K, int blocksize, int* out8);
+
 /* Profiling builds only (libbitsandbytes_mi355x_prof.so, -DBNB_PROFILING): when non-NULL the kernels write s_memtime
  * stamps per wavefront (u64) into this device buffer (tools/timeline_*.py). The product library contains no stamp or
  * ablation code; there the call is accepted and ignored. */
