@@ -33,9 +33,6 @@ namespace bnb {
 
 namespace {
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ float bin_value(unsigned u) {
     return -1.0f + (2.0f * static_cast<float>(u)) / 65535.0f; // the reference's expression, IEEE division
 }
@@ -69,7 +66,7 @@ __device__ __forceinline__ unsigned bin_of(float x, float inv) {
 template <typename T> __device__ __forceinline__ void load4(const T* __restrict__ A, long i, long n, bool vec_ok, float (&x)[4]) {
     if (vec_ok && i + 4 <= n) {
         if constexpr (sizeof(T) == 4) {
-            const f32x4_t r = stream_load<true>(reinterpret_cast<const f32x4_t*>(A + i));
+            const f32x4 r = stream_load<true>(reinterpret_cast<const f32x4*>(A + i));
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 x[j] = r[j];
@@ -121,7 +118,7 @@ __device__ __forceinline__ void build_cell_tables(const float* __restrict__ code
         atomicAdd(&cnt[(t >> 6) + 1u], 1u);
     __syncthreads();
     // thread tid owns c = 4 tid + 1 .. 4 tid + 4
-    const u32x4_t mine = *reinterpret_cast<const u32x4_t*>(&cnt[4 * tid]); // cnt[4 tid .. 4 tid + 3]
+    const u32x4 mine = *reinterpret_cast<const u32x4*>(&cnt[4 * tid]); // cnt[4 tid .. 4 tid + 3]
     const uint32_t last = cnt[4 * tid + 4];
     const unsigned own[4] = {mine[1], mine[2], mine[3], last};
     const unsigned sum = own[0] + own[1] + own[2] + own[3];
@@ -182,7 +179,7 @@ __global__ __launch_bounds__(256) void absmax_partial_sums_kernel(const float* _
         const long i = begin + static_cast<long>(s) * kSumChunk;
         float x[4];
         if (vec_ok && i + 4 <= n) {
-            const f32x4_t r = *reinterpret_cast<const f32x4_t*>(A + i);
+            const f32x4 r = *reinterpret_cast<const f32x4*>(A + i);
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 x[j] = r[j];
@@ -353,10 +350,10 @@ __global__ __launch_bounds__(kQ8LutThreads) void quantize8_lut_kernel(const floa
     // of the 512 sums, and a SWAR running sum over its 32 dwords. No byte can overflow: there are 255 thresholds in all.
     // (A per-u walk over the sorted thresholds cost ~5 us per launch: ~10 instructions for each of the 65536 entries.)
     {
-        u32x4_t* const z = reinterpret_cast<u32x4_t*>(lut);
+        u32x4* const z = reinterpret_cast<u32x4*>(lut);
 #pragma unroll
         for (int i = 0; i < 65536 / 16 / kQ8LutThreads; ++i)
-            z[i * kQ8LutThreads + tid] = u32x4_t{0u, 0u, 0u, 0u};
+            z[i * kQ8LutThreads + tid] = u32x4{0u, 0u, 0u, 0u};
     }
     __syncthreads();
     if (tid < 255) {
@@ -367,10 +364,10 @@ __global__ __launch_bounds__(kQ8LutThreads) void quantize8_lut_kernel(const floa
     __syncthreads();
     {
         uint32_t d[32];
-        const u32x4_t* const src = reinterpret_cast<const u32x4_t*>(lut + tid * 128);
+        const u32x4* const src = reinterpret_cast<const u32x4*>(lut + tid * 128);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const u32x4_t v = src[i];
+            const u32x4 v = src[i];
             d[4 * i] = v[0];
             d[4 * i + 1] = v[1];
             d[4 * i + 2] = v[2];
@@ -396,10 +393,10 @@ __global__ __launch_bounds__(kQ8LutThreads) void quantize8_lut_kernel(const floa
 #pragma unroll
         for (int w = 0; w < kQ8LutThreads / 64; ++w)
             run += (w < (tid >> 6)) ? wave_tot[w] : 0u;
-        u32x4_t* const dst = reinterpret_cast<u32x4_t*>(lut + tid * 128);
+        u32x4* const dst = reinterpret_cast<u32x4*>(lut + tid * 128);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            u32x4_t o;
+            u32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 uint32_t x = d[4 * i + e];
@@ -496,7 +493,7 @@ __global__ __launch_bounds__(256) void dequantize8_kernel(const float* __restric
                 for (int j = 0; j < 4; ++j)
                     v[j] = rounded_f32(lut[(q4[u] >> (8 * j)) & 0xFFu] * s[u]);
                 if constexpr (sizeof(T) == 4) {
-                    stream_store<true>((f32x4_t{v[0], v[1], v[2], v[3]}), reinterpret_cast<f32x4_t*>(out + i));
+                    stream_store<true>((f32x4{v[0], v[1], v[2], v[3]}), reinterpret_cast<f32x4*>(out + i));
                 } else {
                     typedef T v4 __attribute__((ext_vector_type(4)));
                     v4 r;

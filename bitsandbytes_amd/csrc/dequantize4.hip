@@ -38,15 +38,14 @@ template <typename T, bool NT> __device__ __forceinline__ void store8(T* __restr
             r[i] = static_cast<T>(v[i]);
         stream_store<NT>(r, reinterpret_cast<V*>(out + base));
     } else {
-        using V = __attribute__((ext_vector_type(4))) float;
-        V r0, r1;
+        f32x4 r0, r1;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             r0[i] = v[i];
             r1[i] = v[4 + i];
         }
-        stream_store<NT>(r0, reinterpret_cast<V*>(out + base));
-        stream_store<NT>(r1, reinterpret_cast<V*>(out + base + 4));
+        stream_store<NT>(r0, reinterpret_cast<f32x4*>(out + base));
+        stream_store<NT>(r1, reinterpret_cast<f32x4*>(out + base + 4));
     }
 }
 
@@ -171,15 +170,14 @@ __global__ __launch_bounds__(kDqThreads) void dequantize4_f32_lines_kernel(const
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const long base = tile_base + (static_cast<long>(u) * kDqThreads + tid) * 4;
-        using V = __attribute__((ext_vector_type(4))) float;
-        V r;
+        f32x4 r;
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
             const uint32_t byte = (static_cast<uint32_t>(w[u]) >> (8 * b)) & 0xFFu;
             r[2 * b] = rounded_f32(code[byte >> 4] * s[u]);
             r[2 * b + 1] = rounded_f32(code[byte & 0xF] * s[u]);
         }
-        stream_store<true>(r, reinterpret_cast<V*>(out + base));
+        stream_store<true>(r, reinterpret_cast<f32x4*>(out + base));
     }
 }
 
@@ -279,15 +277,14 @@ __global__ __launch_bounds__(kDqThreads) void dequantize4_rows_kernel(const uint
         for (int u = 0; u < 2; ++u) {
             if (col2[u] >= row_len)
                 continue;
-            using V = __attribute__((ext_vector_type(4))) float;
-            V r;
+            f32x4 r;
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
                 const uint32_t byte = (static_cast<uint32_t>(w2[u]) >> (8 * b)) & 0xFFu;
                 r[2 * b] = valid ? rounded_f32(code[byte >> 4] * s2[u]) : __builtin_nanf("");
                 r[2 * b + 1] = valid ? rounded_f32(code[byte & 0xF] * s2[u]) : __builtin_nanf("");
             }
-            *reinterpret_cast<V*>(out + t * row_len + col2[u]) = r;
+            *reinterpret_cast<f32x4*>(out + t * row_len + col2[u]) = r;
         }
         return;
     }

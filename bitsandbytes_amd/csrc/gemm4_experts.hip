@@ -33,10 +33,6 @@ namespace bnb {
 
 namespace {
 
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 constexpr int kSegK = 2048;      // k covered by one wavefront-wide 16-byte load
 constexpr int kLutBytes = 65536; // 256 entries x 32 copies x 8 B
 constexpr int kCode2Bytes = 1024;
@@ -101,24 +97,6 @@ template <> __device__ __forceinline__ void load_x32<float>(const float* src, f3
         dst[2 * q] = f32x2{v[0], v[1]};
         dst[2 * q + 1] = f32x2{v[2], v[3]};
     }
-}
-
-__device__ __forceinline__ float code_literal_rt(bool fp4, int i) {
-    // a compare/select tree over literals: no memory access in front of the table build
-    constexpr float nf4[16] = {BNB_NF4_VALUES};
-    constexpr float fp4v[16] = {BNB_FP4_VALUES};
-    float v = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        v = (i == j) ? (fp4 ? fp4v[j] : nf4[j]) : v;
-    return v;
-}
-
-// An fp32 intermediate that is rounded to fp32 BEFORE it is converted to T: without it the compiler folds `T(a * b)` of fp16
-// instances into v_fma_mixlo_f16, which rounds the exact product once - not what two torch kernels (and the plain form) compute.
-__device__ __forceinline__ float rounded_f32(float v) {
-    asm volatile("" : "+v"(v));
-    return v;
 }
 
 __device__ __forceinline__ long long load_id(const void* ids, int idx64, int i) {
@@ -363,12 +341,12 @@ template <typename T, bool NESTED, int EPI = kEpiPlain> __global__ __launch_boun
             // decode table: entry e8 (a packed byte) = 32 copies of (code[e8 >> 4], code[e8 & 15]) in fp32, 256 B per entry, copy c
             // at byte 8 c. 16-byte chunk c16 = it * 512 + tid holds two copies of entry it * 32 + (tid >> 4): the high code is
             // a literal of the pass, the low one a per-thread constant; every ds_write_b128 of a wavefront covers 1 KiB.
-            const float lo = code_literal_rt(p.fp4 != 0, (tid >> 4) & 15);
+            const float lo = code_literal((tid >> 4) & 15, p.fp4 != 0);
             constexpr int kIters = kLutBytes / 16 / kThreads;
             static_assert(kThreads == 512 && kIters == 8, "chunk -> entry arithmetic below");
 #pragma unroll
             for (int it = 0; it < kIters; ++it) {
-                const float hi = (tid >> 8) ? code_literal_rt(p.fp4 != 0, 2 * it + 1) : code_literal_rt(p.fp4 != 0, 2 * it);
+                const float hi = (tid >> 8) ? code_literal(2 * it + 1, p.fp4 != 0) : code_literal(2 * it, p.fp4 != 0);
                 *reinterpret_cast<f32x4*>(smem + (it * kThreads + tid) * 16) = f32x4{hi, lo, hi, lo};
             }
             if constexpr (NESTED) {

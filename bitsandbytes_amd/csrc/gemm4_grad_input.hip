@@ -36,39 +36,6 @@ namespace bnb {
 
 namespace {
 
-using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-template <typename T> struct GiMma;
-template <> struct GiMma<bf16> {
-    using frag = __attribute__((ext_vector_type(8))) bf16;
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float first, float second) {
-        using V = __attribute__((ext_vector_type(2))) bf16;
-        V v;
-        v[0] = static_cast<bf16>(first);
-        v[1] = static_cast<bf16>(second);
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-template <> struct GiMma<f16> {
-    using frag = __attribute__((ext_vector_type(8))) f16;
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float first, float second) {
-        using V = __attribute__((ext_vector_type(2))) f16;
-        V v;
-        v[0] = static_cast<f16>(first);
-        v[1] = static_cast<f16>(second);
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-
 constexpr int kGiCols = 128;      // k-columns per workgroup = per wavefront (16 lanes x 8)
 constexpr int kGiMaxRows = 64;    // batch rows per workgroup: 16 MT, MT = 1, 2 or 4 MFMA row tiles (template parameter)
 constexpr int kGiBlockN = 32;     // n per wavefront block (one MFMA reduction: 4 lane groups x 8)
@@ -103,16 +70,6 @@ struct GiArgs {
     void* out;
     float* ws; // fp32 [nslices][M][K] partial slabs when nslices > 1
 };
-
-__device__ __forceinline__ float gi_code_literal(int i, bool fp4) {
-    constexpr float nf4[16] = {BNB_NF4_VALUES};
-    constexpr float fp4v[16] = {BNB_FP4_VALUES};
-    float v = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        v = (i == j) ? (fp4 ? fp4v[j] : nf4[j]) : v;
-    return v;
-}
 
 // grid = (K / 128, nslices, ceil(M / (16 MT))); 512 threads
 template <typename T, bool NESTED, int MT>
@@ -203,7 +160,7 @@ __global__ __launch_bounds__(kGiWaves * 64) void gemm4_grad_input_kernel(
     // in fp32, 256 B per entry; thread (half, e) writes 8 of its 16 chunks in an order rotated by e (eight lanes -> eight
     // bank quads)
     {
-        const float cv = gi_code_literal((lane & 15) + opaque_zero(), fp4);
+        const float cv = code_literal((lane & 15) + opaque_zero(), fp4);
         const int cvb = __builtin_bit_cast(int, cv);
         constexpr int PER = 16 * 256 / (kGiWaves * 64); // 16-byte chunks of an entry per thread
         const int e = tid & 255, part = tid >> 8;
@@ -306,13 +263,13 @@ __global__ __launch_bounds__(kGiWaves * 64) void gemm4_grad_input_kernel(
                     p0 = f32x2{a0, a1};
                     p1 = f32x2{b0, b1};
                 }
-                bx[d] = GiMma<T>::pack(p0[0], p1[0]);
-                by[d] = GiMma<T>::pack(p0[1], p1[1]);
+                bx[d] = Mma16x16x32<T>::pack(p0[0], p1[0]);
+                by[d] = Mma16x16x32<T>::pack(p0[1], p1[1]);
             }
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
-                acc[mt][2 * b] = GiMma<T>::run(af[mt], bx, acc[mt][2 * b]);
-                acc[mt][2 * b + 1] = GiMma<T>::run(af[mt], by, acc[mt][2 * b + 1]);
+                acc[mt][2 * b] = Mma16x16x32<T>::run(af[mt], bx, acc[mt][2 * b]);
+                acc[mt][2 * b + 1] = Mma16x16x32<T>::run(af[mt], by, acc[mt][2 * b + 1]);
             }
         }
         if (it < 3)

@@ -39,40 +39,6 @@ thread_local TlsKnob g_mfma_knob1{0}; // 100 * cfg + K-slice count (0 = heuristi
 
 namespace {
 
-using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-template <typename T> struct Mma;
-template <> struct Mma<bf16> {
-    using frag = __attribute__((ext_vector_type(8))) bf16;
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0,
-                                                       0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float lo, float hi) {
-        using V = __attribute__((ext_vector_type(2))) bf16;
-        V v;
-        v[0] = static_cast<bf16>(lo);
-        v[1] = static_cast<bf16>(hi);
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-template <> struct Mma<f16> {
-    using frag = __attribute__((ext_vector_type(8))) f16;
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0,
-                                                      0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float lo, float hi) {
-        using V = __attribute__((ext_vector_type(2))) f16;
-        V v;
-        v[0] = static_cast<f16>(lo);
-        v[1] = static_cast<f16>(hi);
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-
 struct GemmArgs {
     const void* A;
     const uint8_t* B;
@@ -117,9 +83,6 @@ typedef __attribute__((address_space(3))) void* dma_dst_t;
 //   * an A fragment is read once per (m-tile, k-step) and used for the wavefront's NTW n-tiles.
 // K slices across workgroups write fp32 slabs; gemm4_finalize_kernel adds them.
 // ---------------------------------------------------------------------------------------------
-template <int kCount> __device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kCount) : "memory");
-}
 
 // kPcProducers wavefronts share the A-tile DMA issue: one LDS-DMA instruction costs its issuing wavefront
 // ~100-180 cycles while the CU is busy, so a single producer needs > 3000 cycles for the 32 pieces of a
@@ -206,7 +169,7 @@ __global__ __launch_bounds__((CW + kPcProducers) * 64) void gemm4_mfma_pc_kernel
         if (n > 1)
             issue_a(c_begin + 1, 1);
         {
-            const uint32_t pr = Mma<T>::pack(code_hi, code_lo);
+            const uint32_t pr = Mma16x16x32<T>::pack(code_hi, code_lo);
             const u32x4 v = {pr, pr, pr, pr};
             u32x4* dst = reinterpret_cast<u32x4*>(&lut[e * 32]);
 #pragma unroll
@@ -217,9 +180,9 @@ __global__ __launch_bounds__((CW + kPcProducers) * 64) void gemm4_mfma_pc_kernel
         }
         for (int k = 0; k < n; ++k) {
             if (k == 0 && n > 1)
-                wait_vmcnt<XIP>(); // this producer's part of A(0) landed, A(1) may still be in flight
+                wait_vm<XIP>(); // this producer's part of A(0) landed, A(1) may still be in flight
             else
-                wait_vmcnt<0>();
+                wait_vm<0>();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // table written (first time)
             __builtin_amdgcn_s_barrier(); // #k
             if (k >= 1 && k + 1 < n)
@@ -318,15 +281,15 @@ __global__ __launch_bounds__((CW + kPcProducers) * 64) void gemm4_mfma_pc_kernel
             const bool first = STAGGER && (j == 0) && (k0 == 0); // (j is a constant of the unrolled copy: the extra code exists once)
             const int younger = first ? 0 : ((n - 1 - k < D - 1) ? n - 1 - k : D - 1); // (chunk 0: nothing else is in flight yet)
             if (younger <= 0)
-                wait_vmcnt<0>();
+                wait_vm<0>();
             else if (younger == 1)
-                wait_vmcnt<1 * LPC>();
+                wait_vm<1 * LPC>();
             else if (younger == 2)
-                wait_vmcnt<(D > 2 ? 2 : 1) * LPC>();
+                wait_vm<(D > 2 ? 2 : 1) * LPC>();
             else if (younger == 3)
-                wait_vmcnt<(D > 3 ? 3 : 1) * LPC>();
+                wait_vm<(D > 3 ? 3 : 1) * LPC>();
             else
-                wait_vmcnt<(D > 4 ? 4 : 1) * LPC>();
+                wait_vm<(D > 4 ? 4 : 1) * LPC>();
             if (k < 4)
                 BNB_PC_STAMP(2 + 3 * k)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -417,8 +380,8 @@ __global__ __launch_bounds__((CW + kPcProducers) * 64) void gemm4_mfma_pc_kernel
                 for (int t = 0; t < NTW; ++t)
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt) {
-                        part[st][mt][t] = Mma<T>::run(af[mt][0], bf[st][t][0], f32x4{0.f, 0.f, 0.f, 0.f});
-                        part[st][mt][t] = Mma<T>::run(af[mt][1], bf[st][t][1], part[st][mt][t]);
+                        part[st][mt][t] = Mma16x16x32<T>::run(af[mt][0], bf[st][t][0], f32x4{0.f, 0.f, 0.f, 0.f});
+                        part[st][mt][t] = Mma16x16x32<T>::run(af[mt][1], bf[st][t][1], part[st][mt][t]);
                     }
                 __builtin_amdgcn_sched_barrier(0);
                 // (3) the A fragments of block b+1 are read while the matrix pipe works on block b

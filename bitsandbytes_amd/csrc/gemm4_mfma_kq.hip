@@ -32,40 +32,6 @@ namespace bnb {
 
 namespace {
 
-using i32x4 = __attribute__((ext_vector_type(4))) int;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-template <typename T> struct KqMma;
-template <> struct KqMma<bf16> {
-    using frag = __attribute__((ext_vector_type(8))) bf16;
-    static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float first, float second) {
-        using V = __attribute__((ext_vector_type(2))) bf16;
-        V v;
-        v[0] = static_cast<bf16>(first);
-        v[1] = static_cast<bf16>(second);
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-template <> struct KqMma<f16> {
-    using frag = __attribute__((ext_vector_type(8))) f16;
-    static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float first, float second) {
-        using V = __attribute__((ext_vector_type(2))) f16;
-        V v;
-        v[0] = static_cast<f16>(first);
-        v[1] = static_cast<f16>(second);
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-
 constexpr int kKqCols = 128;   // output columns per workgroup: 2 column groups of 64
 constexpr int kKqChunk = 256;  // k per chunk: one 64-k quantization block per K quarter
 constexpr int kKqWaves = 8;    // 2 column groups x 4 K quarters
@@ -110,44 +76,6 @@ struct KqArgs {
 #define BNB_KQ_STAMP(i) {}
 #endif
 
-__device__ __forceinline__ float kq_code_literal(int i, bool fp4) {
-    // compare/select over literals: no memory access in front of the table
-    constexpr float nf4[16] = {BNB_NF4_VALUES};
-    constexpr float fp4v[16] = {BNB_FP4_VALUES};
-    float v = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        v = (i == j) ? (fp4 ? fp4v[j] : nf4[j]) : v;
-    return v;
-}
-
-// LDS-DMA, spelled out (the compiler's own tracking of buffer_load ... lds makes every later ds_read wait for ALL outstanding
-// DMA): the hand-off is by counted waits + s_barrier (see the chunk loop). LDS base and scalar offset are wavefront-uniform.
-__device__ __forceinline__ i32x4 kq_rsrc(const void* base) {
-    const uint64_t a = reinterpret_cast<uint64_t>(base);
-    return i32x4{static_cast<int>(a), static_cast<int>((a >> 32) & 0xFFFFu), 0x7FFFFFFF, 0x00020000};
-}
-__device__ __forceinline__ void kq_dma16(i32x4 rs, uint32_t lds, uint32_t voff, uint32_t soff) {
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds), "v"(voff), "s"(rs), "s"(soff) : "memory", "m0");
-}
-// (weights: read once, by one CU - the non-temporal policy shortens issue -> landed by ~18 %, MI355X guide "nt-weights")
-__device__ __forceinline__ void kq_dma16_nt(i32x4 rs, uint32_t lds, uint32_t voff, uint32_t soff) {
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen nt lds" ::"s"(lds), "v"(voff), "s"(rs), "s"(soff) : "memory", "m0");
-}
-__device__ __forceinline__ void kq_dma4(i32x4 rs, uint32_t lds, uint32_t voff) {
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds" ::"s"(lds), "v"(voff), "s"(rs) : "memory", "m0");
-}
-__device__ __forceinline__ void kq_dma1(i32x4 rs, uint32_t lds, uint32_t voff) {
-    // one byte per lane, landing in the lane's dword slot (the other three bytes are not defined: the reader masks)
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_ubyte %1, %2, 0 offen lds" ::"s"(lds), "v"(voff), "s"(rs) : "memory", "m0");
-}
-template <int N> __device__ __forceinline__ void kq_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void kq_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -215,7 +143,7 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
 
     // ---- sources. Rows past the end (ragged N or M) re-read the last row: MFMA rows / columns are independent and those
     // results are never stored. All byte offsets are < 2^31 (gemm_4bit_kq_supported).
-    const i32x4 rs_w = kq_rsrc(hot_B), rs_a = kq_rsrc(hot_A), rs_s = kq_rsrc(hot_absmax), rs_q = kq_rsrc(hot_absmax8);
+    const i32x4 rs_w = buffer_rsrc(hot_B), rs_a = buffer_rsrc(hot_A), rs_s = buffer_rsrc(hot_absmax), rs_q = buffer_rsrc(hot_absmax8);
     uint32_t lo_a[AI], lo_w[2];
 #pragma unroll
     for (int t = 0; t < AI; ++t) {
@@ -260,7 +188,7 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
         const uint32_t so = static_cast<uint32_t>(cb + (u >> 1)) * 512u + static_cast<uint32_t>(u & 1) * 256u;
 #pragma unroll
         for (int t = 0; t < AI; ++t)
-            kq_dma16(rs_a, static_cast<uint32_t>(L::ABase + slot * L::AHB + (wi + 4 * t) * 1024), lo_a[t], so);
+            lds_dma16(rs_a, static_cast<uint32_t>(L::ABase + slot * L::AHB + (wi + 4 * t) * 1024), lo_a[t], so);
     };
     auto issue_w = [&](int u, int slot, int t) {
         u = u < H ? u : H - 1;
@@ -268,9 +196,9 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
         // (the non-temporal policy, which shortens issue -> landed where a CU fetches whole lines once, costs 25 % here: the two
         // 64-byte halves of a line are requested a phase apart, by different wavefronts - profiles/r4_kq_variants.txt)
         if constexpr ((ABL & 128) != 0)
-            kq_dma16_nt(rs_w, static_cast<uint32_t>(L::WBase + slot * L::WHB + (wi + 4 * t) * 1024), lo_w[t], so);
+            lds_dma16_nt(rs_w, static_cast<uint32_t>(L::WBase + slot * L::WHB + (wi + 4 * t) * 1024), lo_w[t], so);
         else
-            kq_dma16(rs_w, static_cast<uint32_t>(L::WBase + slot * L::WHB + (wi + 4 * t) * 1024), lo_w[t], so);
+            lds_dma16(rs_w, static_cast<uint32_t>(L::WBase + slot * L::WHB + (wi + 4 * t) * 1024), lo_w[t], so);
     };
     // scales of chunk cs (of the slice) into ring slot cs % 3: this group's columns, this wavefront's part
     auto issue_s = [&](int cs, int slot) {
@@ -281,15 +209,15 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
             const uint32_t blk = lo_s + ca * 4u;
             if constexpr (NESTED) {
                 if (wi == 0)
-                    kq_dma4(rs_q, base + static_cast<uint32_t>(g) * 256u, blk);
+                    lds_dma4(rs_q, base + static_cast<uint32_t>(g) * 256u, blk);
             } else {
                 if (wi == 0)
-                    kq_dma16(rs_s, base + static_cast<uint32_t>(g) * 1024u, blk * 4u, 0u);
+                    lds_dma16(rs_s, base + static_cast<uint32_t>(g) * 1024u, blk * 4u, 0u);
             }
         } else {
             static_assert(SFAST || !NESTED, "nested statistics take the fast form (the host routes the other cases elsewhere)");
             const uint32_t blk = (lo_s + ca * 256u) >> bs_shift;
-            kq_dma4(rs_s, base + static_cast<uint32_t>(g) * 1024u + static_cast<uint32_t>(wi) * 256u, blk * 4u);
+            lds_dma4(rs_s, base + static_cast<uint32_t>(g) * 1024u + static_cast<uint32_t>(wi) * 256u, blk * 4u);
         }
     };
     auto issue_w2 = [&](int u, int slot) {
@@ -306,7 +234,7 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
         // (the second-level code table, 256 floats: one dword DMA by each wavefront of group 1; an ordinary load here would
         // make the compiler drain the queue)
         if (g == 1)
-            kq_dma4(kq_rsrc(p.absmax_code), static_cast<uint32_t>(L::Code2 + wi * 256), lane4 + static_cast<uint32_t>(wi) * 256u);
+            lds_dma4(buffer_rsrc(p.absmax_code), static_cast<uint32_t>(L::Code2 + wi * 256), lane4 + static_cast<uint32_t>(wi) * 256u);
         // second-level absmax: entries idx0 and idx0 + 1 of every column, idx0 = index of the 256-block group of the slice's
         // first block in that column (wavefronts 0 / 1 of group g: candidate 0 / 1 of columns 64 g ..)
         if (wi < 2) {
@@ -315,7 +243,7 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
             uint32_t idx = ((static_cast<uint32_t>(col) * static_cast<uint32_t>(K >> 6) + static_cast<uint32_t>(cb) * 4u) >> 8) + static_cast<uint32_t>(wi);
             const uint32_t last = (static_cast<uint32_t>(N) * static_cast<uint32_t>(K >> 6) - 1u) >> 8;
             idx = idx < last ? idx : last;
-            kq_dma4(rs_s, static_cast<uint32_t>(L::A2T + wi * 512 + g * 256), idx * 4u);
+            lds_dma4(rs_s, static_cast<uint32_t>(L::A2T + wi * 512 + g * 256), idx * 4u);
         }
     }
     issue_s(0, 0);
@@ -349,12 +277,12 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
     {
         // decode table: entry e (a packed byte) = 64 copies of T2(code[e >> 4], code[e & 15]), 256 B per entry; the two halves
         // of the workgroup write 8 of its 16 16-byte chunks each, in an order rotated by e (eight lanes -> eight bank quads)
-        const float cv = kq_code_literal((lane & 15) + opaque_zero(), fp4);
+        const float cv = code_literal((lane & 15) + opaque_zero(), fp4);
         const int cvb = __builtin_bit_cast(int, cv);
         const int e = tid & 255;
         const float hi = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(((e >> 4) & 15) * 4, cvb));
         const float lov = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((e & 15) * 4, cvb));
-        const uint32_t pr = KqMma<T>::pack(hi, lov);
+        const uint32_t pr = Mma32x32x16<T>::pack(hi, lov);
         const u32x4 v = {pr, pr, pr, pr};
         u32x4* const dst = reinterpret_cast<u32x4*>(smem + e * 256);
         const int half = tid >> 8;
@@ -546,7 +474,7 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
                     part[nt][mt] = z;
                 }
                 if (BNB_KQ_ON(8))
-                    part[nt][mt] = KqMma<T>::run(afr[s][mt], bfr[f % 3], part[nt][mt]);
+                    part[nt][mt] = Mma32x32x16<T>::run(afr[s][mt], bfr[f % 3], part[nt][mt]);
                 // in the shadow of the MFMA: half (all, with one row tile) of the look-ups of fragment f + 2; one of the phase's
                 // weight / scale requests; once tile 0 is complete (f >= 4), its scale FMAs
                 if (f + 2 < 8) {
@@ -588,11 +516,11 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
         // that the group reads in its next load phase, and the weight half it reads there (requested two compute phases ago)
         if constexpr (ISSUE_W) {
             if (s_extra)
-                kq_wait_vm<3>();
+                wait_vm<3>();
             else
-                kq_wait_vm<2>();
+                wait_vm<2>();
         } else {
-            kq_wait_vm<0>(); // (the tail of the slice: no weight requests behind the activation ones)
+            wait_vm<0>(); // (the tail of the slice: no weight requests behind the activation ones)
         }
         if constexpr (stamp)
             BNB_KQ_STAMP(4)
@@ -635,7 +563,7 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
     using cSt = std::integral_constant<bool, (ABL & 64) != 0>; // (the stamped instance of the measurement build stamps every iteration: the last one gets stored)
     if (g == 0) {
         // barrier -2: half 0 has landed (own part; everybody's behind the barrier), the table is written
-        kq_wait_vm<BATCH>();
+        wait_vm<BATCH>();
         kq_barrier();
         BNB_KQ_STAMP(7)
         load_a2();
@@ -669,12 +597,12 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
     } else {
         // barrier -2: this group's scale (and second-level) requests have landed - the other group's wavefronts read these columns
         // in the phase behind the barrier; [A1 W1][W3] may fly on
-        kq_wait_vm<AI + 4>();
+        wait_vm<AI + 4>();
         kq_barrier();
         BNB_KQ_STAMP(7)
         load_a2();
         // phase -1 (group 0 loads half 0): nothing to do but to make sure half 1 has landed
-        kq_wait_vm<2>();
+        wait_vm<2>();
         kq_barrier();
         int sa = 1, sw = 1, ss = 0; // slots of half 2 j + 1, of chunk j's scales
         auto advance = [&]() {
@@ -706,7 +634,7 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
     // registers are cut into four sets of 8 MT; wavefront (c, o) owns set o: it receives that set from the other three
     // quarters through the LDS (everything the loop used is dead: outstanding DMA of past-the-end chunks is drained first),
     // adds in the order q = 0..3 and stores. Area: [c][owner][3 sources][2 MT chunks of 16 B][64 lanes].
-    kq_wait_vm<0>();
+    wait_vm<0>();
     kq_barrier();
     constexpr int RS = 8 * MT; // registers of a set
     constexpr int CH = RS / 4; // 16-byte chunks of a set per lane
@@ -737,7 +665,7 @@ __global__ __launch_bounds__(kKqWaves * 64) void gemm4_mfma_kq_kernel(
                               ? p.out
                               : static_cast<void*>(p.ws + static_cast<long>(blockIdx.y) * slab_floats +
                                                    (static_cast<long>(blockIdx.z) * gridDim.x + blockIdx.x) * (4096 * MT));
-    const auto rs_o = __builtin_amdgcn_make_buffer_rsrc(st_base, 0, hot_kslices == 1 ? static_cast<int>(static_cast<uint32_t>(M) * row_bytes) : 16384 * MT, 0x00020000);
+    const auto rs_o = __builtin_amdgcn_make_buffer_rsrc(st_base, 0, hot_kslices == 1 ? static_cast<int>(static_cast<uint32_t>(M) * row_bytes) : 16384 * MT, kBufferFlags);
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
         if (q != o) {

@@ -37,37 +37,6 @@ namespace bnb {
 
 namespace {
 
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-template <typename T> struct RtMma;
-template <> struct RtMma<bf16> {
-    using frag = __attribute__((ext_vector_type(8))) bf16;
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float first, float second) {
-        using V = __attribute__((ext_vector_type(2))) bf16;
-        V v;
-        v[0] = static_cast<bf16>(first);
-        v[1] = static_cast<bf16>(second);
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-template <> struct RtMma<f16> {
-    using frag = __attribute__((ext_vector_type(8))) f16;
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float first, float second) {
-        using V = __attribute__((ext_vector_type(2))) f16;
-        V v;
-        v[0] = static_cast<f16>(first);
-        v[1] = static_cast<f16>(second);
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-
 constexpr int kRtLut = 32768;            // 256 entries x 32 copies x 4 B, at LDS address 0
 constexpr int kRtScratch = 2 * 1024 + 256; // per wavefront: two transposition tiles + the scale tile (16 x 16 B)
 constexpr int kRtScratch32 = kRtScratch + 256; // blocksize 32: eight scales per row and chunk - two scale tiles
@@ -94,17 +63,6 @@ struct RtArgs {
 #else
 #define BNB_RT_STAMP(i) {}
 #endif
-
-__device__ __forceinline__ float rt_code_literal(int i, bool fp4) {
-    // compare/select over literals: no memory access (the inner select is scalar)
-    constexpr float nf4[16] = {BNB_NF4_VALUES};
-    constexpr float fp4v[16] = {BNB_FP4_VALUES};
-    float v = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        v = (i == j) ? (fp4 ? fp4v[j] : nf4[j]) : v;
-    return v;
-}
 
 // T in {bf16, f16}; MT = 16-row tiles of the batch handled by one workgroup (the weights of a chunk are loaded, transposed
 // and decoded ONCE and multiplied with MT activation tiles in turn - while tile t is transposed and multiplied, the loads of
@@ -189,8 +147,8 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_rt_kernel(
     const long e0 = static_cast<long>(wrow) * K; // flat element index of the row start
     // (BL: byte offsets are 32-bit and stay below the descriptors' 2^31 records - gemm_4bit_rt_supported)
     constexpr uint32_t kOob = 0xFFFFFFF0u; // beyond num_records
-    const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(hot_B), 0, 0x7FFFFFFF, 0x00020000);
-    const auto rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(hot_A), 0, 0x7FFFFFFF, 0x00020000);
+    const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(hot_B), 0, kBufferWholeSpace, kBufferFlags);
+    const auto rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(hot_A), 0, kBufferWholeSpace, kBufferFlags);
     const uint32_t w_off = static_cast<uint32_t>(wrow) * static_cast<uint32_t>(K >> 1) + static_cast<uint32_t>(pp * 16);
     const uint32_t a_off = (static_cast<uint32_t>(m_base + arow_l) * static_cast<uint32_t>(K) + static_cast<uint32_t>(a_lane_k)) * static_cast<uint32_t>(sizeof(T));
 
@@ -289,7 +247,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_rt_kernel(
     {
         // (literals only: a caller-supplied code table would put a load - and at the join of the two paths a vmcnt(0)
         // that drains the weight loads - in front of the table; such calls go to the LDS-DMA kernels)
-        const float cv = rt_code_literal((lane & 15) + opaque_zero(), fp4);
+        const float cv = code_literal((lane & 15) + opaque_zero(), fp4);
         const int cvb = __builtin_bit_cast(int, cv);
         u32x4* const lut = reinterpret_cast<u32x4*>(smem);
         // (the wavefronts of a 16-wavefront workgroup start ~90 cycles apart and every one of them first pushes its loads
@@ -301,7 +259,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_rt_kernel(
             const int e = idx >> 2, sub = idx & 3;
             const float hi = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((e >> 4) * 4, cvb));
             const float lo = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((e & 15) * 4, cvb));
-            const uint32_t pr = RtMma<T>::pack(hi, lo);
+            const uint32_t pr = Mma16x16x32<T>::pack(hi, lo);
             const u32x4 v = {pr, pr, pr, pr};
             lut[e * 8 + ((2 * sub) ^ (e & 1))] = v;
             lut[e * 8 + ((2 * sub + 1) ^ (e & 1))] = v;
@@ -422,7 +380,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_rt_kernel(
                             bfr[s][q] = *reinterpret_cast<const __attribute__((address_space(3))) uint32_t*>((byte << 7) + lane_off);
                         }
                     }
-                    part = RtMma<T>::run(af, bfr[s], part);
+                    part = Mma16x16x32<T>::run(af, bfr[s], part);
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q)

@@ -39,38 +39,6 @@ namespace bnb {
 
 namespace {
 
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using i32x4 = __attribute__((ext_vector_type(4))) int;
-
-template <typename T> struct SmMma;
-template <> struct SmMma<bf16> {
-    using frag = __attribute__((ext_vector_type(8))) bf16;
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float first, float second) {
-        using V = __attribute__((ext_vector_type(2))) bf16;
-        V v;
-        v[0] = static_cast<bf16>(first);
-        v[1] = static_cast<bf16>(second);
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-template <> struct SmMma<f16> {
-    using frag = __attribute__((ext_vector_type(8))) f16;
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float first, float second) {
-        using V = __attribute__((ext_vector_type(2))) f16;
-        V v;
-        v[0] = static_cast<f16>(first);
-        v[1] = static_cast<f16>(second);
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-
 constexpr int kSmLut = 65536;    // 256 entries x 64 lane-private copies x 4 B, at LDS address 0: a table address is ONE v_perm_b32
 constexpr int kSmCode2 = 1024;   // nested absmax code (256 floats)
 constexpr int kSmScratch = 1536; // per wavefront: one transposition tile (1 KiB) + the scale tile (256 B), padded to 512 B
@@ -117,31 +85,6 @@ struct SmArgs {
 #define BNB_SM_STAMP(i) {}
 #endif
 
-__device__ __forceinline__ float sm_code_literal(int i, bool fp4) {
-    // compare/select over literals: no memory access in front of the table
-    constexpr float nf4[16] = {BNB_NF4_VALUES};
-    constexpr float fp4v[16] = {BNB_FP4_VALUES};
-    float v = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        v = (i == j) ? (fp4 ? fp4v[j] : nf4[j]) : v;
-    return v;
-}
-
-__device__ __forceinline__ i32x4 sm_rsrc(const void* base) {
-    const uint64_t a = reinterpret_cast<uint64_t>(base);
-    return i32x4{static_cast<int>(a), static_cast<int>((a >> 32) & 0xFFFFu), 0x7FFFFFFF, 0x00020000};
-}
-// LDS-DMA, spelled out: the compiler does not know that this is a vector-memory operation, so its own counted waits for the
-// weight ring stay counted (with the builtin it treats the counter as out of order: every register wait becomes vmcnt(0)).
-// An unseen DMA that is YOUNGER than a load the compiler waits for only makes that wait stricter; the waits for the DMAs
-// themselves are written by hand (sm_wait_vm) at the two places that read the staging area.
-__device__ __forceinline__ void sm_dma16(i32x4 rs, uint32_t lds, uint32_t voff, uint32_t soff) {
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds), "v"(voff), "s"(rs), "s"(soff) : "memory", "m0");
-}
-template <int N> __device__ __forceinline__ void sm_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void sm_wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // swizzle of the activation staging area: piece P (16 B = 8 k) of staged row m lives at piece P ^ swz(m) of the row's 512 B.
@@ -272,7 +215,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
 
     // ---- activation DMA: instruction i, lane L fills slot 64 i + L of the staging area = piece P' = L & 31 of staged row
     // m = 2 i + (L >> 5), and fetches piece P' ^ swz(m) of batch row m_base + m (rows past the batch: the last row again)
-    const i32x4 rs_a = sm_rsrc(hot_A);
+    const i32x4 rs_a = buffer_rsrc(hot_A);
     uint32_t a_voff[NA];
     int a_k[NA]; // k of the lane's piece inside the chunk
 #pragma unroll
@@ -295,14 +238,14 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
         const int tail = K - c * CKB;
 #pragma unroll
         for (int i = 0; i < NA; ++i)
-            sm_dma16(rs_a, stage_lds + static_cast<uint32_t>(i * 1024), a_voff[i] | (a_k[i] < tail ? 0u : kOob), static_cast<uint32_t>(c) * static_cast<uint32_t>(CKB * 2));
+            lds_dma16(rs_a, stage_lds + static_cast<uint32_t>(i * 1024), a_voff[i] | (a_k[i] < tail ? 0u : kOob), static_cast<uint32_t>(c) * static_cast<uint32_t>(CKB * 2));
     };
     if constexpr (NESTED) {
         // the second-level code table (256 floats): ONE 1-KiB DMA by wavefront 0, the oldest entry of its queue - the table's
         // address arrives in a preloaded argument, so nothing waits for the kernarg segment here. Landed behind the wait for the
         // first fragments, published by the barrier behind it.
         if (wave == 0)
-            sm_dma16(sm_rsrc(g_code2), static_cast<uint32_t>(kSmLut), static_cast<uint32_t>(lane) * 16u, 0u);
+            lds_dma16(buffer_rsrc(g_code2), static_cast<uint32_t>(kSmLut), static_cast<uint32_t>(lane) * 16u, 0u);
     }
     // ORDER (experiment, single-item instances): 0 = activations first (the DMAs are the oldest entries: fragments in registers
     // before the weights land), 1 = weights first (every wavefront's weight requests go out before anybody's activation requests;
@@ -317,9 +260,9 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
         uint32_t s;  // lane (r, pp): the fp32 absmax of 64-k sub-block pp of row r's chunk (nested: its 8-bit code)
         uint32_t s2; // nested: the second-level absmax of that block
     };
-    const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(g_B), 0, 0x7FFFFFFF, 0x00020000);
-    const auto rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g_absmax), 0, 0x7FFFFFFF, 0x00020000);
-    [[maybe_unused]] const auto rs_q = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(g_absmax8), 0, 0x7FFFFFFF, 0x00020000);
+    const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(g_B), 0, kBufferWholeSpace, kBufferFlags);
+    const auto rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g_absmax), 0, kBufferWholeSpace, kBufferFlags);
+    [[maybe_unused]] const auto rs_q = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(g_absmax8), 0, kBufferWholeSpace, kBufferFlags);
     // item q of this wavefront = (chunk q / TT of its list, tile q % TT). Every load is branch-free: an item past the end of
     // the list, and a tile row past the end of the workgroup's rows, is an out-of-range offset (zeros, nothing fetched).
     auto issue = [&](Stage& st, int q) {
@@ -360,12 +303,12 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
         // (the wavefronts of a 16-wavefront workgroup start ~90 cycles apart: the early half builds the table)
         constexpr int BUILD_THREADS = 512;
         if (tid < BUILD_THREADS) {
-            const float cv = sm_code_literal((lane & 15) + opaque_zero(), fp4);
+            const float cv = code_literal((lane & 15) + opaque_zero(), fp4);
             const int cvb = __builtin_bit_cast(int, cv);
             const int e = tid & 255;
             const float hi = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(((e >> 4) & 15) * 4, cvb));
             const float lov = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((e & 15) * 4, cvb));
-            const uint32_t pr = SmMma<T>::pack(hi, lov);
+            const uint32_t pr = Mma16x16x32<T>::pack(hi, lov);
             const u32x4 v = {pr, pr, pr, pr};
             u32x4* const dst = reinterpret_cast<u32x4*>(smem + e * 256);
             const int half = tid >> 8;
@@ -435,9 +378,9 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
         __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (ORDER == 1)
-        sm_wait_vm<0>();
+        wait_vm<0>();
     else
-        sm_wait_vm<NS * LPS>();
+        wait_vm<NS * LPS>();
     BNB_SM_STAMP(3)
     read_frags();
     if constexpr (!SINGLE) {
@@ -448,7 +391,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
     }
     BNB_SM_STAMP(4)
 #ifdef BNB_PROFILING
-    sm_wait_vm<(NS - 1) * LPS + (SINGLE ? 0 : NA)>(); // (measurement build: when the first ring stage has landed; exact with >= 2 chunks)
+    wait_vm<(NS - 1) * LPS + (SINGLE ? 0 : NA)>(); // (measurement build: when the first ring stage has landed; exact with >= 2 chunks)
     BNB_SM_STAMP(6)
 #endif
 
@@ -523,8 +466,8 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
                 for (int rb = 0; rb < RB; ++rb) {
                     // (32 rows: fragment steps 4 rb + 2 blk, + 1 - the row block's half of the virtual rows)
                     f32x4 part = {0.f, 0.f, 0.f, 0.f};
-                    part = SmMma<T>::run(af[4 * rb * (RB - 1) + 2 * blk], bf[2 * blk - g0], part);
-                    part = SmMma<T>::run(af[4 * rb * (RB - 1) + 2 * blk + 1], bf[2 * blk + 1 - g0], part);
+                    part = Mma16x16x32<T>::run(af[4 * rb * (RB - 1) + 2 * blk], bf[2 * blk - g0], part);
+                    part = Mma16x16x32<T>::run(af[4 * rb * (RB - 1) + 2 * blk + 1], bf[2 * blk + 1 - g0], part);
 #pragma unroll
                     for (int qq = 0; qq < 4; ++qq)
                         accv[rb][qq] = fmaf(sb, part[qq], accv[rb][qq]);
@@ -554,7 +497,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
                 if (t == 0 && q > 0 && q < nitems) {
                     // first item of the wavefront's next chunk: its fragments were requested when the previous chunk's were read,
                     // behind at most the ring stage about to be consumed and in front of the other one
-                    sm_wait_vm<LPS>();
+                    wait_vm<LPS>();
                     read_frags();
                     if (q / TT + 1 < nchunks) {
                         sm_wait_lgkm0();
@@ -613,7 +556,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
                 const int v = __builtin_amdgcn_readlane(ad, i);
                 present |= v < 64 ? (1ull << v) : 0ull;
             }
-            const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(lo_t), 0, 0x7FFFFFFF, 0x00020000);
+            const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(lo_t), 0, kBufferWholeSpace, kBufferFlags);
             const int lm = m_base + ln, lnrow = row0 + 16 * wave + ln;
             f32x4 keep = {0.f, 0.f, 0.f, 0.f};
             while (present != 0) {
@@ -621,8 +564,8 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
                 present &= present - 1;
                 const uint32_t selm = static_cast<uint32_t>(__builtin_amdgcn_ballot_w64(lane < 16 && ad == a)); // bit m: row m_base + m has adapter a
                 const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(
-                    reinterpret_cast<void*>(lo_b + static_cast<uint64_t>(a) * static_cast<uint64_t>(N) * static_cast<uint64_t>(lo_r) * 2u), 0, 0x7FFFFFFF,
-                    0x00020000);
+                    reinterpret_cast<void*>(lo_b + static_cast<uint64_t>(a) * static_cast<uint64_t>(N) * static_cast<uint64_t>(lo_r) * 2u), 0, kBufferWholeSpace,
+                    kBufferFlags);
                 const uint32_t inv_m = ((selm >> ln) & 1u) ? 0u : kOob;
                 u32x4 ta[4], tb[4];
 #pragma unroll
@@ -637,7 +580,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
                     if (32 * s < lo_r) // (wave-uniform)
-                        lacc = SmMma<T>::run(ta[s], tb[s], lacc);
+                        lacc = Mma16x16x32<T>::run(ta[s], tb[s], lacc);
                 // accumulator layout: lane (ln, lg) holds batch rows 4 lg ... 4 lg + 3 of weight column ln
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
@@ -650,8 +593,8 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
         if (wave < TT) {
             // operand shape of v_mfma_f32_16x16x32: lane (ln, lg) holds 8 consecutive k of row ln - batch row ln of t, weight row ln of the
             // tile - from k = 32 s + 8 lg; both operands use the same k, which is all the product needs
-            const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(lo_t), 0, 0x7FFFFFFF, 0x00020000);
-            const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(lo_b), 0, 0x7FFFFFFF, 0x00020000);
+            const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(lo_t), 0, kBufferWholeSpace, kBufferFlags);
+            const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(lo_b), 0, kBufferWholeSpace, kBufferFlags);
             const int lm = m_base + ln, lnrow = row0 + 16 * wave + ln;
             u32x4 ta[4], tb[4];
 #pragma unroll
@@ -667,7 +610,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm4_mfma_sm_kernel(
 #pragma unroll
             for (int s = 0; s < 4; ++s)
                 if (32 * s < lo_r) // (wave-uniform)
-                    lacc = SmMma<T>::run(ta[s], tb[s], lacc);
+                    lacc = Mma16x16x32<T>::run(ta[s], tb[s], lacc);
             *reinterpret_cast<f32x4*>(smem + kLoraLds + wave * 1024 + lane * 16) = lacc;
         }
     }

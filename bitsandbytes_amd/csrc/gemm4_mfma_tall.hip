@@ -29,40 +29,6 @@ namespace bnb {
 
 namespace {
 
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using i32x4 = __attribute__((ext_vector_type(4))) int;
-
-template <typename T> struct TallMma;
-template <> struct TallMma<bf16> {
-    using frag = __attribute__((ext_vector_type(8))) bf16;
-    static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float first, float second) {
-        using V = __attribute__((ext_vector_type(2))) bf16;
-        V v;
-        v[0] = static_cast<bf16>(first);
-        v[1] = static_cast<bf16>(second);
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-template <> struct TallMma<f16> {
-    using frag = __attribute__((ext_vector_type(8))) f16;
-    static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float first, float second) {
-        using V = __attribute__((ext_vector_type(2))) f16;
-        V v;
-        v[0] = static_cast<f16>(first);
-        v[1] = static_cast<f16>(second);
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-
 constexpr int kTallLut = 65536;   // 256 entries x 32 copies x 8 B (two fp32 code values), at LDS address 0
 constexpr int kTallCode2 = 1024;  // nested absmax code
 constexpr int kTallStage = 16384; // one [128][64] 16-bit tile
@@ -79,30 +45,11 @@ struct TallArgs {
     const void* bias;
 };
 
-__device__ __forceinline__ float tall_code_literal(int i, bool fp4) {
-    constexpr float nf4[16] = {BNB_NF4_VALUES};
-    constexpr float fp4v[16] = {BNB_FP4_VALUES};
-    float v = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        v = (i == j) ? (fp4 ? fp4v[j] : nf4[j]) : v;
-    return v;
-}
-
-__device__ __forceinline__ i32x4 tall_rsrc(const void* base) {
-    const uint64_t a = reinterpret_cast<uint64_t>(base);
-    return i32x4{static_cast<int>(a), static_cast<int>((a >> 32) & 0xFFFFu), 0x7FFFFFFF, 0x00020000};
-}
 // piece swizzle of a tile row: bits (row0 ^ row1) | row2 << 1 | row3 << 2 - found by exhaustive search over the linear maps of the
 // row index: the fragment reads (ds_read_b128, 16-lane service groups) AND the decoder's writes (ds_write_b128, 8 contiguous lanes =
 // 2 rows x 4 quarters) are bank-conflict-free
 __device__ __forceinline__ int tall_swz(int row) { return ((row ^ (row >> 1)) & 1) | (((row >> 2) & 1) << 1) | (((row >> 3) & 1) << 2); }
 
-__device__ __forceinline__ void tall_dma16(i32x4 rs, uint32_t lds, uint32_t voff, uint32_t soff) {
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds), "v"(voff), "s"(rs), "s"(soff) : "memory", "m0");
-}
 // register loads spelled in asm: the compiler inserts no wait for them - every wait is written by hand (tall_wait), tied to the
 // registers it releases
 __device__ __forceinline__ u32x4 tall_load16(i32x4 rs, uint32_t voff, uint32_t soff) {
@@ -154,7 +101,7 @@ __global__ __launch_bounds__(512) void gemm4_mfma_tall_kernel(const void* hot_A,
 
     // ---- per-lane sources
     // activations: instruction i = 2 wave + j of a stage covers rows 8 i ... 8 i + 7; lane = (row 8 i + (lane >> 3), piece' = lane & 7)
-    const i32x4 rs_a = tall_rsrc(static_cast<const unsigned char*>(hot_A) + static_cast<size_t>(m0) * K * sizeof(T));
+    const i32x4 rs_a = buffer_rsrc(static_cast<const unsigned char*>(hot_A) + static_cast<size_t>(m0) * K * sizeof(T));
     uint32_t a_voff[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -169,10 +116,10 @@ __global__ __launch_bounds__(512) void gemm4_mfma_tall_kernel(const void* hot_A,
     nrow = nrow < N ? nrow : N - 1;
     // (descriptors are wave-uniform: the row offset goes into the per-lane offset, relative to the tile's first row)
     const int n0c = n0 < N ? n0 : N - 1;
-    const i32x4 rs_wt = tall_rsrc(hot_B + static_cast<size_t>(n0c) * (K >> 1));
+    const i32x4 rs_wt = buffer_rsrc(hot_B + static_cast<size_t>(n0c) * (K >> 1));
     const uint32_t w_voff = static_cast<uint32_t>(nrow - n0c) * static_cast<uint32_t>(K >> 1) + static_cast<uint32_t>(quarter * 8);
-    const i32x4 rs_s = tall_rsrc(hot_absmax);
-    [[maybe_unused]] const i32x4 rs_q = tall_rsrc(hot_absmax8);
+    const i32x4 rs_s = buffer_rsrc(hot_absmax);
+    [[maybe_unused]] const i32x4 rs_q = buffer_rsrc(hot_absmax8);
     const uint32_t e_row = static_cast<uint32_t>(nrow) * static_cast<uint32_t>(K); // flat element index of the row start (N K < 2^32)
     constexpr uint32_t kOob = 0xFFFFFFF0u;
 
@@ -199,15 +146,14 @@ __global__ __launch_bounds__(512) void gemm4_mfma_tall_kernel(const void* hot_A,
         const uint32_t inval = (j >= 0 && j < steps) ? 0u : kOob;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            tall_dma16(rs_a, static_cast<uint32_t>(kTallABase + stage * kTallStage + (2 * wave + i) * 1024), a_voff[i] | inval,
+            lds_dma16(rs_a, static_cast<uint32_t>(kTallABase + stage * kTallStage + (2 * wave + i) * 1024), a_voff[i] | inval,
                        static_cast<uint32_t>(j < 0 ? 0 : j) * 128u);
     };
 
     // ---- decode table: entry e (a packed byte) = 32 copies of (code[e >> 4], code[e & 15]) in fp32, 256 B per entry
     {
-        const float cv = tall_code_literal((lane & 15) + opaque_zero(), fp4);
+        const float cv = code_literal((lane & 15) + opaque_zero(), fp4);
         const int cvb = __builtin_bit_cast(int, cv);
-        using f32x4 = __attribute__((ext_vector_type(4))) float;
         const int e = tid & 255, hf = tid >> 8;
         const float hi = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(((e >> 4) & 15) * 4, cvb));
         const float lo = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((e & 15) * 4, cvb));
@@ -270,7 +216,7 @@ __global__ __launch_bounds__(512) void gemm4_mfma_tall_kernel(const void* hot_A,
             u32x4 o;
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                o[q] = TallMma<T>::pack(rounded_f32(pr[4 * j + q][0] * scale), rounded_f32(pr[4 * j + q][1] * scale));
+                o[q] = Mma32x32x16<T>::pack(rounded_f32(pr[4 * j + q][0] * scale), rounded_f32(pr[4 * j + q][1] * scale));
             *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(static_cast<uint32_t>(kTallBBase + stage * kTallStage) + b_wr +
                                                                          static_cast<uint32_t>(((2 * quarter + j) ^ b_swz) << 4)) = o;
         }
@@ -291,7 +237,7 @@ __global__ __launch_bounds__(512) void gemm4_mfma_tall_kernel(const void* hot_A,
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
-                    acc[i][j] = TallMma<T>::run(af[i], bf[j], acc[i][j]);
+                    acc[i][j] = Mma32x32x16<T>::run(af[i], bf[j], acc[i][j]);
         }
     };
 

@@ -39,10 +39,6 @@ namespace bnb {
 
 namespace {
 
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 typedef __attribute__((address_space(3))) unsigned char* lds_ptr;
 
 constexpr int kSegK = 2048;       // k covered by one wavefront-wide 16-byte load
@@ -168,17 +164,6 @@ struct StreamArgs {
     int lora_an = 0;                       // adapters in the stack: lora_b is [A_n, N, r]
     int lora_idx64 = 0;
 };
-
-template <bool FP4> __device__ __forceinline__ float code_literal(int i) {
-    // a compare/select tree over literals: no memory access (15 v_cndmask, once per wavefront)
-    constexpr float nf4[16] = {BNB_NF4_VALUES};
-    constexpr float fp4[16] = {BNB_FP4_VALUES};
-    float v = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        v = (i == j) ? (FP4 ? fp4[j] : nf4[j]) : v;
-    return v;
-}
 
 template <typename T> __device__ __forceinline__ void unpack16(const u32x4& v, float* dst);
 template <> __device__ __forceinline__ void unpack16<bf16>(const u32x4& v, float* dst) {
@@ -370,8 +355,6 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     };
     Stage st[NS];
     constexpr uint32_t kOob = 0xFFFFFFF0u; // beyond num_records
-    constexpr int kRsrcFlags = 0x00020000;
-    constexpr int kRecords = 0x7FFFFFFF;   // the descriptors only exist for the out-of-range trick: valid offsets are < 2^31 (stream_size_ok)
     constexpr int kWeightAux = NT ? 2 : 0; // nt: streamed once, read by one CU
 
     // matrix of a concatenated row (grouped launches): wave-uniform scan over <= kMaxGroup descriptors
@@ -410,13 +393,13 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
             am8 = p.mat[mi].absmax8;
             row = valid ? grow - p.mat[mi].row_start : 0;
         }
-        const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(Bp), 0, kRecords, kRsrcFlags);
+        const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(Bp), 0, kBufferWholeSpace, kBufferFlags);
         s.w = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
                                             rs_w, (k0 >> 1) | inval,
                                             static_cast<uint32_t>(row) * static_cast<uint32_t>(K >> 1), kWeightAux));
         const uint32_t blk = (static_cast<uint32_t>(row) * static_cast<uint32_t>(K) + k0) >> bs_shift;
         if constexpr (NESTED) {
-            const auto rs_q = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(am8), 0, kRecords, kRsrcFlags);
+            const auto rs_q = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(am8), 0, kBufferWholeSpace, kBufferFlags);
             s.s = __builtin_bit_cast(float, static_cast<uint32_t>(__builtin_amdgcn_raw_buffer_load_b8(rs_q, blk | inval, 0, 0)));
             // second level: the <= 2048 / bs blocks of an item lie in at most TWO groups of 256 blocks (in ONE when K is a
             // multiple of 2048): two scalar loads per item instead of a third vector-memory instruction per ring stage - the
@@ -434,7 +417,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
             s.s2a = amc[__builtin_amdgcn_readfirstlane(ga)];
             s.s2b = amc[__builtin_amdgcn_readfirstlane(gb)];
         } else {
-            const auto rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(am), 0, kRecords, kRsrcFlags);
+            const auto rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(am), 0, kBufferWholeSpace, kBufferFlags);
             s.s = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_a, (blk * 4u) | inval, 0, 0));
         }
     };
@@ -605,7 +588,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
             const int peer_mode = (hot_packed >> 24) & 15;
             x_from_peer = (peer_mode & 1) != 0;
             if (x_from_peer && wave < WAVES - BUILDERS) {
-                const auto rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(hot_A), 0, K * 4, kRsrcFlags);
+                const auto rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(hot_A), 0, K * 4, kBufferFlags);
 #pragma unroll
                 for (int r = 0; r < kChainRounds; ++r)
                     gx[r] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
@@ -664,7 +647,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
         const int tid_b = (PEER && x_from_peer) ? tid - (WAVES - BUILDERS) * 64 : tid;
         if (ph == 0 && table_builder) {
             if constexpr (!CODEPTR)
-                cv = code_literal<(FLAGS & kFp4) != 0>((lane & 15) + opaque_zero()); // (opaque: not hoisted above the loads)
+                cv = code_literal((lane & 15) + opaque_zero(), (FLAGS & kFp4) != 0); // (opaque: not hoisted above the loads)
             // (2) decode table, built while the loads fly: entry e (a packed byte) = 32 copies of
             // (code[e >> 4], code[e & 15]) in fp32, 256 B per entry, copy c at byte 8 c. Chunk c16 of the table
             // (16 B = two copies) is written by thread c16 % THREADS: every ds_write_b128 of a wavefront covers 1 KiB
@@ -739,7 +722,6 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
                     return gr;
                 };
                 // four values = half of the 16-byte chunk c of x; chunk (l', q) of a segment lives at slot CH l' + (q ^ swz(l'))
-                using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
                 auto put4 = [&](uint32_t j4, u32x2 four) {
                     const uint32_t c = j4 >> 1, half = j4 & 1u;
                     const uint32_t sg = c >> 8, cs = c & 255u, lp = cs / CH, q = cs % CH;
@@ -952,7 +934,6 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
                     const uint32_t abits = static_cast<uint32_t>(__builtin_bit_cast(unsigned short, at));
                     const uint32_t anext = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute((lane ^ 2) << 2, static_cast<int>(abits)));
                     if (!(row & 3)) {
-                        using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
                         const u32x2 granule = {abits | (anext << 16), epoch_out};
                         const size_t aslot = kChainDataOffset + (static_cast<size_t>((p.peer.epoch_offset + 1u) & (kChainRegions - 1u)) * p.peer.max_granules +
                                                                  ((static_cast<size_t>(p.peer.rank) * static_cast<size_t>(rows_total >> 1) + static_cast<size_t>(row >> 1)) >> 1)) * 8u;
@@ -980,7 +961,6 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
                         }
                     }
                 } else if (!(row & 1)) {
-                    using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
                     const u32x2 granule = {pair, epoch_out};
                     for (int pr = 0; pr < p.peer.world; ++pr) {
                         unsigned char* const dst = p.peer.base[pr] + slot;
@@ -1453,7 +1433,6 @@ __global__ __launch_bounds__(256) void peer_chain_read_kernel(PeerChain pc, T* _
     uint32_t* const hdr = reinterpret_cast<uint32_t*>(pc.local);
     const uint32_t epoch = pc.epoch_word[0] + pc.epoch_offset;
     const unsigned char* const src = pc.local + kChainDataOffset + static_cast<size_t>(pc.epoch_offset & (kChainRegions - 1u)) * pc.max_granules * 8u;
-    using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
     uint32_t wait_bound = pc.spin_bound;
     for (int gi = blockIdx.x * 256 + threadIdx.x; 2 * gi < nvalues; gi += gridDim.x * 256) {
         const unsigned char* const addr = src + static_cast<size_t>(gi) * 8u;

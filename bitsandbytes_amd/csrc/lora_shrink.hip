@@ -28,23 +28,6 @@
 namespace bnb {
 namespace {
 
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-template <typename T> struct ShrinkMma;
-template <> struct ShrinkMma<bf16> {
-    using frag = __attribute__((ext_vector_type(8))) bf16;
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0, 0);
-    }
-};
-template <> struct ShrinkMma<f16> {
-    using frag = __attribute__((ext_vector_type(8))) f16;
-    static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c, 0, 0, 0);
-    }
-};
-
 constexpr int kShrinkWaves = 16;    // wavefronts per workgroup = the K interleave of the summation order
 constexpr int kShrinkTile = 8;      // adapter rows per workgroup
 constexpr int kShrinkBatch = 8;     // steps of a wavefront whose loads are issued together (16 x 16 bytes in flight per lane)
@@ -96,7 +79,7 @@ __device__ __forceinline__ void shrink_tile(const T* __restrict__ x, const T* __
 #pragma unroll
         for (int u = 0; u < kShrinkBatch; ++u)
             if (s0 + u * kShrinkWaves < steps)
-                acc = ShrinkMma<T>::run(xv[u], av[u], acc);
+                acc = Mma16x16x32<T>::run(xv[u], av[u], acc);
     }
     // accumulator layout: lane (ln, lg) holds rows m = 4 lg ... 4 lg + 3 of column ln
     if (a_lane)

@@ -62,11 +62,10 @@ __global__ __launch_bounds__(kPeerThreads) void peer_allgather_kernel(PeerBufs b
     unsigned char* const dst = bufs.base[p] + kPeerDataOffset + (static_cast<size_t>(e & 1u) * world + rank) * slot_stride;
 
     // ---- payload (slots are 256-byte aligned)
-    using V16 = __attribute__((ext_vector_type(4))) uint32_t;
     const int tid = threadIdx.x;
     const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(out) | bytes) & 15u) == 0;
     if (vec)
-        peer_copy<V16>(dst, src, bytes, tid);
+        peer_copy<u32x4>(dst, src, bytes, tid);
     else
         peer_copy<unsigned char>(dst, src, bytes, tid);
     __threadfence_system(); // every lane's stores are visible system-wide before ...
@@ -101,7 +100,7 @@ __global__ __launch_bounds__(kPeerThreads) void peer_allgather_kernel(PeerBufs b
     if (landed) {
         const unsigned char* const slot = local + kPeerDataOffset + (static_cast<size_t>(e & 1u) * world + p) * slot_stride;
         if (vec)
-            peer_copy<V16>(o, slot, bytes, tid);
+            peer_copy<u32x4>(o, slot, bytes, tid);
         else
             peer_copy<unsigned char>(o, slot, bytes, tid);
     } else {

@@ -236,7 +236,6 @@ template <typename T> __device__ __forceinline__ bool abs_pattern_is_special(uin
 template <typename T>
 __device__ __forceinline__ void load8(const T* __restrict__ A, long base, long n, bool vec_ok, Raw8<T>& r) {
     if (vec_ok) { // caller guarantees base + 8 <= n
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         const u32x4* p = reinterpret_cast<const u32x4*>(A + base);
         const u32x4 a = stream_load<sizeof(T) == 2>(p);
         r.w[0] = a.x, r.w[1] = a.y, r.w[2] = a.z, r.w[3] = a.w;
