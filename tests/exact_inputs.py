@@ -19,6 +19,9 @@ output element the sum of the MAGNITUDES of its products (plus |bias|) stays bel
 product is a multiple of. Under that bound every fp32 partial sum - in any order, over any K split, through any slab reduction - is
 an integer multiple of the unit below 2^24 units, hence exact; the float64 reference is exact for the same reason, so rounding it
 once gives the only correct result.
+
+The seven codes used here reach 49 of the 256 entries of a kernel's byte -> (code[hi], code[lo]) table and no NF4 entry; the other
+codes, both tables and a caller-supplied one are read out bit for bit by tests/decode_probe_cases.py (one-hot rows, hand-packed bytes).
 """
 from __future__ import annotations
 
