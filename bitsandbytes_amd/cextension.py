@@ -131,6 +131,12 @@ def _declare(dll: ct.CDLL) -> None:
     # (form, dtype, M, rows, K, blocksize, out8: int32[8] on the host)
     sig(["bnb_mi355x_stream_geometry"], [_I32] * 3 + [ct.c_long, _I32, _I32, _VOID_P], _I32)
     sig(["bnb_mi355x_set_tuning"], [_I32] * 4)
+    sig(["bnb_mi355x_set_cu_count"], [_I32])
+    # (kernel, dtype, M, N, K, blocksize, nested, out16: int32[16] on the host)
+    sig(["bnb_mi355x_gemm_4bit_plan"], [_I32] * 7 + [_VOID_P], _I32)
+    # (form, dtype, M, N, group_N: int32[N] on the host or NULL, K, blocksize, nested, out16)
+    sig(["bnb_mi355x_gemm_4bit_sm_form_plan"], [_I32] * 4 + [_VOID_P] + [_I32] * 3 + [_VOID_P], _I32)
+    sig(["bnb_mi355x_gemm_4bit_grad_input_plan"], [_I32] * 5 + [_VOID_P], _I32)  # (dtype, M, N, K, blocksize, out16)
     sig(["bnb_mi355x_set_stamp_buffer"], [_VOID_P])
     sig(["bnb_mi355x_version"], [], ct.c_char_p)
 
@@ -172,5 +178,7 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_peer_close", "bnb_mi355x_peer_allgather", "bnb_mi355x_peer_status",
        "bnb_mi355x_peer_chain_buffer_bytes", "bnb_mi355x_peer_chain_alloc", "bnb_mi355x_gemv_4bit_peer_serves", "bnb_mi355x_gemv_4bit_peer",
        "bnb_mi355x_peer_chain_read",
-       "bnb_mi355x_set_stream_tuning", "bnb_mi355x_gemv_4bit_stream_exact", "bnb_mi355x_stream_geometry", "bnb_mi355x_set_tuning", "bnb_mi355x_set_stamp_buffer", "bnb_mi355x_version"]
+       "bnb_mi355x_set_stream_tuning", "bnb_mi355x_gemv_4bit_stream_exact", "bnb_mi355x_stream_geometry", "bnb_mi355x_set_tuning",
+       "bnb_mi355x_set_cu_count", "bnb_mi355x_gemm_4bit_plan", "bnb_mi355x_gemm_4bit_sm_form_plan", "bnb_mi355x_gemm_4bit_grad_input_plan",
+       "bnb_mi355x_set_stamp_buffer", "bnb_mi355x_version"]
 )

@@ -331,9 +331,18 @@ template <int C> __device__ __forceinline__ void wave_sum_n(float (&v)[C]) {
     }
 }
 
+// CU-count override (bnb_mi355x_set_cu_count: tests and tools - every setting computes correct results). A knob like the ones above:
+// thread-local, 0 = ask the device. The launch plans of the calling thread are then made for a device of that many compute units -
+// what a partitioned MI355X presents (DPX / QPX / CPX: 128 / 64 / 32) - whatever device runs them.
+inline thread_local TlsKnob g_cu_count_override{0};
+
 // Compute units of the current device (cached per device); 256 (MI355X) when no device can be queried - the launch-plan
-// functions that use it are also reachable from pure size queries (workspace bytes) on a host without a GPU.
+// functions that use it are also reachable from pure size queries (workspace bytes) on a host without a GPU. The override
+// above goes first: it neither reads nor writes the per-device cache.
 inline int device_cu_count_or_default() {
+    const int forced = g_cu_count_override.load(std::memory_order_relaxed);
+    if (forced > 0)
+        return forced;
     static std::atomic<int> cached[LdsLimit::kMaxDevices] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) {

@@ -73,6 +73,8 @@ size_t gemm_4bit_mfma_workspace_bytes(int M, int N, int K, int blocksize);
 void gemm_4bit_mfma(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
                     const float* absmax_offset, const float* code16, void* out, const void* bias, int M, int N, int K, int blocksize, int quant_type,
                     void* workspace, size_t workspace_bytes, hipStream_t stream);
+bool gemm_4bit_mfma_plan_query(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, int M, int N, int K, int blocksize,
+                               int* out16);
 
 // gemm4_mfma_rt.hip (the register-transposed kernel for small batches on small / medium matrices)
 bool gemm_4bit_rt_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize);
@@ -81,6 +83,7 @@ size_t gemm_4bit_rt_workspace_bytes(int M, int N, int K, int force_ks);
 void gemm_4bit_rt(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
                   const float* absmax_offset, void* out, const void* bias, int M, int N, int K, int blocksize, int quant_type, void* workspace,
                   size_t workspace_bytes, int force_ks, int force_waves, int variant, hipStream_t stream);
+void gemm_4bit_rt_plan_query(int M, int N, int K, int blocksize, int force_ks, int force_waves, int* out16);
 
 // gemm4_mfma_kq.hip (the K-quarter kernel: 32x32x16 MFMA, shares of a chunk copied to registers, 17 ... 64-row batches)
 bool gemm_4bit_kq_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize);
@@ -89,6 +92,7 @@ size_t gemm_4bit_kq_workspace_bytes(int M, int N, int K, int force_ks);
 void gemm_4bit_kq(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
                   const float* absmax_offset, void* out, const void* bias, int M, int N, int K, int blocksize, int quant_type, void* workspace,
                   size_t workspace_bytes, int force_ks, int ablate, hipStream_t stream);
+void gemm_4bit_kq_plan_query(int M, int N, int K, bool nested, int force_ks, int* out16);
 
 // gemm4_mfma_sm.hip (the streaming MFMA kernel: one persistent workgroup per CU, activations once per CU; 2 ... 16 rows)
 bool gemm_4bit_sm_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize);
@@ -109,6 +113,8 @@ bool gemm_4bit_sm_lora_ids(int dtype, const void* A, const uint8_t* B, const flo
 bool gemm_4bit_sm_grouped(int dtype, const void* A, int count, const uint8_t* const* B, const float* const* absmax, const uint8_t* const* absmax8,
                           const float* const* absmax_code, const float* const* absmax_offset, void* const* out, const void* const* bias,
                           const int* N, int M, int K, int blocksize, int quant_type, hipStream_t stream);
+bool gemm_4bit_sm_plan_query(int form, int M, int N, int K, int variant, int* out16);
+bool gemm_4bit_sm_grouped_plan_query(int count, const int* N, int M, int K, int* out16);
 
 // gemm4_mfma_tall.hip (128 x 128 tiles, pre-scaled operand decoded once per 128 rows: tall batches)
 bool gemm_4bit_tall_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize);
@@ -123,6 +129,7 @@ size_t gemm_4bit_grad_input_workspace_bytes(int M, int N, int K);
 void gemm_4bit_grad_input(int dtype, const void* G, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
                           const float* absmax_offset, void* out, int M, int N, int K, int blocksize, int quant_type, void* workspace,
                           size_t workspace_bytes, hipStream_t stream);
+bool gemm_4bit_grad_input_plan_query(int dtype, int M, int N, int K, int blocksize, int* out16);
 
 // gemm4_experts.hip
 bool gemm_4bit_experts_supported(int dtype, long E, long N, long K, int blocksize);

@@ -572,6 +572,58 @@ int bnb_mi355x_gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocks
 int bnb_mi355x_stream_geometry(int form, int dtype, int M, long rows, int K, int blocksize, int* out8) {
     return gemv_4bit_stream_geometry(form, dtype, M, rows, K, blocksize, out8) ? 1 : 0;
 }
+void bnb_mi355x_set_cu_count(int cus) { g_cu_count_override.store(cus > 0 ? cus : 0, std::memory_order_relaxed); }
+int bnb_mi355x_gemm_4bit_plan(int kernel, int dtype, int M, int N, int K, int blocksize, int nested, int* out16) {
+    if (out16 == nullptr || M <= 0 || N <= 0 || K <= 0 || blocksize <= 0 || dtype < 0 || dtype > 2)
+        return 0;
+    // (gemm_4bit_dispatch's question, with the aligned pointers of the shape-only queries)
+    const float* const absmax = reinterpret_cast<const float*>(kAlignedDummy);
+    const uint8_t* const absmax8 = nested ? kAlignedDummy8 : nullptr;
+    int v[16];
+    if (route_to_mfma(kernel, dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N, K, blocksize, !nested) &&
+        gemm_4bit_mfma_plan_query(dtype, kAlignedDummy, kAlignedDummy8, absmax, absmax8, M, N, K, blocksize, v)) {
+        for (int i = 0; i < 16; ++i)
+            out16[i] = v[i];
+        return 1;
+    }
+    if (g_mfma_knob1.load(std::memory_order_relaxed) / 100 == 60 && route_to_mfma(kernel, dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N, K, blocksize, !nested) &&
+        gemm_4bit_tall_supported(dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N, K, blocksize))
+        return 0;
+    int g[8];
+    if (!gemv_4bit_stream_geometry(0, dtype, M, N, K, blocksize, g))
+        return 0;
+    const int w[16] = {kKernelStream, g[4], (M + g[6] - 1) / g[6], 1, 1, g[3], (K + 2047) / 2048, g[6], g[7], g[6], g[0], g[1], g[5], 2048, g[2], 0};
+    for (int i = 0; i < 16; ++i)
+        out16[i] = w[i];
+    return 1;
+}
+int bnb_mi355x_gemm_4bit_sm_form_plan(int form, int dtype, int M, int N, const int* group_N, int K, int blocksize, int nested, int* out16) {
+    if (out16 == nullptr || form < 1 || form > 4 || M <= 0 || N <= 0 || K <= 0 || blocksize <= 0)
+        return 0;
+    const float* const absmax = reinterpret_cast<const float*>(kAlignedDummy);
+    int v[16];
+    bool ok = false;
+    if (form == 1)
+        ok = !nested && gated_family(dtype, kAlignedDummy, kAlignedDummy8, absmax, M, N, K, blocksize) == kKernelSm && gemm_4bit_sm_plan_query(1, M, N, K, 0, v);
+    else if (form <= 3)
+        ok = lora_family(dtype, kAlignedDummy, kAlignedDummy8, absmax, nested ? kAlignedDummy8 : nullptr, kAlignedDummy, kAlignedDummy, M, N, K, blocksize, 8) == kKernelSm &&
+             gemm_4bit_sm_plan_query(form, M, N, K, 0, v);
+    else
+        ok = group_N != nullptr && bnb_mi355x_gemm_4bit_grouped_route(dtype, N, group_N, M, K, blocksize) == 2 && gemm_4bit_sm_grouped_plan_query(N, group_N, M, K, v);
+    if (!ok)
+        return 0;
+    for (int i = 0; i < 16; ++i)
+        out16[i] = v[i];
+    return 1;
+}
+int bnb_mi355x_gemm_4bit_grad_input_plan(int dtype, int M, int N, int K, int blocksize, int* out16) {
+    int v[16];
+    if (out16 == nullptr || !gemm_4bit_grad_input_plan_query(dtype, M, N, K, blocksize, v))
+        return 0;
+    for (int i = 0; i < 16; ++i)
+        out16[i] = v[i];
+    return 1;
+}
 void bnb_mi355x_set_stamp_buffer(void* device_u64_buffer) {
 #ifdef BNB_PROFILING
     g_dbg_buf = static_cast<unsigned long long*>(device_u64_buffer);

@@ -437,6 +437,19 @@ size_t gemm_4bit_grad_input_workspace_bytes(int M, int N, int K) {
     return pl.ns > 1 ? static_cast<size_t>(pl.ns) * M * K * sizeof(float) : 0;
 }
 
+// The plan of a launch without the launch (bnb_mi355x_gemm_4bit_grad_input_plan), with the workspace the size query names. false
+// outside the shape preconditions. out16: see include/bnb_mi355x.h.
+bool gemm_4bit_grad_input_plan_query(int dtype, int M, int N, int K, int blocksize, int* out16) {
+    if (M <= 0 || !gemm_4bit_grad_input_supported(dtype, nullptr, nullptr, M, N, K, blocksize))
+        return false;
+    const GiPlan pl = gi_plan(M, N, K);
+    const int v[16] = {0, K / kGiCols, pl.ns, (M + 16 * pl.mt - 1) / (16 * pl.mt), pl.ns, pl.bps, N / kGiBlockN, pl.mt, kGiWaves, 16 * pl.mt,
+                       kGiCols, 0, gi_lds_bytes(pl.mt), kGiBlockN, 0, 0};
+    for (int i = 0; i < 16; ++i)
+        out16[i] = v[i];
+    return true;
+}
+
 // grad_A[M, K] = grad_out[M, N] * dequant(B)[N, K]. dtype 1 = f16, 2 = bf16. The workspace (fp32 slabs, see
 // gemm_4bit_grad_input_workspace_bytes) is required when the plan uses more than one N slice; with a smaller one the launch
 // uses as many slices as fit.

@@ -645,17 +645,23 @@ template <typename T, int MT, int CW, int NTW> void launch_mfma_pc(GemmArgs& p, 
         launch_mfma_pc_one<T, MT, false, CW, NTW, pc_depth(MT, CW, NTW, false)>(p, stream);
 }
 
+// consumer wavefronts and n-tiles per consumer of a geometry (Plan::cfg); the launch and the plan query ask here
+constexpr int pc_cw(int cfg) { return (cfg == 12 || cfg == 14) ? 4 : 8; }
+constexpr int pc_ntw(int cfg) { return (cfg == 12 || cfg == 13) ? 2 : 1; }
+// (8 x 2 consumers exist only where their ring fits beside the A tile: otherwise cfg 13 runs as 11)
+constexpr int pc_cfg_launched(int cfg, int MT) { return (cfg == 12 || cfg == 14) ? cfg : (cfg == 13 && pc_depth(MT, 8, 2, true) >= 2) ? 13 : 11; }
+
 template <typename T, int MT> void launch_mfma(GemmArgs& p, int cfg, hipStream_t stream) {
     // producer/consumer geometries. LDS: 32 KiB table + 2 x MT*8 KiB A stages + CW*D ring slots.
-    if (cfg == 12)
-        return launch_mfma_pc<T, MT, 4, 2>(p, stream);
-    if (cfg == 14)
-        return launch_mfma_pc<T, MT, 4, 1>(p, stream);
-    if constexpr (pc_depth(MT, 8, 2, true) >= 2) {
-        if (cfg == 13)
-            return launch_mfma_pc<T, MT, 8, 2>(p, stream);
+    switch (pc_cfg_launched(cfg, MT)) {
+    case 12: return launch_mfma_pc<T, MT, pc_cw(12), pc_ntw(12)>(p, stream);
+    case 14: return launch_mfma_pc<T, MT, pc_cw(14), pc_ntw(14)>(p, stream);
+    case 13:
+        if constexpr (pc_depth(MT, 8, 2, true) >= 2)
+            return launch_mfma_pc<T, MT, pc_cw(13), pc_ntw(13)>(p, stream);
+        [[fallthrough]];
+    default: return launch_mfma_pc<T, MT, pc_cw(11), pc_ntw(11)>(p, stream);
     }
-    return launch_mfma_pc<T, MT, 8, 1>(p, stream); // cfg 11
 }
 
 template <typename T> void dispatch_mfma(GemmArgs& p, float* ws, size_t ws_bytes, int knob1, hipStream_t stream) {
@@ -872,35 +878,88 @@ size_t gemm_4bit_mfma_workspace_bytes(int M, int N, int K, int blocksize) {
     return b > kq_bytes ? b : kq_bytes;
 }
 
-void gemm_4bit_mfma(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
-                    const float* absmax_code, const float* absmax_offset, const float* code16, void* out,
-                    const void* bias, int M, int N, int K, int blocksize, int quant_type, void* workspace,
-                    size_t workspace_bytes, hipStream_t stream) {
-    int fks, fw;
-    const int knob0 = g_mfma_knob0.load(std::memory_order_relaxed), knob1 = g_mfma_knob1.load(std::memory_order_relaxed);
-    int qks;
+namespace {
+// The kernel family a call that took the MFMA route launches, in the order the families are tried, with what the tuning knobs force
+// on it. gemm_4bit_mfma below and the plan query (gemm_4bit_mfma_plan_query) ask here. kKernelStream: the call leaves the route
+// again (the streaming kernel, or its generic fall-back).
+struct MfmaFamily {
+    int kernel;
+    int force_ks = 0, force_waves = 0; // register-transposed / K-quarter kernel: forced K slices, wavefronts (0 = built-in choice)
+};
+MfmaFamily mfma_family(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* code16, int M, int N, int K,
+                       int blocksize, int knob0, int knob1) {
+    int fks, fw, qks;
     if (blocksize == 32) {
         // blocksize 32: the register-transposed kernel's BS32 instances at any M (row passes over grid.z). The callers
         // route here only what gemm_4bit_mfma_supported(..., plain_absmax) accepted; anything else is a caller's bug.
         if (!gemm_4bit_rt_supported(dtype, A, B, code16, M, N, K, blocksize) || !gemm_4bit_rt_serves(absmax, absmax8, blocksize))
             // (not reachable through route_to_mfma, which asks the same questions; a direct caller gets the streaming kernel, not exit(1))
-            return gemv_4bit_stream(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, code16, out, bias, M, N, K, blocksize, quant_type, stream);
-        return gemm_4bit_rt(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, M, N, K, blocksize, quant_type, workspace,
-                            workspace_bytes, 0, 0, 0, stream);
+            return {kKernelStream};
+        return {kKernelRt};
     }
     if (knob1 / 100 == 60 && gemm_4bit_tall_supported(dtype, A, B, code16, M, N, K, blocksize)) // (tuning knob cfg 60: the tall-tile kernel)
-        return gemm_4bit_tall(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, M, N, K, blocksize, quant_type, knob1 % 100, stream);
+        return {kKernelTall};
     if (sm_selected(M, N, K, knob0, knob1) && gemm_4bit_sm_supported(dtype, A, B, code16, M, N, K, blocksize) && gemm_4bit_sm_serves(absmax, absmax8, blocksize))
-        return gemm_4bit_sm(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, M, N, K, blocksize, quant_type, knob0, stream);
+        return {kKernelSm};
     if (K % kKC) // (rows that are not whole 256-k chunks are the streaming MFMA kernel's alone: a call it turned down runs the streaming kernel)
-        return gemv_4bit_stream(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, code16, out, bias, M, N, K, blocksize, quant_type, stream);
+        return {kKernelStream};
     if (kq_selected(M, N, K, knob1, &qks) && gemm_4bit_kq_supported(dtype, A, B, code16, M, N, K, blocksize) &&
         gemm_4bit_kq_serves(absmax, absmax8, blocksize, K))
-        return gemm_4bit_kq(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, M, N, K, blocksize, quant_type,
-                            workspace, workspace_bytes, qks, knob0, stream);
+        return {kKernelKq, qks, 0};
     if (rt_selected(M, N, K, knob1, &fks, &fw) && gemm_4bit_rt_supported(dtype, A, B, code16, M, N, K, blocksize))
+        return {kKernelRt, fks, fw};
+    return {kKernelPc};
+}
+} // namespace
+
+// The plan of a call on the MFMA route without the call (bnb_mi355x_gemm_4bit_plan; pointers: the alignment the caller assumes).
+// false: the call leaves the route for the streaming kernel, or runs the tall-tile kernel (a tuning knob's, no plan query).
+bool gemm_4bit_mfma_plan_query(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, int M, int N, int K, int blocksize,
+                               int* out16) {
+    const int knob0 = g_mfma_knob0.load(std::memory_order_relaxed), knob1 = g_mfma_knob1.load(std::memory_order_relaxed);
+    const MfmaFamily f = mfma_family(dtype, A, B, absmax, absmax8, nullptr, M, N, K, blocksize, knob0, knob1);
+    switch (f.kernel) {
+    case kKernelSm: return gemm_4bit_sm_plan_query(0, M, N, K, knob0, out16);
+    case kKernelKq: gemm_4bit_kq_plan_query(M, N, K, absmax8 != nullptr, f.force_ks, out16); return true;
+    case kKernelRt: gemm_4bit_rt_plan_query(M, N, K, blocksize, f.force_ks, f.force_waves, out16); return true;
+    case kKernelPc: break;
+    default: return false;
+    }
+    const Plan pl = make_plan(M, N, K, knob1);
+    const int cfg = pc_cfg_launched(pl.cfg, pl.mt), cw = pc_cw(cfg), ntw = pc_ntw(cfg);
+    const bool nested = absmax8 != nullptr;
+    const int groups = K / kKC, per = (groups + pl.ks - 1) / pl.ks;
+    const int v[16] = {kKernelPc, (N + cw * ntw * 16 - 1) / (cw * ntw * 16), pl.ks, (M + pl.mt * 16 - 1) / (pl.mt * 16), pl.ks, per, groups, pl.mt,
+                       cw + kPcProducers, 16 * pl.mt, cw * ntw * 16, 0,
+                       static_cast<int>(pc_smem_bytes(pl.mt, cw, ntw, pc_depth(pl.mt, cw, ntw, nested), nested)), kKC, pc_depth(pl.mt, cw, ntw, nested), cfg};
+    for (int i = 0; i < 16; ++i)
+        out16[i] = v[i];
+    return true;
+}
+
+void gemm_4bit_mfma(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
+                    const float* absmax_code, const float* absmax_offset, const float* code16, void* out,
+                    const void* bias, int M, int N, int K, int blocksize, int quant_type, void* workspace,
+                    size_t workspace_bytes, hipStream_t stream) {
+    const int knob0 = g_mfma_knob0.load(std::memory_order_relaxed), knob1 = g_mfma_knob1.load(std::memory_order_relaxed);
+    const MfmaFamily f = mfma_family(dtype, A, B, absmax, absmax8, code16, M, N, K, blocksize, knob0, knob1);
+    switch (f.kernel) {
+    case kKernelStream:
+        return gemv_4bit_stream(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, code16, out, bias, M, N, K, blocksize, quant_type, stream);
+    case kKernelTall:
+        return gemm_4bit_tall(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, M, N, K, blocksize, quant_type, knob1 % 100, stream);
+    case kKernelSm:
+        return gemm_4bit_sm(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, M, N, K, blocksize, quant_type, knob0, stream);
+    case kKernelKq:
+        return gemm_4bit_kq(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, M, N, K, blocksize, quant_type,
+                            workspace, workspace_bytes, f.force_ks, knob0, stream);
+    case kKernelRt:
+        // (blocksize 32: built-in slices and wavefronts, no variant - mfma_family leaves the forces at 0 there)
         return gemm_4bit_rt(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, M, N, K, blocksize,
-                            quant_type, workspace, workspace_bytes, fks, fw, knob0 & 1, stream);
+                            quant_type, workspace, workspace_bytes, f.force_ks, f.force_waves, blocksize == 32 ? 0 : (knob0 & 1), stream);
+    default:
+        break;
+    }
     GemmArgs p;
     p.A = A;
     p.B = B;

@@ -910,6 +910,17 @@ size_t gemm_4bit_kq_workspace_bytes(int M, int N, int K, int force_ks) {
     return pl.ks > 1 ? static_cast<size_t>(pl.ks) * kq_slab_floats(M, N, pl.mt) * sizeof(float) : 0;
 }
 
+// The plan of a launch without the launch (bnb_mi355x_gemm_4bit_plan), with the workspace the size query names. out16: see
+// include/bnb_mi355x.h; out16[11] = kslices x the slab's floats / 1024 where K is split (the workspace is whole workgroup tiles).
+void gemm_4bit_kq_plan_query(int M, int N, int K, bool nested, int force_ks, int* out16) {
+    const KqPlan pl = kq_plan(M, N, K, force_ks);
+    const int lds = pl.mt == 1 ? (nested ? KqLds<1, true>::Alloc : KqLds<1, false>::Alloc) : (nested ? KqLds<2, true>::Alloc : KqLds<2, false>::Alloc);
+    const int v[16] = {kKernelKq, (N + kKqCols - 1) / kKqCols, pl.ks, (M + 32 * pl.mt - 1) / (32 * pl.mt), pl.ks, pl.cps, K / kKqChunk, pl.mt, kKqWaves,
+                       32 * pl.mt, kKqCols, static_cast<int>(kq_slab_floats(M, N, pl.mt) / 1024), lds, kKqChunk, 0, 0};
+    for (int i = 0; i < 16; ++i)
+        out16[i] = v[i];
+}
+
 // dtype: 1 = f16, 2 = bf16. force_ks (0 = built-in choice): sweeps and tests.
 void gemm_4bit_kq(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
                   const float* absmax_code, const float* absmax_offset, void* out, const void* bias, int M, int N, int K,

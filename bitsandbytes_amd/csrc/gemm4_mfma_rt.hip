@@ -478,11 +478,17 @@ RtPlan rt_plan(int M, int N, int K, int force_ks) {
     return pl;
 }
 
+// Dynamic LDS of an instance: the table, per wavefront the scratch tiles (two scale tiles at blocksize 32), the nested code, per
+// wavefront and row tile the reduction tile. The launch and the plan query (gemm_4bit_rt_plan_query) ask here.
+constexpr size_t rt_lds_bytes(int waves, int mt, bool bs32) {
+    return kRtLut + static_cast<size_t>(waves) * (bs32 ? kRtScratch32 : kRtScratch) + 1024 + static_cast<size_t>(waves) * mt * 1024;
+}
+
 template <typename T, int MT, int WAVES, bool DIRECT, bool BL>
 void rt_launch_bl(const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, int M, int N, int K, int flags,
                   const RtPlan& pl, const RtArgs& a, hipStream_t stream) {
     const bool bs32 = (flags & 31) == 5;
-    const size_t lds = kRtLut + static_cast<size_t>(WAVES) * (bs32 ? kRtScratch32 : kRtScratch) + 1024 + static_cast<size_t>(WAVES) * MT * 1024;
+    const size_t lds = rt_lds_bytes(WAVES, MT, bs32);
     dim3 grid((N + 15) / 16, pl.ks, (M + 16 * MT - 1) / (16 * MT));
     if constexpr (BL) {
         if (bs32) { // (fp32 absmax only: gemm_4bit_rt_supported; the branch-free form only)
@@ -562,6 +568,18 @@ size_t gemm_4bit_rt_workspace_bytes(int M, int N, int K, int force_ks) {
         return 0;
     const RtPlan pl = rt_plan(M, N, K, force_ks);
     return pl.ks > 1 ? static_cast<size_t>(pl.ks) * M * N * sizeof(float) : 0;
+}
+
+// The plan of a launch without the launch (bnb_mi355x_gemm_4bit_plan), with the workspace the size query names. out16: see
+// include/bnb_mi355x.h.
+void gemm_4bit_rt_plan_query(int M, int N, int K, int blocksize, int force_ks, int force_waves, int* out16) {
+    RtPlan pl = rt_plan(M, N, K, force_ks);
+    if (force_waves == 8 || (force_waves == 16 && pl.mt == 1))
+        pl.waves = force_waves;
+    const int v[16] = {kKernelRt, (N + 15) / 16, pl.ks, (M + 16 * pl.mt - 1) / (16 * pl.mt), pl.ks, pl.cps, K / kRtChunk, pl.mt, pl.waves, 16 * pl.mt,
+                       16, 0, static_cast<int>(rt_lds_bytes(pl.waves, pl.mt, blocksize == 32)), kRtChunk, (pl.mt == 1 && M <= pl.direct_max) ? 1 : 0, 0};
+    for (int i = 0; i < 16; ++i)
+        out16[i] = v[i];
 }
 
 // dtype: 1 = f16, 2 = bf16. force_ks / force_waves: sweeps and tests (0 = built-in choice).

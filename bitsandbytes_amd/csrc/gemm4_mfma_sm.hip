@@ -728,6 +728,26 @@ SmPlan sm_plan(int M, int N, bool gated = false) {
     return pl;
 }
 
+// The plan of a grouped launch (members of N[i] rows, `total` in all): the single-matrix plan of the whole group, then rows per
+// workgroup raised until the members' own shares - every member rounds its own up - need no more workgroups than the plan's whole
+// rounds of the chip. The launch and the plan query (gemm_4bit_sm_grouped_plan_query) ask here.
+SmPlan sm_grouped_plan(int M, int count, const int* N, long total) {
+    SmPlan pl = sm_plan(M, static_cast<int>(total));
+    const long limit = static_cast<long>(pl.grid_x) > sm_cu_count() ? static_cast<long>(pl.grid_x) : sm_cu_count();
+    for (;; ++pl.R) {
+        long blocks = 0;
+        for (int i = 0; i < count; ++i)
+            blocks += (N[i] + pl.R - 1) / pl.R;
+        if (blocks <= limit || pl.R >= 16 * kSmMaxTiles) {
+            pl.grid_x = static_cast<int>(blocks);
+            break;
+        }
+    }
+    pl.tt = (pl.R + 15) / 16;
+    pl.grouped = true;
+    return pl;
+}
+
 // The kernel's positional arguments: constant from the entry point down to the launch.
 struct SmCall {
     const void* A;
@@ -738,13 +758,24 @@ struct SmCall {
     int M, N, K, geom;
 };
 
+// Dynamic LDS of an instance: the table, the nested code, per wavefront the larger of the staging area and the accumulator
+// exchange, + the adapter's tiles (LORA), + the rows' scalings (IDS). The launch and the plan query (gemm_4bit_sm_plan_query) ask here.
+constexpr int sm_row_blocks(int rows) { return rows == 32 ? 2 : 1; } // 16-row blocks per decoded fragment = per grid.y step
+constexpr size_t sm_lds_bytes(int rows, int waves, int tt, bool lora, bool ids) {
+    const int V = (rows < 16 && waves == 8) ? 2 : 1; // (accumulator sets per tile: the kernel's V)
+    const int RB = sm_row_blocks(rows), SROWS = rows == 32 ? 16 : rows;
+    const size_t region = (SROWS * 512 + kSmScratch) > V * tt * RB * 1024 ? (SROWS * 512 + kSmScratch) : V * tt * RB * 1024;
+    return kSmLut + kSmCode2 + static_cast<size_t>(waves) * region + (lora ? tt * 1024 : 0) + (ids ? 128 : 0);
+}
+// 16 wavefronts per workgroup, 8 where 128 registers (three or four tiles' accumulators and item bodies beside the fragments and the ring) or the LDS
+// (8-KiB staging areas at ROWS = 16) do not allow them
+constexpr int sm_waves(int rows, int tt) { return (rows >= 16 || tt >= 3) ? 8 : 16; }
+
 template <typename T, int ROWS, int WAVES, int TT, bool NESTED, bool SINGLE, int ORDER = 0, bool GROUPED = false, bool GATED = false, bool LORA = false,
           bool IDS = false>
 void sm_launch_one(const SmCall& c, const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
-    constexpr int V = (ROWS < 16 && WAVES == 8) ? 2 : 1; // (accumulator sets per tile: the kernel's V)
-    constexpr int RB = ROWS == 32 ? 2 : 1, SROWS = ROWS == 32 ? 16 : ROWS;
-    constexpr size_t region = (SROWS * 512 + kSmScratch) > V * TT * RB * 1024 ? (SROWS * 512 + kSmScratch) : V * TT * RB * 1024;
-    constexpr size_t lds = kSmLut + kSmCode2 + static_cast<size_t>(WAVES) * region + (LORA ? TT * 1024 : 0) + (IDS ? 128 : 0); // (+ the adapter's tiles, + the rows' scalings)
+    constexpr int RB = sm_row_blocks(ROWS);
+    constexpr size_t lds = sm_lds_bytes(ROWS, WAVES, TT, LORA, IDS);
     auto kern = gemm4_mfma_sm_kernel<T, ROWS, WAVES, TT, NESTED, SINGLE, ORDER, GROUPED, GATED, LORA, IDS>;
     static LdsLimit lim;
     ensure_dynamic_lds(lim, reinterpret_cast<const void*>(kern), lds);
@@ -799,15 +830,12 @@ template <typename T, int ROWS, int WAVES, int TT> void sm_launch_kind(const SmC
     sm_launch_form<T, ROWS, WAVES, TT, false, false, false>(c, pl, a, stream);
 }
 
-// 16 wavefronts per workgroup, 8 where 128 registers (three or four tiles' accumulators and item bodies beside the fragments and the ring) or the LDS
-// (8-KiB staging areas at ROWS = 16) do not allow them
 template <typename T, int ROWS> void sm_launch_tt(const SmCall& c, const SmPlan& pl, const SmArgs& a, hipStream_t stream) {
-    constexpr int W = ROWS >= 16 ? 8 : 16;
     switch (pl.tt) {
-    case 1: return sm_launch_kind<T, ROWS, W, 1>(c, pl, a, stream);
-    case 2: return sm_launch_kind<T, ROWS, W, 2>(c, pl, a, stream);
-    case 3: return sm_launch_kind<T, ROWS, 8, 3>(c, pl, a, stream);
-    default: return sm_launch_kind<T, ROWS, 8, 4>(c, pl, a, stream);
+    case 1: return sm_launch_kind<T, ROWS, sm_waves(ROWS, 1), 1>(c, pl, a, stream);
+    case 2: return sm_launch_kind<T, ROWS, sm_waves(ROWS, 2), 2>(c, pl, a, stream);
+    case 3: return sm_launch_kind<T, ROWS, sm_waves(ROWS, 3), 3>(c, pl, a, stream);
+    default: return sm_launch_kind<T, ROWS, sm_waves(ROWS, 4), 4>(c, pl, a, stream);
     }
 }
 
@@ -876,6 +904,44 @@ void gemm_4bit_sm(int dtype, const void* A, const uint8_t* B, const float* absma
         pl.rows = 16;
     sm_launch(dtype, SmCall{A, B, absmax, absmax8, absmax_code, M, N, K, sm_geom(pl, quant_type, blocksize)}, pl,
               sm_args(absmax_offset, out, bias, stamp_buffer()), stream);
+}
+
+// The plan of a launch without the launch (bnb_mi355x_gemm_4bit_plan). form: 0 = plain (gemm_4bit_sm), 1 = gated, 2 = LoRA, 3 = LoRA
+// with adapter ids; variant: the plain call's knob0. false where the form's launcher would refuse the plan (its shape predicates are
+// the caller's business). out16: see include/bnb_mi355x.h.
+static void sm_plan_out(const SmPlan& pl, int M, int K, bool lora, bool ids, int* out16) {
+    const int tt = pl.tt < kSmMaxTiles ? pl.tt : kSmMaxTiles; // (sm_launch_tt's default case)
+    const int waves = sm_waves(pl.rows, tt), rb = sm_row_blocks(pl.rows);
+    const bool single = !pl.grouped && tt == 1 && pl.rows != 32 && sm_single_item(K, waves); // (sm_launch_form; grouped: ring instances only)
+    const int chunks = (K + kSmChunk - 1) / kSmChunk;
+    const int v[16] = {kKernelSm, pl.grid_x, (M + 16 * rb - 1) / (16 * rb), 1, 1, chunks, chunks, pl.tt, waves, 16 * rb, pl.R, 16 * tt,
+                       static_cast<int>(sm_lds_bytes(pl.rows, waves, tt, lora, ids)), kSmChunk, pl.rows, single ? 1 : 0};
+    for (int i = 0; i < 16; ++i)
+        out16[i] = v[i];
+}
+bool gemm_4bit_sm_plan_query(int form, int M, int N, int K, int variant, int* out16) {
+    SmPlan pl = sm_plan(M, N, form == 1);
+    if (form == 0 && (variant & 16) && pl.rows == 32)
+        pl.rows = 16;
+    if (form != 0 && (pl.rows > 16 || pl.tt > kSmMaxTiles || (form == 1 && (pl.R & 1))))
+        return false;
+    sm_plan_out(pl, M, K, form >= 2, form == 3, out16);
+    return true;
+}
+// ... of a grouped launch (gemm_4bit_sm_grouped's shape conditions; out16[1] = the workgroups of all members)
+bool gemm_4bit_sm_grouped_plan_query(int count, const int* N, int M, int K, int* out16) {
+    if (count < 1 || count > kSmMaxGroup || M < 1)
+        return false;
+    long total = 0;
+    for (int i = 0; i < count; ++i) {
+        if (N[i] < 1)
+            return false;
+        total += N[i];
+    }
+    if (total >= (1L << 30))
+        return false;
+    sm_plan_out(sm_grouped_plan(M, count, N, total), M, K, false, false, out16);
+    return true;
 }
 
 // Gated form (see the kernel's GATED): B [N = 2 F, K] interleaved, bias [N], out [M, F]. 2 <= ... M <= 16 (the 4-, 8- and 16-row
@@ -968,20 +1034,7 @@ bool gemm_4bit_sm_grouped(int dtype, const void* A, int count, const uint8_t* co
     }
     if (total >= (1L << 30))
         return false;
-    SmPlan pl = sm_plan(M, static_cast<int>(total));
-    // rows per workgroup: every member rounds its own share up - not more workgroups than the plan's whole rounds of the chip
-    const long limit = static_cast<long>(pl.grid_x) > sm_cu_count() ? static_cast<long>(pl.grid_x) : sm_cu_count();
-    for (;; ++pl.R) {
-        long blocks = 0;
-        for (int i = 0; i < count; ++i)
-            blocks += (N[i] + pl.R - 1) / pl.R;
-        if (blocks <= limit || pl.R >= 16 * kSmMaxTiles) {
-            pl.grid_x = static_cast<int>(blocks);
-            break;
-        }
-    }
-    pl.tt = (pl.R + 15) / 16;
-    pl.grouped = true;
+    const SmPlan pl = sm_grouped_plan(M, count, N, total);
     SmArgs a = sm_args(nested ? absmax_offset[0] : nullptr, out[0], bias ? bias[0] : nullptr, stamp_buffer());
     a.start[0] = 0;
     for (int i = 0; i < kSmMaxGroup; ++i) {

@@ -373,6 +373,46 @@ int bnb_mi355x_gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocks
  * mb activation rows per pass, waves wavefronts per workgroup}. */
 int bnb_mi355x_stream_geometry(int form, int dtype, int M, long rows, int K, int blocksize, int* out8);
 
+/* CU-count override for tests and tools (0 = ask the device, the default): every launch plan the calling thread makes afterwards -
+ * rows per workgroup, K / N slices, row tiles, wavefronts, the route's "fills the chip" tests, the quantizers' grid caps - is made for a
+ * device of `cus` compute units, what a partitioned MI355X presents (DPX / QPX / CPX: 128 / 64 / 32), whatever device runs it; the
+ * size and plan queries follow it. Every setting computes correct results - it only chooses a launch geometry. THREAD-LOCAL like
+ * bnb_mi355x_set_tuning (autograd's backward thread does not see it); it bypasses the per-device cache of the real count and never
+ * writes to it. Negative values count as 0. Not for the peer-chain kernels, whose workgroups wait for one another. */
+void bnb_mi355x_set_cu_count(int cus);
+
+/* Test and tool infrastructure: the launch plan of a bnb_mi355x_gemm_4bit call, without the call. Host logic only - no device
+ * pointer, no HIP call beyond the CU count of the current device (256 without one; bnb_mi355x_set_cu_count goes first) -, under the
+ * calling thread's tuning, computed by the functions the launch itself calls. Aligned pointers and literal code tables are assumed, as
+ * in bnb_mi355x_gemm_4bit_route; nested: the call carries double-quantised statistics. Returns 0, out16 untouched, where no plan can be
+ * named: a call the streaming kernel's predicates refuse (it runs the generic kernel) or the tall-tile kernel of a tuning knob.
+ * Returns 1 and out16 =
+ *   [0]  family, as bnb_mi355x_last_gemm_kernel names it (1 streaming, 3 register-transposed, 4 producer/consumer, 6 K-quarter,
+ *        7 streaming MFMA)
+ *   [1] [2] [3]  grid x, y, z
+ *   [4]  K slices (grid y of families 3, 4, 6; 1 otherwise)     [5]  k units per slice     [6]  k units of a row
+ *   [7]  row tiles per workgroup (families 3, 4, 6: mt; 7: 16-row tiles of weight rows, tt; 1: activation rows per pass, mb)
+ *   [8]  wavefronts per workgroup
+ *   [9]  batch rows per step of the grid axis that carries M (y for families 1 and 7, z otherwise)
+ *   [10] output columns (weight rows) per workgroup along grid x: R of families 1 and 7
+ *   [11] family 7: weight rows the instance's tiles hold (16 x tiles); family 6: floats / 1024 of one slice's workspace slab;
+ *        family 1: segment columns SW; else 0
+ *   [12] dynamic LDS bytes
+ *   [13] k per unit (family 1: 2048, [5] = phases P, [6] = segments)
+ *   [14] family 7: rows instance (4, 8, 16, 32); 3: direct activation fragments (0 / 1); 4: ring depth; 1: row groups G
+ *   [15] family 7: single-item instance (0 / 1); 4: cfg; else 0 */
+int bnb_mi355x_gemm_4bit_plan(int kernel, int dtype, int M, int N, int K, int blocksize, int nested, int* out16);
+
+/* ... of the streaming MFMA kernel's fused forms and grouped launch (the streaming kernel's: bnb_mi355x_stream_geometry). form:
+ * 1 = gated (N = 2 F), 2 = LoRA, 3 = LoRA with adapter ids: 0 where bnb_mi355x_gemm_4bit_gated / _lora on this shape does not run the
+ * streaming MFMA kernel. form 4 = grouped: N points to `count` (= the `N` argument) row counts on the host, 0 where
+ * bnb_mi355x_gemm_4bit_grouped_route does not answer 2; out16[1] = the workgroups of all members, out16[10] = the rows of each. */
+int bnb_mi355x_gemm_4bit_sm_form_plan(int form, int dtype, int M, int N, const int* group_N, int K, int blocksize, int nested, int* out16);
+
+/* ... of bnb_mi355x_gemm_4bit_grad_input: out16 as above with [0] = 0, grid x = K / 128, [4] N slices (grid y), [5] 32-n blocks per
+ * slice, [6] blocks of a column, [7] row tiles, [10] = 128 k-columns per workgroup. 0 outside bnb_mi355x_gemm_4bit_grad_input_supported. */
+int bnb_mi355x_gemm_4bit_grad_input_plan(int dtype, int M, int N, int K, int blocksize, int* out16);
+
 /* Profiling builds only (libbitsandbytes_mi355x_prof.so, -DBNB_PROFILING): when non-NULL the kernels write s_memtime
  * stamps per wavefront (u64) into this device buffer (tools/timeline_*.py). The product library contains no stamp or
  * ablation code; there the call is accepted and ignored. */

@@ -1,7 +1,10 @@
 """Child process of tests/test_stream_geometry_host.py: one FORM of bnb_mi355x_stream_geometry over the whole grid, in a process of
 its own - a query that kills its process (a division by zero in the host geometry did) is then a failed form, not a dead pytest.
 
-    python stream_geometry_sweep.py <library> <form> <out.npz>
+    python stream_geometry_sweep.py <library> <form> <out.npz> [<cus> [<tuning indices, comma separated>]]
+
+<cus>: the sweep runs under bnb_mi355x_set_cu_count(cus) (tests/test_cu_count_host.py; absent or 0: the device's count, 256 without
+one), over the named subset of TUNINGS (absent: all of them).
 
 Needs ctypes and numpy only: no torch, no GPU, nothing preloaded. Writes, per (tuning, dtype, M) in grid order, the answers as
 int32 [tunings, dtypes, Ms, rows, Ks, 9] = (supported, R, SW, G, P, grid_x, lds, mb, waves); the invariants are asserted by the parent.
@@ -37,13 +40,13 @@ def load(path):
     return lib
 
 
-def sweep(lib, form: int) -> np.ndarray:
-    out = np.zeros((len(TUNINGS), len(DTYPES), len(MS), len(ROWS), len(KS), 9), dtype=np.int32)
+def sweep(lib, form: int, tunings=TUNINGS) -> np.ndarray:
+    out = np.zeros((len(tunings), len(DTYPES), len(MS), len(ROWS), len(KS), 9), dtype=np.int32)
     query = lib.bnb_mi355x_stream_geometry
     base = out.ctypes.data
     addr = base + 4   # (entry 0 of a record is the answer, filled in at the end)
     answers = []
-    for tune in TUNINGS:
+    for tune in tunings:
         lib.bnb_mi355x_set_stream_tuning(*tune)
         for dtype in DTYPES:
             for M in MS:
@@ -61,7 +64,14 @@ def main(argv):
     if argv[2] == "gated-query":
         print(lib.bnb_mi355x_gemm_4bit_gated_supported(*[int(a) for a in argv[3:8]]))
         return 0
-    np.savez(argv[3], answers=sweep(lib, FORMS.index(argv[2])))
+    tunings = TUNINGS
+    if len(argv) > 4 and int(argv[4]) > 0:
+        lib.bnb_mi355x_set_cu_count.argtypes = [ct.c_int]
+        lib.bnb_mi355x_set_cu_count.restype = None
+        lib.bnb_mi355x_set_cu_count(int(argv[4]))
+    if len(argv) > 5:
+        tunings = tuple(TUNINGS[int(i)] for i in argv[5].split(","))
+    np.savez(argv[3], answers=sweep(lib, FORMS.index(argv[2]), tunings))
     return 0
 
 
