@@ -30,32 +30,6 @@ _DT_NAME = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"
 _DT_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 _QT_CODE = {"fp4": 1, "nf4": 2}
 
-# Largest M routed to the fused kernels; above it one dequantize + hipBLASLt GEMM moves fewer bytes per FLOP than re-streaming the
-# packed weight per 64-row pass. Calibrated on MI355X, us per call, fused vs dequantize + hipBLASLt:
-#  * M = 512 (profiles/r4_route_ab.txt): 4096^2 24 vs 41, 8192^2 89 vs 111, 11008 x 4096 70 vs 78, 4096 x 11008 59 vs 94 - 512 rows everywhere;
-#  * 513 ... 1024 rows (round 5, profiles/r5_tall_small_ab.txt): the row passes of a call run side by side over grid.z, so on matrices
-#    with LONG rows (K >= 2 N: 2048 x 8192, 1376 x 4096, 4096 x 11008) the fused call stays 8 - 30 % ahead up to 1024 rows, on square-ish
-#    ones (K >= 0.7 N: 4096^2, 3072^2, 5120^2, 5120 x 3584) up to 640 rows, and on wide ones (8192 x 2048, 11008 x 4096) it loses from
-#    576 on. Measured up to 45 M weights: the extended ranges apply up to FUSED_TALL_WEIGHTS, larger matrices keep 512 (8192^2 at
-#    M = 1024: 178 vs 144).
-FUSED_MAX_M = 512
-FUSED_MAX_M_LONG_ROWS = 1024   # K >= 2 N
-FUSED_MAX_M_SQUARE = 640       # 10 K >= 7 N
-FUSED_TALL_WEIGHTS = 48 << 20
-# Calls the MFMA kernels do not serve (K not a multiple of 256 - e.g. K = 2752, a 4-way shard of an 11008-wide projection -, or
-# blocksize 32 with double-quantised statistics) run the streaming kernel in 4-row passes: ahead of dequantize + GEMM up to 12 rows,
-# level at 16, 3 - 4 x behind at 64 (profiles/r5_tall_small_ab.txt, second table; until round 5 they were sent there up to 512 rows).
-STREAM_ONLY_MAX_M = 16
-# Round 6: rows that are not whole 256-k chunks (K % 64 == 0: K = 2752, 1344, 1088 ...) on matrices of >= SM_MIN_ROWS rows run the
-# streaming MFMA kernel (csrc/gemm4_mfma_sm.hip), above 16 rows its 32-row instances in row passes over grid.y. Fused vs dequantize + GEMM,
-# us (profiles/r6_sm_rows32_ab.txt): 4096 x 2752 M = 64 / 96 / 128 11.5 / 16.7 / 21.2 vs 30.2 / 36.8 / 36.7; 11008 x 1344 13.9 / 20.0 / 25.7 vs
-# 31.6 / 29.9 / 30.2; 8192 x 2752 15.5 / 21.7 / 28.4 vs 43.4 / 44.1 / 44.5; 14336 x 1088 15.6 / 22.3 / 29.0 vs 30.9 / 32.6 / 28.8: ahead or level to 128 rows.
-SM_TAIL_MAX_M = 128
-SM_MIN_ROWS = 128  # (csrc/gemm4_mfma.hip: sm_selected / kSmMinRows; small matrices, profiles/r6_sm_small_n_ab.txt: 1376 x 2752 M = 16 / 64 4.5 / 8.1 us
-# against 16.2 / 56.6 for the streaming kernel's passes)
-# Blocksize 32 (plain statistics) runs the register-transposed kernel's BS32 instances, 64-row passes one after the other: 4096^2
-# fused vs unfused 11.5 vs 28.9 us at 64 rows, 21.0 vs 37.5 at 128, 39.1 vs 33.1 at 256, 75 vs 40 at 512 (profiles/r5_tall_small_ab.txt, table 3).
-FUSED_MAX_M_BS32 = 128
 _REFERENCE_CUSTOM_MAX_M = 256  # reference backends/cuda/ops.py:816 (_gemm_4bit_custom_max_m on ROCm)
 
 
@@ -369,9 +343,16 @@ def _(A, B, shapeB: Sequence[int], absmax, code, blocksize: int, out: torch.Tens
 
 
 # ------------------------------------------------------------------------------------------ gemm_4bit
+@functools.lru_cache(maxsize=None)
+def _fused_max_m(dtype_code: int, N: int, K: int, blocksize: int, nested: bool) -> int:
+    # (the library's answer is a pure function of these arguments - include/bnb_mi355x.h -, so it is asked once per layer shape)
+    return lib.bnb_mi355x_gemm_4bit_fused_max_m(dtype_code, N, K, blocksize, int(nested))
+
+
 def _gemm_4bit_route(dtype: torch.dtype, M: int, N: int, K: int, blocksize: int, nested: bool = False) -> str:
     """MI355X routing: 'fused' (HIP dot / MFMA kernels, chosen inside the library by M) or 'unfused'
-    (dequantize + hipBLASLt). Replaces reference backends/cuda/ops.py:814-843,921-962."""
+    (dequantize + hipBLASLt). Replaces reference backends/cuda/ops.py:814-843,921-962; the fused range is the library's
+    (``bnb_mi355x_gemm_4bit_fused_max_m``, which the C++-registered kernel of the op asks as well)."""
     if K % blocksize != 0:
         # the reference only warns where its custom kernel could have run (M <= 256 on ROCm,
         # backends/cuda/ops.py:956-962): larger batches take dequantize + linear silently
@@ -382,29 +363,13 @@ def _gemm_4bit_route(dtype: torch.dtype, M: int, N: int, K: int, blocksize: int,
                 UserWarning,
             )
         return "unfused"
-    if dtype == torch.float32:
-        # fp32 activations: the streaming kernel (fp32 FMA decode, same code path as bf16/fp16) for decode-sized batches;
-        # no fp32 MFMA path worth having above that (1/16 of the bf16 matrix rate)
-        return "fused" if M <= 4 else "unfused"
-    return "fused" if M <= fused_max_m(N, K, blocksize, nested) else "unfused"
+    # (a dtype outside _DT_CODE routes like the 16-bit ones and is refused by the path it lands on)
+    return "fused" if M <= _fused_max_m(_DT_CODE.get(dtype, 1), N, K, blocksize, bool(nested)) else "unfused"
 
 
 def fused_max_m(N: int, K: int, blocksize: int = 64, nested: bool = False) -> int:
-    """Largest batch (rows of A) the fused 16-bit kernels are used for on an N x K weight (csrc/torch_dispatch.cpp: fused_max_m)."""
-    if K % 256 != 0 and K % 64 == 0 and blocksize >= 64 and N >= SM_MIN_ROWS:
-        return SM_TAIL_MAX_M  # (the streaming MFMA kernel's row passes)
-    if K % 256 != 0 or blocksize < 32 or (blocksize == 32 and nested):
-        return STREAM_ONLY_MAX_M  # (the MFMA kernels' preconditions, csrc/gemm4_mfma.hip: gemm_4bit_mfma_supported)
-    if blocksize == 32:
-        return FUSED_MAX_M_BS32
-    # (the extended ranges were measured on the K-quarter kernel: plain statistics at any blocksize >= 64, nested ones at blocksize 64
-    # and K <= 16384 - csrc/gemm4_mfma_kq.hip: gemm_4bit_kq_serves; other nested calls run the producer/consumer kernel and keep 512)
-    if N * K <= FUSED_TALL_WEIGHTS and blocksize >= 64 and (not nested or (blocksize == 64 and K <= 16384)):
-        if K >= 2 * N:
-            return FUSED_MAX_M_LONG_ROWS
-        if 10 * K >= 7 * N:
-            return FUSED_MAX_M_SQUARE
-    return FUSED_MAX_M
+    """Largest batch (rows of A) the fused 16-bit kernels are used for on an N x K weight."""
+    return _fused_max_m(1, N, K, blocksize, bool(nested))
 
 
 def _gemm_4bit_fused(A, B, shapeB, absmax, blocksize, quant_type, bias, absmax_8bit, absmax_code, absmax_offset,
@@ -909,4 +874,4 @@ if not NATIVE_DISPATCH:
     register_kernel("bitsandbytes::gemm_4bit", "cuda")(_gemm_4bit_python_kernel)
 
 
-__all__ = ["FUSED_MAX_M", "NATIVE_DISPATCH", "fused_max_m", "gemm_4bit_grouped", "prod"]
+__all__ = ["NATIVE_DISPATCH", "fused_max_m", "gemm_4bit_grouped", "prod"]

@@ -75,6 +75,7 @@ def _declare(dll: ct.CDLL) -> None:
     sig(["bnb_mi355x_gemm_4bit"], [_I32, _I32] + [_VOID_P] * 9 + [_I32] * 5 + [_VOID_P, ct.c_size_t, _VOID_P])
     sig(["bnb_mi355x_gemm_4bit_workspace_bytes"], [_I32] * 6, ct.c_size_t)
     sig(["bnb_mi355x_gemm_4bit_route"], [_I32] * 6, _I32)
+    sig(["bnb_mi355x_gemm_4bit_fused_max_m"], [_I32] * 5, _I32)  # (dtype, N, K, blocksize, nested)
     sig(["bnb_mi355x_last_gemm_kernel"], [], _I32)
     # (dtype, A, a_slot_stride, B, absmax, absmax_8bit, absmax_code, absmax_offset, bias, ids, index_bytes, out, P, S, E, N, K, blocksize,
     #  quant_type, stream)
@@ -164,7 +165,8 @@ EXPORTED_SYMBOLS = tuple(
     + [f"cgemm_4bit_{d}" for d in ("fp32", "bf16", "fp16")]
     + [f"cgemm_4bit_inference_naive_{d}" for d in ("fp32", "bf16", "fp16")]
     + ["get_context", "cget_managed_ptr", "bnb_mi355x_quantize_4bit", "bnb_mi355x_quantize_8bit", "bnb_mi355x_quantize_4bit_nested", "bnb_mi355x_dequantize_4bit_nested", "bnb_mi355x_dequantize_4bit_rows",
-       "bnb_mi355x_gemm_4bit", "bnb_mi355x_gemm_4bit_workspace_bytes", "bnb_mi355x_gemm_4bit_route", "bnb_mi355x_last_gemm_kernel",
+       "bnb_mi355x_gemm_4bit", "bnb_mi355x_gemm_4bit_workspace_bytes", "bnb_mi355x_gemm_4bit_route", "bnb_mi355x_gemm_4bit_fused_max_m",
+       "bnb_mi355x_last_gemm_kernel",
        "bnb_mi355x_gemm_4bit_grouped", "bnb_mi355x_gemm_4bit_grouped_route",
        "bnb_mi355x_gemm_4bit_experts", "bnb_mi355x_gemm_4bit_experts_supported",
        "bnb_mi355x_gemm_4bit_experts_ffn", "bnb_mi355x_gemm_4bit_experts_ffn_supported",

@@ -63,18 +63,33 @@ bool gemv_4bit_peer(void* const* bufs, void* epoch_word, int world, int rank, in
 void peer_chain_read(void* const* bufs, void* epoch_word, int world, int rank, int dtype, void* out, int nvalues, long max_values,
                      uint32_t epoch_offset, uint32_t spin_bound, hipStream_t stream);
 
-// gemm4_mfma.hip (the MFMA dispatcher, the slab finalize launch and the library-owned workspace)
+// gemm4_mfma.hip (gemm_4bit's route and dispatcher, the slab finalize launch and the library-owned workspace)
 extern thread_local TlsKnob g_mfma_knob0, g_mfma_knob1;
 void gemm_4bit_finalize(int dtype, const float* ws, const void* bias, void* out, int M, int N, int kslices, hipStream_t stream);
 float* gemm_4bit_internal_workspace(size_t bytes, hipStream_t stream);
-bool gemm_4bit_sm_routes(int dtype, int M, int N, int K, int blocksize);
-bool gemm_4bit_mfma_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize, bool plain_absmax);
-size_t gemm_4bit_mfma_workspace_bytes(int M, int N, int K, int blocksize);
-void gemm_4bit_mfma(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
-                    const float* absmax_offset, const float* code16, void* out, const void* bias, int M, int N, int K, int blocksize, int quant_type,
-                    void* workspace, size_t workspace_bytes, hipStream_t stream);
-bool gemm_4bit_mfma_plan_query(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, int M, int N, int K, int blocksize,
-                               int* out16);
+// The alignment of A / B / absmax is unknown to the shape-only queries: they assume the aligned (fast) case and pass this.
+alignas(16) inline const int kAlignedDummy[4] = {0, 0, 0, 0};
+inline const uint8_t* const kAlignedDummy8 = reinterpret_cast<const uint8_t*>(kAlignedDummy);
+// gemm_4bit_route's answer: the kernel family (kKernelStream / Sm / Kq / Rt / Pc / Tall), the K slices / wavefronts a tuning knob forces
+// on it (0 = built-in choice), and the call's one snapshot of the knobs for what the launch passes on (variant, ablation)
+struct Gemm4Route {
+    int kernel;
+    int force_ks, force_waves;
+    int knob0, knob1;
+};
+Gemm4Route gemm_4bit_route(int kernel, int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* code16, int M,
+                           int N, int K, int blocksize, bool without_kq = false);
+void gemm_4bit(int kernel, int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+               const float* absmax_offset, const float* code16, void* out, const void* bias, int M, int N, int K, int blocksize, int quant_type,
+               void* workspace, size_t workspace_bytes, hipStream_t stream);
+size_t gemm_4bit_workspace_bytes(int kernel, int dtype, const void* A, const uint8_t* B, const float* absmax, int M, int N, int K, int blocksize);
+bool gemm_4bit_plan_query(int kernel, int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, int M, int N, int K,
+                          int blocksize, int* out16);
+int gemm_4bit_gated_family(int dtype, const void* A, const uint8_t* B, const float* absmax, int M, int N, int K, int blocksize);
+int gemm_4bit_lora_family(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const void* lora_t, const void* lora_b,
+                          int M, int N, int K, int blocksize, int r);
+int gemm_4bit_grouped_route(int dtype, const void* A, int count, const uint8_t* const* B, const float* const* absmax, const uint8_t* const* absmax8,
+                            const int* N, int M, int K, int blocksize);
 
 // gemm4_mfma_rt.hip (the register-transposed kernel for small batches on small / medium matrices)
 bool gemm_4bit_rt_supported(int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize);

@@ -13,40 +13,12 @@ unsigned long long* g_dbg_buf = nullptr; // profiling builds only: device buffer
 
 namespace {
 
-// The alignment of A / B / absmax is unknown to the shape-only queries: they assume the aligned (fast) case and pass this.
-const int kAlignedDummy[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
-const uint8_t* const kAlignedDummy8 = reinterpret_cast<const uint8_t*>(kAlignedDummy);
-
 // Error convention of the reference ABI (bnb_common.h): an entry point that cannot serve its call prints and terminates.
 void require_quant_type(const char* entry, int quant_type) {
     if (quant_type != kFP4 && quant_type != kNF4) {
         fprintf(stderr, "bitsandbytes_amd: %s: quant_type must be 1 (FP4) or 2 (NF4), got %d\n", entry, quant_type);
         exit(1);
     }
-}
-
-// M at or below which the streaming dot kernel is used (its activations live in registers: 32 fp32 per row and
-// lane); above it the MFMA kernels (when supported). MI355X-specific replacement for the reference's per-arch
-// heuristic (bitsandbytes/backends/cuda/ops.py:814-843), calibrated on gfx950 — see DESIGN.md.
-constexpr int kStreamMaxM = 4;
-
-// plain_absmax: the call carries fp32 absmax (not the double-quantised form) - what the MFMA route needs to know at blocksize 32,
-// where only the register-transposed kernel's BS32 instances (fp32 absmax) exist; the shape-only queries pass true.
-bool route_to_mfma(int kernel, int dtype, const void* A, const uint8_t* B, const float* code16, int M, int N, int K, int blocksize, bool plain_absmax) {
-    if (kernel == 1 || kernel == 3)
-        return false;
-    // the streaming MFMA kernel's own reach: 2 ... 16 rows on matrices of >= 128 rows (csrc/gemm4_mfma.hip: sm_selected has the
-    // measured exceptions), any K % 64 == 0 (the other MFMA kernels need whole 256-k chunks) - round 6
-    const bool sm = gemm_4bit_sm_routes(dtype, M, N, K, blocksize) && gemm_4bit_sm_supported(dtype, A, B, code16, M, N, K, blocksize);
-    if (kernel == 2)
-        return sm || gemm_4bit_mfma_supported(dtype, A, B, code16, M, N, K, blocksize, plain_absmax);
-    // three or four rows: the streaming kernel's FMA count grows with M while the MFMA kernel's does not - on matrices that
-    // fill the chip with 16-column workgroups the MFMA kernel is ahead from M = 3 (4096^2 6.5 vs 6.9 us, 4096 x 11008 10.8 vs
-    // 26.7), on small ones the streaming kernel's cheaper launch still wins (1376 x 4096 4.9 vs 5.3)
-    // round 6: from TWO rows on wherever the streaming MFMA kernel (gemm4_mfma_sm.hip) serves the shape - one decode for all rows,
-    // activations once per CU (4096^2 M = 2: 4.44 vs 4.95 us; profiles/r6_sm_v3_ab_full.txt)
-    const bool big = static_cast<long>(N) * K >= (12L << 20);
-    return sm || ((M > kStreamMaxM || (M >= 3 && big)) && gemm_4bit_mfma_supported(dtype, A, B, code16, M, N, K, blocksize, plain_absmax));
 }
 
 void gemm_4bit_dispatch(int kernel, int dtype, const void* A, const uint8_t* B, const float* absmax,
@@ -56,55 +28,8 @@ void gemm_4bit_dispatch(int kernel, int dtype, const void* A, const uint8_t* B, 
     if (M <= 0 || N <= 0)
         return;
     require_quant_type("gemm_4bit", quant_type);
-    if (route_to_mfma(kernel, dtype, A, B, code16, M, N, K, blocksize, absmax8 == nullptr && aligned_to(absmax, 16)))
-        gemm_4bit_mfma(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, code16, out, bias, M, N, K, blocksize,
-                       quant_type, workspace, workspace_bytes, stream);
-    else
-        gemv_4bit_stream(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, code16, out, bias, M, N, K, blocksize,
-                         quant_type, stream);
-}
-
-// Gated call (bnb_mi355x_gemm_4bit_gated) on the interleaved [N = 2F, K] matrix at M rows: the kernel FAMILY the plain call on the
-// same matrix and M runs - so that the gated result is the plain result's silu(gate) * up bit for bit - when that family has a gated
-// form: kKernelStream or kKernelSm, else 0 (not supported). 16-bit activations, fp32 absmax, 1 <= M <= 16, blocksize >= 64, whole
-// quantization blocks per row, aligned pointers.
-int gated_family(int dtype, const void* A, const uint8_t* B, const float* absmax, int M, int N, int K, int blocksize) {
-    if ((dtype != 1 && dtype != 2) || M < 1 || M > 16 || N < 2 || (N & 1) || K <= 0 || blocksize < 64 || !is_pow2(blocksize) || (K % blocksize) != 0 ||
-        !aligned_to(A, 16) || !aligned_to(B, 16) || !aligned_to(absmax, 4))
-        return kKernelNone;
-    if (route_to_mfma(0, dtype, A, B, nullptr, M, N, K, blocksize, aligned_to(absmax, 16))) {
-        // (gemm_4bit_mfma's order: the tall-tile knob first, then the streaming MFMA kernel; every other MFMA kernel has no gated form)
-        if (g_mfma_knob1.load(std::memory_order_relaxed) / 100 == 60)
-            return kKernelNone;
-        return gemm_4bit_sm_routes(dtype, M, N, K, blocksize) && gemm_4bit_sm_gated_supported(dtype, A, B, M, N, K, blocksize) &&
-                       gemm_4bit_sm_serves(absmax, nullptr, blocksize)
-                   ? kKernelSm
-                   : kKernelNone;
-    }
-    return gemv_4bit_stream_gated_supported(dtype, M, N, K, blocksize) ? kKernelStream : kKernelNone;
-}
-
-// LoRA call (bnb_mi355x_gemm_4bit_lora) at M rows: the kernel FAMILY the plain bnb_mi355x_gemm_4bit call on the same matrix, M and
-// statistics runs - the adapter term is an epilogue of that launch, everything in front of it the plain instance's - when that family
-// has the epilogue: kKernelStream or kKernelSm, else 0 (not supported). 16-bit activations, 1 <= M <= 16, blocksize >= 64, whole
-// quantization blocks per row, r a multiple of 8 in [8, 128], aligned pointers.
-int lora_family(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const void* lora_t, const void* lora_b, int M,
-                int N, int K, int blocksize, int r) {
-    if ((dtype != 1 && dtype != 2) || M < 1 || M > 16 || N < 1 || K <= 0 || blocksize < 64 || !is_pow2(blocksize) || (K % blocksize) != 0 || r < 8 || r > 128 ||
-        (r % 8) != 0 || !aligned_to(A, 16) || !aligned_to(B, 16) || !aligned_to(absmax, 4) || !aligned_to(lora_t, 16) || !aligned_to(lora_b, 16))
-        return kKernelNone;
-    if (route_to_mfma(0, dtype, A, B, nullptr, M, N, K, blocksize, absmax8 == nullptr && aligned_to(absmax, 16))) {
-        // (gemm_4bit_mfma's order: the tall-tile knob, the streaming MFMA kernel, the streaming kernel for rows that are not whole
-        // 256-k chunks; every other MFMA kernel has no LoRA epilogue)
-        if (g_mfma_knob1.load(std::memory_order_relaxed) / 100 == 60)
-            return kKernelNone;
-        if (gemm_4bit_sm_routes(dtype, M, N, K, blocksize) && gemm_4bit_sm_supported(dtype, A, B, nullptr, M, N, K, blocksize) &&
-            gemm_4bit_sm_serves(absmax, absmax8, blocksize))
-            return gemm_4bit_sm_lora_supported(dtype, A, B, M, N, K, blocksize, r) ? kKernelSm : kKernelNone;
-        if ((K % 256) == 0)
-            return kKernelNone;
-    }
-    return gemv_4bit_stream_lora_supported(dtype, M, N, K, blocksize, r) ? kKernelStream : kKernelNone;
+    gemm_4bit(kernel, dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, code16, out, bias, M, N, K, blocksize, quant_type, workspace,
+              workspace_bytes, stream);
 }
 
 } // namespace
@@ -283,23 +208,6 @@ void bnb_mi355x_gemm_4bit(int kernel, int dtype, const void* A, const uint8_t* B
     gemm_4bit_dispatch(kernel, dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, code16, out, bias, M, N, K,
                        blocksize, quant_type, workspace, workspace_bytes, S(s));
 }
-// Groups of 17 ... 64 rows as ONE launch of the streaming MFMA kernel - although no member's own route at that many rows is this
-// kernel: its 32-row instances multiply two 16-row blocks against every decoded weight fragment (row passes of 32 over grid.y above
-// that; small groups: passes of 16 side by side on the CUs they leave idle), and the group shares one boundary, one table build and one
-// activation fetch per CU. Measured (profiles/r6_grouped_ab.txt, third table; us per group, grouped launch vs the members one by one):
-// 4 x 4096^2 M = 24 / 32 / 48 / 64 17.2 / 17.3 / 29.6 / 30.2 vs 32.9 / 33.4 / 39.4 / 44.4; 4096 + 2 x 1024 (x 4096) 11.0 / 11.3 / 19.7 / 20.0
-// vs 19.4 / 20.2 / 21.6 / 22.8; 3 x 512 x 4096 5.9 / 5.9 / 7.9 / 7.9 vs 15.1 / 15.3 / 15.4 / 15.4; 2 x 11008 x 4096 26.8 / 27.0 vs 28.0 / 28.4
-// but 47.4 / 48.4 vs 35.0 / 35.5 at 48 / 64 rows; 2 x 14336 x 4096 and 3 x 8192^2 behind (big members keep their own kernels).
-// Such a group is NOT bit-identical to separate calls (another kernel family: the oracle's tolerance, like every fused call).
-static bool grouped_sm_passes(int dtype, int count, const int* N, int M, int K, int blocksize) {
-    if (dtype == 0 || M <= 16 || M > 64 || count < 2 || count > 8 || blocksize < 64 || (K % 64) != 0 || g_mfma_knob0.load(std::memory_order_relaxed) != 0 ||
-        g_mfma_knob1.load(std::memory_order_relaxed) != 0)
-        return false;
-    long long weights = 0;
-    for (int i = 0; i < count; ++i)
-        weights += static_cast<long long>(N[i]) * K;
-    return weights <= (M <= 32 ? (96LL << 20) : (72LL << 20));
-}
 void bnb_mi355x_gemm_4bit_grouped(int dtype, const void* A, int count, const uint8_t* const* B, const float* const* absmax,
                                   const uint8_t* const* absmax_8bit, const float* const* absmax_code,
                                   const float* const* absmax_offset, void* const* out, const void* const* bias, const int* N,
@@ -307,63 +215,30 @@ void bnb_mi355x_gemm_4bit_grouped(int dtype, const void* A, int count, const uin
     if (count <= 0 || M <= 0)
         return;
     require_quant_type("gemm_4bit_grouped", quant_type);
-    // Tried in this order (bnb_mi355x_gemm_4bit_grouped_route answers the same question from shapes alone):
-    //  * up to 8 members that the single-matrix entry point would ALL route to the streaming MFMA kernel (2 ... 16 rows,
-    //    csrc/gemm4_mfma.hip: sm_selected): ONE launch of that kernel over the members' rows - bit-identical to separate calls (the
-    //    same kernel family, and its summation order does not depend on the launch geometry);
-    //  * a group of 17 ... 64 rows that grouped_sm_passes accepts (above): ONE launch of that kernel as well, in row passes of 32 or
-    //    16 - NOT bit-identical to separate calls, whose route at that many rows is another family;
-    //  * otherwise, when no member is routed to an MFMA kernel and gemv_4bit_grouped takes the group (M <= 4, up to 8 matrices,
-    //    K % 32 == 0, single-phase rows): ONE launch of the streaming kernel, bit-identical to separate calls;
-    //  * everything else (mixed routes, more than 8 matrices, a group either launcher refuses): matrix by matrix.
-    bool any_mfma = false, all_sm = count <= 8;
-    for (int i = 0; i < count; ++i) {
-        any_mfma = any_mfma || route_to_mfma(0, dtype, A, B[i], nullptr, M, N[i], K, blocksize,
-                                             (absmax_8bit == nullptr || absmax_8bit[i] == nullptr) && aligned_to(absmax[i], 16));
-        all_sm = all_sm && gemm_4bit_sm_routes(dtype, M, N[i], K, blocksize);
-    }
-    if ((all_sm || grouped_sm_passes(dtype, count, N, M, K, blocksize)) &&
-        gemm_4bit_sm_grouped(dtype, A, count, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, N, M, K, blocksize, quant_type, S(s)))
+    const int route = gemm_4bit_grouped_route(dtype, A, count, B, absmax, absmax_8bit, N, M, K, blocksize);
+    if (route == 2 && gemm_4bit_sm_grouped(dtype, A, count, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, N, M, K, blocksize, quant_type, S(s)))
         return;
-    if (!any_mfma && gemv_4bit_grouped(dtype, A, count, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, N, M, K,
-                                       blocksize, quant_type, S(s)))
+    if (route == 1 && gemv_4bit_grouped(dtype, A, count, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, N, M, K, blocksize, quant_type, S(s)))
         return;
-    // not a streaming-kernel shape (M > 4, more than 8 matrices, odd K ...): one launch per matrix, same results
+    // (gemm_4bit_grouped_route has the three cases) matrix by matrix - also a group that its launcher refused: same results
     for (int i = 0; i < count; ++i)
         gemm_4bit_dispatch(0, dtype, A, B[i], absmax[i], absmax_8bit ? absmax_8bit[i] : nullptr,
                            absmax_code ? absmax_code[i] : nullptr, absmax_offset ? absmax_offset[i] : nullptr, nullptr, out[i],
                            bias ? bias[i] : nullptr, M, N[i], K, blocksize, quant_type, nullptr, 0, S(s));
 }
 int bnb_mi355x_gemm_4bit_grouped_route(int dtype, int count, const int* N, int M, int K, int blocksize) {
-    // what bnb_mi355x_gemm_4bit_grouped does with such a group, assuming aligned pointers and members of one kind of statistics:
-    // 2 = one launch of the streaming MFMA kernel, 1 = one launch of the streaming kernel, 0 = matrix by matrix
-    if (count <= 0 || count > 8 || M <= 0 || blocksize <= 0 || K % blocksize != 0)
-        return 0;
-    bool any_mfma = false, all_sm = true;
-    for (int i = 0; i < count; ++i) {
-        any_mfma = any_mfma || route_to_mfma(0, dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N[i], K, blocksize, true);
-        all_sm = all_sm && gemm_4bit_sm_routes(dtype, M, N[i], K, blocksize) &&
-                 gemm_4bit_sm_supported(dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N[i], K, blocksize);
+    // what bnb_mi355x_gemm_4bit_grouped does with such a group, assuming aligned pointers and members of plain statistics
+    const uint8_t* B[8];
+    const float* absmax[8];
+    for (int i = 0; i < 8; ++i) {
+        B[i] = kAlignedDummy8;
+        absmax[i] = reinterpret_cast<const float*>(kAlignedDummy);
     }
-    if (all_sm)
-        return 2;
-    if (grouped_sm_passes(dtype, count, N, M, K, blocksize)) {
-        bool ok = true;
-        for (int i = 0; i < count; ++i)
-            ok = ok && gemm_4bit_sm_supported(dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N[i], K, blocksize);
-        if (ok)
-            return 2;
-    }
-    bool stream_sizes = true; // (gemv_4bit_grouped: every member below 2^32 elements)
-    for (int i = 0; i < count; ++i)
-        stream_sizes = stream_sizes && gemv_4bit_stream_size_ok(N[i], K);
-    return (!any_mfma && M <= 4 && stream_sizes) ? 1 : 0;
+    return gemm_4bit_grouped_route(dtype, kAlignedDummy, count, B, absmax, nullptr, N, M, K, blocksize);
 }
 size_t bnb_mi355x_gemm_4bit_workspace_bytes(int kernel, int dtype, int M, int N, int K, int blocksize) {
     // alignment of A/B is unknown here; assume the aligned (fast) case, an unused workspace is harmless
-    if (!route_to_mfma(kernel, dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N, K, blocksize, true))
-        return 0;
-    return gemm_4bit_mfma_workspace_bytes(M, N, K, blocksize);
+    return gemm_4bit_workspace_bytes(kernel, dtype, kAlignedDummy, kAlignedDummy8, reinterpret_cast<const float*>(kAlignedDummy), M, N, K, blocksize);
 }
 int bnb_mi355x_last_gemm_kernel(void) { return g_last_gemm_kernel; }
 
@@ -393,7 +268,7 @@ int bnb_mi355x_gemm_4bit_experts_ffn_supported(int dtype, int E, int N, int K, i
 void bnb_mi355x_gemm_4bit_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N,
                                 int K, int blocksize, int quant_type, bnb_stream_t s) {
     require_quant_type("gemm_4bit_gated", quant_type);
-    const int family = gated_family(dtype, A, B, absmax, M, N, K, blocksize);
+    const int family = gemm_4bit_gated_family(dtype, A, B, absmax, M, N, K, blocksize);
     const bool ok = family == kKernelSm       ? gemm_4bit_sm_gated(dtype, A, B, absmax, out, bias, M, N, K, blocksize, quant_type, S(s))
                     : family == kKernelStream ? gemv_4bit_stream_gated(dtype, A, B, absmax, out, bias, M, N, K, blocksize, quant_type, S(s))
                                               : false;
@@ -405,7 +280,7 @@ void bnb_mi355x_gemm_4bit_gated(int dtype, const void* A, const uint8_t* B, cons
 }
 int bnb_mi355x_gemm_4bit_gated_supported(int dtype, int M, int N, int K, int blocksize) {
     // (alignment of A / B / absmax is unknown here; the aligned case is assumed, as in the route query)
-    return gated_family(dtype, kAlignedDummy, kAlignedDummy8, reinterpret_cast<const float*>(kAlignedDummy), M, N, K, blocksize) != kKernelNone ? 1 : 0;
+    return gemm_4bit_gated_family(dtype, kAlignedDummy, kAlignedDummy8, reinterpret_cast<const float*>(kAlignedDummy), M, N, K, blocksize) != kKernelNone ? 1 : 0;
 }
 
 // ------------------------------------------------------------------ LoRA gemm_4bit (the adapter term as the decode kernels' epilogue)
@@ -413,7 +288,7 @@ void bnb_mi355x_gemm_4bit_lora(int dtype, const void* A, const uint8_t* B, const
                                const float* absmax_code, const float* absmax_offset, void* out, const void* bias, const void* lora_t,
                                const void* lora_b, float scaling, int r, int M, int N, int K, int blocksize, int quant_type, bnb_stream_t s) {
     require_quant_type("gemm_4bit_lora", quant_type);
-    const int family = lora_family(dtype, A, B, absmax, absmax_8bit, lora_t, lora_b, M, N, K, blocksize, r);
+    const int family = gemm_4bit_lora_family(dtype, A, B, absmax, absmax_8bit, lora_t, lora_b, M, N, K, blocksize, r);
     const bool ok = family == kKernelSm ? gemm_4bit_sm_lora(dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, lora_t, lora_b, scaling, r,
                                                             M, N, K, blocksize, quant_type, S(s))
                     : family == kKernelStream ? gemv_4bit_stream_lora(dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, lora_t, lora_b,
@@ -427,7 +302,7 @@ void bnb_mi355x_gemm_4bit_lora(int dtype, const void* A, const uint8_t* B, const
 }
 int bnb_mi355x_gemm_4bit_lora_supported(int dtype, int M, int N, int K, int blocksize, int nested, int r) {
     // (alignment is unknown here; the aligned case is assumed, as in the route query)
-    return lora_family(dtype, kAlignedDummy, kAlignedDummy8, reinterpret_cast<const float*>(kAlignedDummy), nested ? kAlignedDummy8 : nullptr, kAlignedDummy,
+    return gemm_4bit_lora_family(dtype, kAlignedDummy, kAlignedDummy8, reinterpret_cast<const float*>(kAlignedDummy), nested ? kAlignedDummy8 : nullptr, kAlignedDummy,
                        kAlignedDummy, M, N, K, blocksize, r) != kKernelNone
                ? 1
                : 0;
@@ -439,7 +314,7 @@ void bnb_mi355x_gemm_4bit_lora_ids(int dtype, const void* A, const uint8_t* B, c
                                    const void* lora_b, const float* scalings, const void* ids, int index_bytes, int A_n, int r, int M, int N, int K,
                                    int blocksize, int quant_type, bnb_stream_t s) {
     require_quant_type("gemm_4bit_lora_ids", quant_type);
-    const int family = lora_family(dtype, A, B, absmax, absmax_8bit, lora_t, lora_b, M, N, K, blocksize, r);
+    const int family = gemm_4bit_lora_family(dtype, A, B, absmax, absmax_8bit, lora_t, lora_b, M, N, K, blocksize, r);
     const bool ok = family == kKernelSm ? gemm_4bit_sm_lora_ids(dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, lora_t, lora_b,
                                                                 scalings, ids, index_bytes, A_n, r, M, N, K, blocksize, quant_type, S(s))
                     : family == kKernelStream ? gemv_4bit_stream_lora_ids(dtype, A, B, absmax, absmax_8bit, absmax_code, absmax_offset, out, bias, lora_t,
@@ -539,7 +414,7 @@ void bnb_mi355x_peer_chain_read(void* const* bufs, void* epoch_word, int world, 
 }
 int bnb_mi355x_gemm_4bit_route(int kernel, int dtype, int M, int N, int K, int blocksize) {
     // (alignment of A / B is unknown here; the aligned - fast - case is assumed, as in the workspace query)
-    return route_to_mfma(kernel, dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N, K, blocksize, true) ? 1 : 0;
+    return gemm_4bit_route(kernel, dtype, kAlignedDummy, kAlignedDummy8, reinterpret_cast<const float*>(kAlignedDummy), nullptr, nullptr, M, N, K, blocksize).kernel != kKernelStream ? 1 : 0;
 }
 void bnb_mi355x_gemm_4bit_grad_input(int dtype, const void* grad_out, const uint8_t* B, const float* absmax,
                                      const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, void* grad_A,
@@ -576,25 +451,13 @@ void bnb_mi355x_set_cu_count(int cus) { g_cu_count_override.store(cus > 0 ? cus 
 int bnb_mi355x_gemm_4bit_plan(int kernel, int dtype, int M, int N, int K, int blocksize, int nested, int* out16) {
     if (out16 == nullptr || M <= 0 || N <= 0 || K <= 0 || blocksize <= 0 || dtype < 0 || dtype > 2)
         return 0;
-    // (gemm_4bit_dispatch's question, with the aligned pointers of the shape-only queries)
-    const float* const absmax = reinterpret_cast<const float*>(kAlignedDummy);
-    const uint8_t* const absmax8 = nested ? kAlignedDummy8 : nullptr;
+    // (bnb_mi355x_gemm_4bit's question, with the aligned pointers of the shape-only queries)
     int v[16];
-    if (route_to_mfma(kernel, dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N, K, blocksize, !nested) &&
-        gemm_4bit_mfma_plan_query(dtype, kAlignedDummy, kAlignedDummy8, absmax, absmax8, M, N, K, blocksize, v)) {
-        for (int i = 0; i < 16; ++i)
-            out16[i] = v[i];
-        return 1;
-    }
-    if (g_mfma_knob1.load(std::memory_order_relaxed) / 100 == 60 && route_to_mfma(kernel, dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N, K, blocksize, !nested) &&
-        gemm_4bit_tall_supported(dtype, kAlignedDummy, kAlignedDummy8, nullptr, M, N, K, blocksize))
+    if (!gemm_4bit_plan_query(kernel, dtype, kAlignedDummy, kAlignedDummy8, reinterpret_cast<const float*>(kAlignedDummy), nested ? kAlignedDummy8 : nullptr, M, N, K,
+                              blocksize, v))
         return 0;
-    int g[8];
-    if (!gemv_4bit_stream_geometry(0, dtype, M, N, K, blocksize, g))
-        return 0;
-    const int w[16] = {kKernelStream, g[4], (M + g[6] - 1) / g[6], 1, 1, g[3], (K + 2047) / 2048, g[6], g[7], g[6], g[0], g[1], g[5], 2048, g[2], 0};
     for (int i = 0; i < 16; ++i)
-        out16[i] = w[i];
+        out16[i] = v[i];
     return 1;
 }
 int bnb_mi355x_gemm_4bit_sm_form_plan(int form, int dtype, int M, int N, const int* group_N, int K, int blocksize, int nested, int* out16) {
@@ -604,9 +467,9 @@ int bnb_mi355x_gemm_4bit_sm_form_plan(int form, int dtype, int M, int N, const i
     int v[16];
     bool ok = false;
     if (form == 1)
-        ok = !nested && gated_family(dtype, kAlignedDummy, kAlignedDummy8, absmax, M, N, K, blocksize) == kKernelSm && gemm_4bit_sm_plan_query(1, M, N, K, 0, v);
+        ok = !nested && gemm_4bit_gated_family(dtype, kAlignedDummy, kAlignedDummy8, absmax, M, N, K, blocksize) == kKernelSm && gemm_4bit_sm_plan_query(1, M, N, K, 0, v);
     else if (form <= 3)
-        ok = lora_family(dtype, kAlignedDummy, kAlignedDummy8, absmax, nested ? kAlignedDummy8 : nullptr, kAlignedDummy, kAlignedDummy, M, N, K, blocksize, 8) == kKernelSm &&
+        ok = gemm_4bit_lora_family(dtype, kAlignedDummy, kAlignedDummy8, absmax, nested ? kAlignedDummy8 : nullptr, kAlignedDummy, kAlignedDummy, M, N, K, blocksize, 8) == kKernelSm &&
              gemm_4bit_sm_plan_query(form, M, N, K, 0, v);
     else
         ok = group_N != nullptr && bnb_mi355x_gemm_4bit_grouped_route(dtype, N, group_N, M, K, blocksize) == 2 && gemm_4bit_sm_grouped_plan_query(N, group_N, M, K, v);

@@ -27,6 +27,8 @@
 // sweep records in profiles/r1_sweep_mfma_variants.txt, profiles/r2_mfma_ab.txt.
 #include "bnb_launchers.h"
 
+#include "../../include/bnb_mi355x.h" // (bnb_mi355x_gemm_4bit_fused_max_m is defined here, next to the predicates it states)
+
 #include <mutex>
 #include <unordered_map>
 
@@ -823,14 +825,6 @@ bool kq_selected(int M, int N, int K, int knob1, int* force_ks) {
         return weights >= (16L << 20);
     return false;
 }
-} // namespace
-
-// Whether the built-in route hands this problem to the streaming MFMA kernel (c_api.hip: such calls take the MFMA route from two
-// rows on; pointer alignment is gemm_4bit_mfma_supported's business)
-bool gemm_4bit_sm_routes(int dtype, int M, int N, int K, int blocksize) {
-    return dtype != 0 && blocksize >= 64 && (K % 64) == 0 &&
-           sm_selected(M, N, K, g_mfma_knob0.load(std::memory_order_relaxed), g_mfma_knob1.load(std::memory_order_relaxed));
-}
 
 // Preconditions of the MFMA kernels: 16-bit activations, K a multiple of 256, 16-byte aligned A, 8-byte aligned B, and a blocksize
 // >= 64 (a 64-k MFMA pair stays inside one quantization block) - or, round 5, blocksize 32 with fp32 absmax (`plain_absmax`: the
@@ -848,102 +842,226 @@ bool gemm_4bit_mfma_supported(int dtype, const void* A, const uint8_t* B, const 
     return dtype != 0 && M >= 1 && N >= 1 && (K % kKC) == 0 && is_pow2(blocksize) && blocksize >= 64 && aligned_to(A, 16) && aligned_to(B, 8);
 }
 
-// Bytes of fp32 slab workspace the launch heuristics would like for this problem (0 = none needed).
-size_t gemm_4bit_mfma_workspace_bytes(int M, int N, int K, int blocksize) {
-    if (M < 1 || N < 1 || K < kKC)
-        return 0;
-    if (blocksize == 32) // (served by the register-transposed kernel alone, whatever the shape)
-        return gemm_4bit_rt_workspace_bytes(M, N, K, 0);
-    int fks, fw;
-    const int knob1 = g_mfma_knob1.load(std::memory_order_relaxed);
-    // (the streaming MFMA kernel needs none; a call it turns down at launch time - a caller-supplied code table, misaligned
-    // statistics - runs the kernels below with the library's own buffer or fewer K slices)
-    if (blocksize >= 64 && sm_selected(M, N, K, g_mfma_knob0.load(std::memory_order_relaxed), knob1))
-        return 0;
-    if (K % kKC)
-        return 0; // (only the streaming MFMA kernel takes rows that are not whole 256-k chunks)
-    int qks;
-    size_t kq_bytes = 0;
-    if (kq_selected(M, N, K, knob1, &qks)) {
-        kq_bytes = gemm_4bit_kq_workspace_bytes(M, N, K, qks);
-        // (a call whose statistics or alignment the K-quarter kernel does not serve - gemm_4bit_kq_serves / _supported - runs the
-        // kernels below: the query does not know and answers with the larger of the two)
-    }
-    if (rt_selected(M, N, K, knob1, &fks, &fw)) {
-        const size_t b = gemm_4bit_rt_workspace_bytes(M, N, K, fks);
-        return b > kq_bytes ? b : kq_bytes;
-    }
-    const Plan pl = make_plan(M, N, K, knob1);
-    const size_t b = pl.ks > 1 ? static_cast<size_t>(pl.ks) * M * N * sizeof(float) : 0;
-    return b > kq_bytes ? b : kq_bytes;
-}
-
-namespace {
-// The kernel family a call that took the MFMA route launches, in the order the families are tried, with what the tuning knobs force
-// on it. gemm_4bit_mfma below and the plan query (gemm_4bit_mfma_plan_query) ask here. kKernelStream: the call leaves the route
-// again (the streaming kernel, or its generic fall-back).
-struct MfmaFamily {
-    int kernel;
-    int force_ks = 0, force_waves = 0; // register-transposed / K-quarter kernel: forced K slices, wavefronts (0 = built-in choice)
-};
-MfmaFamily mfma_family(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* code16, int M, int N, int K,
-                       int blocksize, int knob0, int knob1) {
-    int fks, fw, qks;
-    if (blocksize == 32) {
-        // blocksize 32: the register-transposed kernel's BS32 instances at any M (row passes over grid.z). The callers
-        // route here only what gemm_4bit_mfma_supported(..., plain_absmax) accepted; anything else is a caller's bug.
-        if (!gemm_4bit_rt_supported(dtype, A, B, code16, M, N, K, blocksize) || !gemm_4bit_rt_serves(absmax, absmax8, blocksize))
-            // (not reachable through route_to_mfma, which asks the same questions; a direct caller gets the streaming kernel, not exit(1))
-            return {kKernelStream};
-        return {kKernelRt};
-    }
-    if (knob1 / 100 == 60 && gemm_4bit_tall_supported(dtype, A, B, code16, M, N, K, blocksize)) // (tuning knob cfg 60: the tall-tile kernel)
-        return {kKernelTall};
-    if (sm_selected(M, N, K, knob0, knob1) && gemm_4bit_sm_supported(dtype, A, B, code16, M, N, K, blocksize) && gemm_4bit_sm_serves(absmax, absmax8, blocksize))
-        return {kKernelSm};
-    if (K % kKC) // (rows that are not whole 256-k chunks are the streaming MFMA kernel's alone: a call it turned down runs the streaming kernel)
-        return {kKernelStream};
-    if (kq_selected(M, N, K, knob1, &qks) && gemm_4bit_kq_supported(dtype, A, B, code16, M, N, K, blocksize) &&
-        gemm_4bit_kq_serves(absmax, absmax8, blocksize, K))
-        return {kKernelKq, qks, 0};
-    if (rt_selected(M, N, K, knob1, &fks, &fw) && gemm_4bit_rt_supported(dtype, A, B, code16, M, N, K, blocksize))
-        return {kKernelRt, fks, fw};
-    return {kKernelPc};
-}
+// M at or below which the streaming dot kernel is used (its activations live in registers: 32 fp32 per row and
+// lane); above it the MFMA kernels (when supported). MI355X-specific replacement for the reference's per-arch
+// heuristic (bitsandbytes/backends/cuda/ops.py:814-843), calibrated on gfx950 — see DESIGN.md.
+constexpr int kStreamMaxM = 4;
 } // namespace
 
-// The plan of a call on the MFMA route without the call (bnb_mi355x_gemm_4bit_plan; pointers: the alignment the caller assumes).
-// false: the call leaves the route for the streaming kernel, or runs the tall-tile kernel (a tuning knob's, no plan query).
-bool gemm_4bit_mfma_plan_query(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, int M, int N, int K, int blocksize,
-                               int* out16) {
+// THE answer to "what does this bnb_mi355x_gemm_4bit(kernel, ...) call launch": the kernel family, in the order the families are tried,
+// with what the tuning knobs force on it. Every launch and every query of the library asks here - the plain call, its workspace and
+// plan queries, the gated / LoRA forms (served where the plain call's family has the form) and the grouped call's decision - and this
+// is the only place that reads the knobs for routing. kKernelStream: the streaming kernel (or its generic fall-back). The shape-only
+// queries pass the aligned pointers of kAlignedDummy; absmax8 == nullptr and a 16-byte aligned absmax mean plain fp32 statistics,
+// what the MFMA route needs to know at blocksize 32, where only the register-transposed kernel's BS32 instances exist.
+// without_kq: the family the call runs where the K-quarter kernel turns it down (the workspace query, which does not know the statistics).
+Gemm4Route gemm_4bit_route(int kernel, int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* code16, int M,
+                           int N, int K, int blocksize, bool without_kq) {
     const int knob0 = g_mfma_knob0.load(std::memory_order_relaxed), knob1 = g_mfma_knob1.load(std::memory_order_relaxed);
-    const MfmaFamily f = mfma_family(dtype, A, B, absmax, absmax8, nullptr, M, N, K, blocksize, knob0, knob1);
-    switch (f.kernel) {
-    case kKernelSm: return gemm_4bit_sm_plan_query(0, M, N, K, knob0, out16);
-    case kKernelKq: gemm_4bit_kq_plan_query(M, N, K, absmax8 != nullptr, f.force_ks, out16); return true;
-    case kKernelRt: gemm_4bit_rt_plan_query(M, N, K, blocksize, f.force_ks, f.force_waves, out16); return true;
-    case kKernelPc: break;
-    default: return false;
+    const auto family = [&](int k, int force_ks = 0, int force_waves = 0) { return Gemm4Route{k, force_ks, force_waves, knob0, knob1}; };
+    if (kernel == 1 || kernel == 3)
+        return family(kKernelStream);
+    // the streaming MFMA kernel's own reach: 2 ... 16 rows on matrices of >= 128 rows (sm_selected has the measured exceptions), any
+    // K % 64 == 0 (the other MFMA kernels need whole 256-k chunks) - round 6
+    const bool sm = sm_selected(M, N, K, knob0, knob1) && gemm_4bit_sm_supported(dtype, A, B, code16, M, N, K, blocksize);
+    // three or four rows: the streaming kernel's FMA count grows with M while the MFMA kernel's does not - on matrices that
+    // fill the chip with 16-column workgroups the MFMA kernel is ahead from M = 3 (4096^2 6.5 vs 6.9 us, 4096 x 11008 10.8 vs
+    // 26.7), on small ones the streaming kernel's cheaper launch still wins (1376 x 4096 4.9 vs 5.3)
+    // round 6: from TWO rows on wherever the streaming MFMA kernel (gemm4_mfma_sm.hip) serves the shape - one decode for all rows,
+    // activations once per CU (4096^2 M = 2: 4.44 vs 4.95 us; profiles/r6_sm_v3_ab_full.txt)
+    const bool big = static_cast<long>(N) * K >= (12L << 20);
+    if (!sm && !((kernel == 2 || M > kStreamMaxM || (M >= 3 && big)) &&
+                 gemm_4bit_mfma_supported(dtype, A, B, code16, M, N, K, blocksize, absmax8 == nullptr && aligned_to(absmax, 16))))
+        return family(kKernelStream);
+    int fks, fw, qks;
+    if (blocksize == 32) // the register-transposed kernel's BS32 instances at any M (row passes over grid.z): gemm_4bit_mfma_supported asked
+        return family(kKernelRt);
+    if (knob1 / 100 == 60 && gemm_4bit_tall_supported(dtype, A, B, code16, M, N, K, blocksize)) // (tuning knob cfg 60: the tall-tile kernel)
+        return family(kKernelTall);
+    if (sm && gemm_4bit_sm_serves(absmax, absmax8, blocksize))
+        return family(kKernelSm);
+    if (K % kKC) // (rows that are not whole 256-k chunks are the streaming MFMA kernel's alone: a call it turned down runs the streaming kernel)
+        return family(kKernelStream);
+    if (!without_kq && kq_selected(M, N, K, knob1, &qks) && gemm_4bit_kq_supported(dtype, A, B, code16, M, N, K, blocksize) &&
+        gemm_4bit_kq_serves(absmax, absmax8, blocksize, K))
+        return family(kKernelKq, qks);
+    if (rt_selected(M, N, K, knob1, &fks, &fw) && gemm_4bit_rt_supported(dtype, A, B, code16, M, N, K, blocksize))
+        return family(kKernelRt, fks, fw);
+    return family(kKernelPc);
+}
+
+// Largest M for which bitsandbytes::gemm_4bit stays on the fused kernels (include/bnb_mi355x.h); above it one dequantize + hipBLASLt
+// GEMM moves fewer bytes per FLOP than re-streaming the packed weight per 64-row pass. Shapes and statistics only: no CU count, no knob.
+// Calibrated on MI355X, us per call, fused vs dequantize + hipBLASLt:
+//  * M = 512 (profiles/r4_route_ab.txt): 4096^2 24 vs 41, 8192^2 89 vs 111, 11008 x 4096 70 vs 78, 4096 x 11008 59 vs 94 - 512 rows everywhere;
+//  * 513 ... 1024 rows (round 5, profiles/r5_tall_small_ab.txt): the row passes of a call run side by side over grid.z, so on matrices
+//    with LONG rows (K >= 2 N: 2048 x 8192, 1376 x 4096, 4096 x 11008) the fused call stays 8 - 30 % ahead up to 1024 rows, on square-ish
+//    ones (10 K >= 7 N: 4096^2, 3072^2, 5120^2, 5120 x 3584) up to 640 rows, and on wide ones (8192 x 2048, 11008 x 4096) it loses from
+//    576 on. Measured up to 45 M weights: the extended ranges apply up to 48 M, larger matrices keep 512 (8192^2 at M = 1024: 178 vs 144).
+//    They were measured on the K-quarter kernel, so they hold where it serves the statistics (gemm_4bit_kq_serves); other nested calls run
+//    the producer/consumer kernel and keep 512;
+//  * calls the MFMA kernels do not serve (K not a multiple of 256 - e.g. K = 2752, a 4-way shard of an 11008-wide projection -, or
+//    blocksize 32 with double-quantised statistics) run the streaming kernel in 4-row passes: ahead of dequantize + GEMM up to 12 rows,
+//    level at 16, 3 - 4 x behind at 64 (profiles/r5_tall_small_ab.txt, second table);
+//  * rows that are not whole 256-k chunks (K % 64 == 0) on matrices of >= kSmMinRows rows: the streaming MFMA kernel's row passes, ahead or
+//    level to 128 rows (sm_selected quotes profiles/r6_sm_rows32_ab.txt; small matrices, profiles/r6_sm_small_n_ab.txt: 1376 x 2752
+//    M = 16 / 64 4.5 / 8.1 us against 16.2 / 56.6 for the streaming kernel's passes);
+//  * blocksize 32 (plain statistics) runs the register-transposed kernel's BS32 instances, 64-row passes one after the other: 4096^2 fused
+//    vs unfused 11.5 vs 28.9 us at 64 rows, 21.0 vs 37.5 at 128, 39.1 vs 33.1 at 256, 75 vs 40 at 512 (profiles/r5_tall_small_ab.txt, table 3);
+//  * fp32 activations: the streaming kernel (fp32 FMA decode, same code path as bf16 / fp16) for decode-sized batches; no fp32 MFMA path
+//    worth having above that (1/16 of the bf16 matrix rate).
+extern "C" __attribute__((visibility("default"))) int bnb_mi355x_gemm_4bit_fused_max_m(int dtype, int N, int K, int blocksize, int nested) {
+    if (dtype == 0)
+        return kStreamMaxM;
+    if (K % kKC != 0 && K % 64 == 0 && blocksize >= 64 && N >= kSmMinRows)
+        return 128;
+    if (K % kKC != 0 || blocksize < 32 || (blocksize == 32 && nested))
+        return 16;
+    if (blocksize == 32)
+        return 128;
+    const long weights = static_cast<long>(N) * K;
+    if (weights <= (48L << 20) && blocksize >= 64 && gemm_4bit_kq_serves(reinterpret_cast<const float*>(kAlignedDummy), nested ? kAlignedDummy8 : nullptr, blocksize, K)) {
+        if (K >= 2L * N)
+            return 1024;
+        if (10L * K >= 7L * N)
+            return 640;
     }
-    const Plan pl = make_plan(M, N, K, knob1);
-    const int cfg = pc_cfg_launched(pl.cfg, pl.mt), cw = pc_cw(cfg), ntw = pc_ntw(cfg);
-    const bool nested = absmax8 != nullptr;
-    const int groups = K / kKC, per = (groups + pl.ks - 1) / pl.ks;
-    const int v[16] = {kKernelPc, (N + cw * ntw * 16 - 1) / (cw * ntw * 16), pl.ks, (M + pl.mt * 16 - 1) / (pl.mt * 16), pl.ks, per, groups, pl.mt,
-                       cw + kPcProducers, 16 * pl.mt, cw * ntw * 16, 0,
-                       static_cast<int>(pc_smem_bytes(pl.mt, cw, ntw, pc_depth(pl.mt, cw, ntw, nested), nested)), kKC, pc_depth(pl.mt, cw, ntw, nested), cfg};
+    return 512;
+}
+
+// Bytes of fp32 slab workspace the launch heuristics would like for this call (0 = none needed); pointers: the alignment the caller
+// assumes, statistics: plain fp32 ones. Where the route names the K-quarter kernel the answer covers the next family as well: a call
+// whose statistics that kernel does not serve (gemm_4bit_kq_serves) runs it, and the query does not know.
+size_t gemm_4bit_workspace_bytes(int kernel, int dtype, const void* A, const uint8_t* B, const float* absmax, int M, int N, int K, int blocksize) {
+    if (M < 1 || N < 1 || K < kKC)
+        return 0;
+    size_t kq_bytes = 0, bytes = 0;
+    Gemm4Route r = gemm_4bit_route(kernel, dtype, A, B, absmax, nullptr, nullptr, M, N, K, blocksize);
+    if (r.kernel == kKernelKq) {
+        kq_bytes = gemm_4bit_kq_workspace_bytes(M, N, K, r.force_ks);
+        r = gemm_4bit_route(kernel, dtype, A, B, absmax, nullptr, nullptr, M, N, K, blocksize, true);
+    }
+    if (r.kernel == kKernelRt) {
+        bytes = gemm_4bit_rt_workspace_bytes(M, N, K, r.force_ks);
+    } else if (r.kernel == kKernelPc || r.kernel == kKernelTall) { // (the tall-tile knob: that kernel uses none; answered as without the knob)
+        const Plan pl = make_plan(M, N, K, r.knob1);
+        bytes = pl.ks > 1 ? static_cast<size_t>(pl.ks) * M * N * sizeof(float) : 0;
+    } // (the streaming kernels need none; a call the streaming MFMA kernel turns down at launch time - a caller-supplied code table -
+      // runs the other kernels with the library's own buffer or fewer K slices)
+    return bytes > kq_bytes ? bytes : kq_bytes;
+}
+
+// The plan of a call without the call (bnb_mi355x_gemm_4bit_plan; pointers: the alignment the caller assumes). false: no plan - the
+// tall-tile kernel (a tuning knob's, no plan query), or a shape the streaming kernel has no geometry for.
+bool gemm_4bit_plan_query(int kernel, int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, int M, int N, int K,
+                          int blocksize, int* out16) {
+    const Gemm4Route r = gemm_4bit_route(kernel, dtype, A, B, absmax, absmax8, nullptr, M, N, K, blocksize);
+    switch (r.kernel) {
+    case kKernelTall: return false;
+    case kKernelSm:
+        if (gemm_4bit_sm_plan_query(0, M, N, K, r.knob0, out16))
+            return true;
+        break;
+    case kKernelKq: gemm_4bit_kq_plan_query(M, N, K, absmax8 != nullptr, r.force_ks, out16); return true;
+    case kKernelRt: gemm_4bit_rt_plan_query(M, N, K, blocksize, r.force_ks, r.force_waves, out16); return true;
+    case kKernelPc: {
+        const Plan pl = make_plan(M, N, K, r.knob1);
+        const int cfg = pc_cfg_launched(pl.cfg, pl.mt), cw = pc_cw(cfg), ntw = pc_ntw(cfg);
+        const bool nested = absmax8 != nullptr;
+        const int groups = K / kKC, per = (groups + pl.ks - 1) / pl.ks;
+        const int v[16] = {kKernelPc, (N + cw * ntw * 16 - 1) / (cw * ntw * 16), pl.ks, (M + pl.mt * 16 - 1) / (pl.mt * 16), pl.ks, per, groups, pl.mt,
+                           cw + kPcProducers, 16 * pl.mt, cw * ntw * 16, 0,
+                           static_cast<int>(pc_smem_bytes(pl.mt, cw, ntw, pc_depth(pl.mt, cw, ntw, nested), nested)), kKC, pc_depth(pl.mt, cw, ntw, nested), cfg};
+        for (int i = 0; i < 16; ++i)
+            out16[i] = v[i];
+        return true;
+    }
+    default: break;
+    }
+    int g[8];
+    if (!gemv_4bit_stream_geometry(0, dtype, M, N, K, blocksize, g))
+        return false;
+    const int w[16] = {kKernelStream, g[4], (M + g[6] - 1) / g[6], 1, 1, g[3], (K + 2047) / 2048, g[6], g[7], g[6], g[0], g[1], g[5], 2048, g[2], 0};
     for (int i = 0; i < 16; ++i)
-        out16[i] = v[i];
+        out16[i] = w[i];
     return true;
 }
 
-void gemm_4bit_mfma(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
-                    const float* absmax_code, const float* absmax_offset, const float* code16, void* out,
-                    const void* bias, int M, int N, int K, int blocksize, int quant_type, void* workspace,
-                    size_t workspace_bytes, hipStream_t stream) {
-    const int knob0 = g_mfma_knob0.load(std::memory_order_relaxed), knob1 = g_mfma_knob1.load(std::memory_order_relaxed);
-    const MfmaFamily f = mfma_family(dtype, A, B, absmax, absmax8, code16, M, N, K, blocksize, knob0, knob1);
-    switch (f.kernel) {
+// Gated call (bnb_mi355x_gemm_4bit_gated) on the interleaved [N = 2F, K] matrix at M rows: the kernel FAMILY the plain call on the
+// same matrix and M runs - so that the gated result is the plain result's silu(gate) * up bit for bit - when that family has a gated
+// form: kKernelStream or kKernelSm, else 0 (not supported). 16-bit activations, fp32 absmax, 1 <= M <= 16, blocksize >= 64, whole
+// quantization blocks per row, aligned pointers.
+int gemm_4bit_gated_family(int dtype, const void* A, const uint8_t* B, const float* absmax, int M, int N, int K, int blocksize) {
+    if ((dtype != 1 && dtype != 2) || M < 1 || M > 16 || N < 2 || (N & 1) || K <= 0 || blocksize < 64 || !is_pow2(blocksize) || (K % blocksize) != 0 ||
+        !aligned_to(A, 16) || !aligned_to(B, 16) || !aligned_to(absmax, 4))
+        return kKernelNone;
+    switch (gemm_4bit_route(0, dtype, A, B, absmax, nullptr, nullptr, M, N, K, blocksize).kernel) {
+    case kKernelSm: return gemm_4bit_sm_gated_supported(dtype, A, B, M, N, K, blocksize) ? kKernelSm : kKernelNone;
+    case kKernelStream: return gemv_4bit_stream_gated_supported(dtype, M, N, K, blocksize) ? kKernelStream : kKernelNone;
+    default: return kKernelNone;
+    }
+}
+
+// LoRA call (bnb_mi355x_gemm_4bit_lora) at M rows: the kernel FAMILY the plain bnb_mi355x_gemm_4bit call on the same matrix, M and
+// statistics runs - the adapter term is an epilogue of that launch, everything in front of it the plain instance's - when that family
+// has the epilogue: kKernelStream or kKernelSm, else 0 (not supported). 16-bit activations, 1 <= M <= 16, blocksize >= 64, whole
+// quantization blocks per row, r a multiple of 8 in [8, 128], aligned pointers.
+int gemm_4bit_lora_family(int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const void* lora_t, const void* lora_b,
+                          int M, int N, int K, int blocksize, int r) {
+    if ((dtype != 1 && dtype != 2) || M < 1 || M > 16 || N < 1 || K <= 0 || blocksize < 64 || !is_pow2(blocksize) || (K % blocksize) != 0 || r < 8 || r > 128 ||
+        (r % 8) != 0 || !aligned_to(A, 16) || !aligned_to(B, 16) || !aligned_to(absmax, 4) || !aligned_to(lora_t, 16) || !aligned_to(lora_b, 16))
+        return kKernelNone;
+    switch (gemm_4bit_route(0, dtype, A, B, absmax, absmax8, nullptr, M, N, K, blocksize).kernel) {
+    case kKernelSm: return gemm_4bit_sm_lora_supported(dtype, A, B, M, N, K, blocksize, r) ? kKernelSm : kKernelNone;
+    case kKernelStream: return gemv_4bit_stream_lora_supported(dtype, M, N, K, blocksize, r) ? kKernelStream : kKernelNone;
+    default: return kKernelNone;
+    }
+}
+
+// What bnb_mi355x_gemm_4bit_grouped does with a group, tried in this order (the launch asks with its pointers, the shape-only query
+// with aligned ones and members of one kind of statistics):
+//  2: up to 8 members whose own calls ALL run the streaming MFMA kernel (2 ... 16 rows, sm_selected): ONE launch of that kernel over
+//     the members' rows - bit-identical to separate calls (the same kernel family, and its summation order does not depend on the
+//     launch geometry);
+//  2: a group of 17 ... 64 rows as ONE launch of the streaming MFMA kernel as well - although no member's own route at that many rows is
+//     this kernel: its 32-row instances multiply two 16-row blocks against every decoded weight fragment (row passes of 32 over grid.y
+//     above that; small groups: passes of 16 side by side on the CUs they leave idle), and the group shares one boundary, one table
+//     build and one activation fetch per CU. Measured (profiles/r6_grouped_ab.txt, third table; us per group, grouped launch vs the
+//     members one by one): 4 x 4096^2 M = 24 / 32 / 48 / 64 17.2 / 17.3 / 29.6 / 30.2 vs 32.9 / 33.4 / 39.4 / 44.4; 4096 + 2 x 1024
+//     (x 4096) 11.0 / 11.3 / 19.7 / 20.0 vs 19.4 / 20.2 / 21.6 / 22.8; 3 x 512 x 4096 5.9 / 5.9 / 7.9 / 7.9 vs 15.1 / 15.3 / 15.4 / 15.4;
+//     2 x 11008 x 4096 26.8 / 27.0 vs 28.0 / 28.4 but 47.4 / 48.4 vs 35.0 / 35.5 at 48 / 64 rows; 2 x 14336 x 4096 and 3 x 8192^2 behind
+//     (big members keep their own kernels). Such a group is NOT bit-identical to separate calls (another kernel family: the oracle's
+//     tolerance, like every fused call);
+//  1: no member's own call runs an MFMA kernel, M <= 4: ONE launch of the streaming kernel (gemv_4bit_grouped: K % 32 == 0,
+//     single-phase rows), bit-identical to separate calls;
+//  0: everything else (mixed routes, more than 8 matrices; also what a group either launcher refuses ends as): matrix by matrix.
+int gemm_4bit_grouped_route(int dtype, const void* A, int count, const uint8_t* const* B, const float* const* absmax, const uint8_t* const* absmax8,
+                            const int* N, int M, int K, int blocksize) {
+    if (count <= 0 || count > 8 || M <= 0 || blocksize <= 0 || K % blocksize != 0)
+        return 0;
+    bool any_mfma = false, all_sm = true, sm_serves_all = true, stream_sizes = true;
+    long long weights = 0;
+    for (int i = 0; i < count; ++i) {
+        const int family = gemm_4bit_route(0, dtype, A, B[i], absmax[i], absmax8 ? absmax8[i] : nullptr, nullptr, M, N[i], K, blocksize).kernel;
+        any_mfma = any_mfma || family != kKernelStream;
+        all_sm = all_sm && family == kKernelSm;
+        sm_serves_all = sm_serves_all && gemm_4bit_sm_supported(dtype, A, B[i], nullptr, M, N[i], K, blocksize);
+        stream_sizes = stream_sizes && gemv_4bit_stream_size_ok(N[i], K); // (gemv_4bit_grouped: every member below 2^32 elements)
+        weights += static_cast<long long>(N[i]) * K;
+    }
+    const bool passes = sm_serves_all && M > 16 && M <= 64 && count >= 2 && g_mfma_knob0.load(std::memory_order_relaxed) == 0 &&
+                        g_mfma_knob1.load(std::memory_order_relaxed) == 0 && weights <= (M <= 32 ? (96LL << 20) : (72LL << 20));
+    if (all_sm || passes)
+        return 2;
+    return !any_mfma && M <= 4 && stream_sizes ? 1 : 0;
+}
+
+void gemm_4bit(int kernel, int dtype, const void* A, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+               const float* absmax_offset, const float* code16, void* out, const void* bias, int M, int N, int K, int blocksize, int quant_type,
+               void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    const Gemm4Route r = gemm_4bit_route(kernel, dtype, A, B, absmax, absmax8, code16, M, N, K, blocksize);
+    const int knob0 = r.knob0, knob1 = r.knob1;
+    switch (r.kernel) {
     case kKernelStream:
         return gemv_4bit_stream(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, code16, out, bias, M, N, K, blocksize, quant_type, stream);
     case kKernelTall:
@@ -952,11 +1070,11 @@ void gemm_4bit_mfma(int dtype, const void* A, const uint8_t* B, const float* abs
         return gemm_4bit_sm(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, M, N, K, blocksize, quant_type, knob0, stream);
     case kKernelKq:
         return gemm_4bit_kq(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, M, N, K, blocksize, quant_type,
-                            workspace, workspace_bytes, f.force_ks, knob0, stream);
+                            workspace, workspace_bytes, r.force_ks, knob0, stream);
     case kKernelRt:
-        // (blocksize 32: built-in slices and wavefronts, no variant - mfma_family leaves the forces at 0 there)
+        // (blocksize 32: built-in slices and wavefronts, no variant - the route leaves the forces at 0 there)
         return gemm_4bit_rt(dtype, A, B, absmax, absmax8, absmax_code, absmax_offset, out, bias, M, N, K, blocksize,
-                            quant_type, workspace, workspace_bytes, f.force_ks, f.force_waves, blocksize == 32 ? 0 : (knob0 & 1), stream);
+                            quant_type, workspace, workspace_bytes, r.force_ks, r.force_waves, blocksize == 32 ? 0 : (knob0 & 1), stream);
     default:
         break;
     }

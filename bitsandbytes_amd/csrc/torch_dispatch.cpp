@@ -29,38 +29,7 @@
 
 namespace {
 
-// keep in step with bitsandbytes_amd/backends/hip.py (FUSED_MAX_M, FUSED_MAX_M_LONG_ROWS, FUSED_MAX_M_SQUARE, FUSED_TALL_WEIGHTS,
-// STREAM_ONLY_MAX_M, SM_TAIL_MAX_M, SM_MIN_ROWS, _REFERENCE_CUSTOM_MAX_M, fused_max_m, _gemm_4bit_route - the measurements behind the numbers are quoted there);
-// the GPU test tests/test_gpu_parity.py::test_native_dispatch_matches_python_kernel runs both over fused and unfused shapes,
-// tests/test_cabi.py pins the constants and the function against the Python twin
-constexpr int64_t kFusedMaxM = 512;
-constexpr int64_t kFusedMaxMLongRows = 1024; // K >= 2 N
-constexpr int64_t kFusedMaxMSquare = 640;    // 10 K >= 7 N
-constexpr int64_t kFusedTallWeights = 50331648; // 48 << 20
-constexpr int64_t kStreamOnlyMaxM = 16;
-constexpr int64_t kSmTailMaxM = 128;  // rows that are not whole 256-k chunks: the streaming MFMA kernel's row passes (>= kSmMinRows rows)
-constexpr int64_t kSmMinRows = 128;
-constexpr int64_t kFusedMaxMBs32 = 128; // blocksize 32, plain statistics: the register-transposed kernel's row passes
-constexpr int64_t kFusedMaxMFp32 = 4;
-constexpr int64_t kReferenceCustomMaxM = 256; // reference backends/cuda/ops.py:816
-
-// Largest batch the fused 16-bit kernels are used for on an N x K weight (backends/hip.py: fused_max_m)
-int64_t fused_max_m(int64_t N, int64_t K, int64_t blocksize, bool nested) {
-    if (K % 256 != 0 && K % 64 == 0 && blocksize >= 64 && N >= kSmMinRows)
-        return kSmTailMaxM; // the streaming MFMA kernel's row passes
-    if (K % 256 != 0 || blocksize < 32 || (blocksize == 32 && nested))
-        return kStreamOnlyMaxM; // the MFMA kernels do not serve the call: the streaming kernel's 4-row passes
-    if (blocksize == 32)
-        return kFusedMaxMBs32;
-    // (the extended ranges were measured on the K-quarter kernel: nested statistics only at blocksize 64 and K <= 16384)
-    if (N * K <= kFusedTallWeights && blocksize >= 64 && (!nested || (blocksize == 64 && K <= 16384))) {
-        if (K >= 2 * N)
-            return kFusedMaxMLongRows;
-        if (10 * K >= 7 * N)
-            return kFusedMaxMSquare;
-    }
-    return kFusedMaxM;
-}
+constexpr int64_t kReferenceCustomMaxM = 256; // the reference's warning threshold (backends/cuda/ops.py:816); not routing
 
 int dtype_code(at::ScalarType t) {
     switch (t) {
@@ -150,7 +119,7 @@ at::Tensor gemm_4bit_hip(const at::Tensor& A_in, const at::Tensor& B_in, at::Int
     const at::Tensor B = B_in.contiguous();
     const at::Tensor absmax = absmax_in.contiguous();
 
-    // ---- MI355X routing (backends/hip.py:_gemm_4bit_route; replaces reference backends/cuda/ops.py:814-843,921-962)
+    // ---- MI355X routing (the library's bnb_mi355x_gemm_4bit_fused_max_m; replaces reference backends/cuda/ops.py:814-843,921-962)
     bool fused;
     if (blocksize <= 0 || K % blocksize != 0) {
         if (M <= kReferenceCustomMaxM)
@@ -158,7 +127,9 @@ at::Tensor gemm_4bit_hip(const at::Tensor& A_in, const at::Tensor& B_in, at::Int
                                ", falling back to slower implementation."));
         fused = false;
     } else {
-        fused = M <= (dt == 0 ? kFusedMaxMFp32 : fused_max_m(N, K, blocksize, absmax_8bit_in.has_value()));
+        check_c_int(N, "gemm_4bit N");
+        check_c_int(K, "gemm_4bit K");
+        fused = M <= bnb_mi355x_gemm_4bit_fused_max_m(dt, static_cast<int>(N), static_cast<int>(K), static_cast<int>(blocksize), absmax_8bit_in.has_value());
     }
 
     if (!fused) {
@@ -187,8 +158,6 @@ at::Tensor gemm_4bit_hip(const at::Tensor& A_in, const at::Tensor& B_in, at::Int
     }
 
     check_c_int(M, "gemm_4bit M");
-    check_c_int(N, "gemm_4bit N");
-    check_c_int(K, "gemm_4bit K");
     auto out_sizes = A.sizes().vec();
     out_sizes.back() = N;
     at::Tensor out = at::empty(out_sizes, A.options());

@@ -145,6 +145,12 @@ size_t bnb_mi355x_gemm_4bit_workspace_bytes(int kernel, int dtype, int M, int N,
  * scalar kernel (family 2, 64-bit addressing, correct and slow); the gated, LoRA and grouped-streaming forms answer "not supported"
  * there. The expert-indexed kernel (E * N < 2^31 rows) and the fused backward have no element limit. */
 int bnb_mi355x_gemm_4bit_route(int kernel, int dtype, int M, int N, int K, int blocksize);
+/* The fused range of bitsandbytes::gemm_4bit, stated once for every dispatcher of the op (the C++-registered kernel, the Python one,
+ * the tests): the largest M at which a call on an N x K weight of this blocksize and kind of statistics (nested: double-quantised)
+ * stays on the fused kernels above; taller batches dequantize once and run a dense GEMM. fp16 / bf16: one of 16, 128, 512, 640, 1024
+ * (the measurements are quoted at the definition, csrc/gemm4_mfma.hip); fp32: 4. A pure function of its arguments: it reads neither the
+ * CU count nor the tuning knobs, so a caller may cache the answer. K % blocksize != 0 is the caller's to refuse. */
+int bnb_mi355x_gemm_4bit_fused_max_m(int dtype, int N, int K, int blocksize, int nested);
 /* Which kernel family the calling thread's LAST gemm_4bit / gemv_4bit call (any entry point) launched: 0 none yet, 1 streaming
  * kernel (gemv4_stream_kernel), 2 generic scalar kernel (odd shapes), 3 register-transposed MFMA kernel (gemm4_mfma_rt_kernel),
  * 4 producer/consumer MFMA kernel (gemm4_mfma_pc_kernel), 6 K-quarter MFMA kernel (gemm4_mfma_kq_kernel),

@@ -37,28 +37,14 @@ BLOCKSIZES = (32, 64, 128)
 FAMILY = {1: "stream", 7: "sm", 3: "rt", 4: "pc", 6: "kq"}
 GRAD_MS = (8, 32, 64)
 DT_BF16 = 2
-# backends/hip.py: fused_max_m (the census runs without torch; tests/test_cu_count_host.py holds the two together)
-SM_MIN_ROWS, SM_TAIL_MAX_M, STREAM_ONLY_MAX_M, FUSED_MAX_M_BS32 = 128, 128, 16, 128
-FUSED_TALL_WEIGHTS, FUSED_MAX_M_LONG_ROWS, FUSED_MAX_M_SQUARE, FUSED_MAX_M = 48 << 20, 1024, 640, 512
-
-
-def fused_max_m(N, K, blocksize, nested):
-    if K % 256 != 0 and K % 64 == 0 and blocksize >= 64 and N >= SM_MIN_ROWS:
-        return SM_TAIL_MAX_M
-    if K % 256 != 0 or blocksize < 32 or (blocksize == 32 and nested):
-        return STREAM_ONLY_MAX_M
-    if blocksize == 32:
-        return FUSED_MAX_M_BS32
-    if N * K <= FUSED_TALL_WEIGHTS and blocksize >= 64 and (not nested or (blocksize == 64 and K <= 16384)):
-        if K >= 2 * N:
-            return FUSED_MAX_M_LONG_ROWS
-        if 10 * K >= 7 * N:
-            return FUSED_MAX_M_SQUARE
-    return FUSED_MAX_M
 
 
 def load(path):
     return C.load(path)
+
+
+def fused_max_m(lib, N, K, blocksize, nested):
+    return lib.bnb_mi355x_gemm_4bit_fused_max_m(DT_BF16, N, K, blocksize, nested)
 
 
 def _plan(lib, cus, M, N, K, bs, nested):
@@ -86,11 +72,11 @@ def pick(lib):
                     key=lambda s: (s[0] * s[1], s[2], s[3], s[0]))
     base = {}
     for s in shapes:
-        ms = [m for m in C.MS if m <= fused_max_m(*s) + 1]
-        base[s] = (ms, [_plan(lib, 256, m, *s) if m <= fused_max_m(*s) else None for m in ms])
+        ms = [m for m in C.MS if m <= fused_max_m(lib, *s) + 1]
+        base[s] = (ms, [_plan(lib, 256, m, *s) if m <= fused_max_m(lib, *s) else None for m in ms])
     cells, report = {}, []
     for cus in OVERRIDES:
-        here = {s: [_plan(lib, cus, m, *s) if m <= fused_max_m(*s) else None for m in base[s][0]] for s in shapes}
+        here = {s: [_plan(lib, cus, m, *s) if m <= fused_max_m(lib, *s) else None for m in base[s][0]] for s in shapes}
         for fam, name in FAMILY.items():
             for kind in ("plan", "route"):
                 found = None
@@ -110,7 +96,7 @@ def pick(lib):
     for (cus, N, K, bs, nested), why in sorted(cells.items()):
         s = (N, K, bs, nested)
         ms, b = base[s]
-        a = [_plan(lib, cus, m, *s) if m <= fused_max_m(*s) else None for m in ms]
+        a = [_plan(lib, cus, m, *s) if m <= fused_max_m(lib, *s) else None for m in ms]
         keep = [i for i in range(len(ms)) if a[i] is not None and a[i] != b[i]]
         gemm.append(dict(cus=cus, N=N, K=K, blocksize=bs, nested=bool(nested), why=why, Ms=[ms[i] for i in keep], plans=[a[i] for i in keep],
                          plans_256=[b[i] for i in keep]))

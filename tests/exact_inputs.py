@@ -194,7 +194,7 @@ class SweepCase:
         return (self.N * 31 + self.K * 7 + self.blocksize + (1 if self.nested else 0)) % (1 << 31)
 
 
-# One case per branch of the routing tables (backends/hip.py: fused_max_m; csrc/c_api.hip: route_to_mfma; csrc/gemm4_mfma.hip:
+# One case per branch of the routing tables (backends/hip.py: fused_max_m; csrc/gemm4_mfma.hip: gemm_4bit_route; csrc/gemm4_mfma.hip:
 # sm_selected, kq_selected, rt_selected, make_plan). The comment names what the case is there for.
 SWEEP_CASES = (
     SweepCase("4096x4096", 4096, 4096),                        # square-ish: fused to 640; sm 2-16, rt 17-48, pc, kq from 65, grid.z passes
@@ -218,7 +218,7 @@ SWEEP_CASES = (
     SweepCase("4096x4096-fp32", 4096, 4096, dtype=torch.float32),  # fp32 activations: fused to 4 rows only
 )
 
-FUSED_MAX_M_FP32 = 4  # (backends/hip.py: _gemm_4bit_route)
+FUSED_MAX_M_FP32 = 4  # (bnb_mi355x_gemm_4bit_fused_max_m at fp32)
 
 
 def sweep_ms(fused_max: int):

@@ -303,7 +303,7 @@ def first_wrong_row(y: torch.Tensor, ref: torch.Tensor):
 
 # ------------------------------------------------------------------------------------------ the ledger: the source predicates, restated
 KC = 256                # csrc/gemm4_mfma.hip: kKC, the MFMA kernels' k chunk
-STREAM_MAX_M = 4        # csrc/c_api.hip: kStreamMaxM
+STREAM_MAX_M = 4        # csrc/gemm4_mfma.hip: kStreamMaxM
 SM_MIN_ROWS = 128       # csrc/gemm4_mfma.hip: kSmMinRows
 DEFAULT_CUS = 256       # csrc/bnb_common.h: device_cu_count_or_default without a device; the MI355X has as many
 
@@ -345,7 +345,7 @@ def mfma_supported(M: int, N: int, K: int, bs: int) -> bool:
 
 
 def expected_route(M: int, N: int, K: int, bs: int, cus: int = DEFAULT_CUS) -> int:
-    """csrc/c_api.hip: route_to_mfma (kernel 0) for 16-bit activations: 1 = an MFMA kernel, 0 = the streaming / generic kernel."""
+    """csrc/gemm4_mfma.hip: gemm_4bit_route (kernel 0) for 16-bit activations: 1 = an MFMA kernel, 0 = the streaming / generic kernel."""
     sm = bs >= 64 and K % 64 == 0 and sm_selected(M, N, K, cus) and sm_supported(M, N, K, bs)
     big = N * K >= (12 << 20)
     return int(sm or ((M > STREAM_MAX_M or (M >= 3 and big)) and mfma_supported(M, N, K, bs)))

@@ -467,61 +467,56 @@ def test_bench_dump_outputs_full_and_sampled(tmp_path, monkeypatch):
 
 
 def test_native_dispatch_routing_constants_match_python():
-    """csrc/torch_dispatch.cpp repeats the routing thresholds of backends/hip.py (the two kernels of bitsandbytes::gemm_4bit must
-    route identically; the GPU test compares their results, this one pins the constants on a host without a GPU)."""
-    from bitsandbytes_amd.backends import hip
+    """The fused range of bitsandbytes::gemm_4bit is stated once, in the library (bnb_mi355x_gemm_4bit_fused_max_m); the Python kernel
+    of the op (backends/hip.py) and the C++-registered one (csrc/torch_dispatch.cpp) both ask it. Pinned on a host without a GPU: the
+    values at the thresholds, the whole answer over a grid of shapes (sha256 of the space-joined answers, computed from the three
+    restatements this function replaced), and that the dispatcher library imports the symbol instead of carrying a copy."""
+    import hashlib
+    import shutil
+    import subprocess
 
-    src = open(os.path.join(ROOT, "bitsandbytes_amd", "csrc", "torch_dispatch.cpp")).read()
-
-    def const(name):
-        m = re.search(rf"constexpr\s+int64_t\s+{name}\s*=\s*(\d+)\s*;", src)
-        assert m, name
-        return int(m.group(1))
-
-    assert const("kFusedMaxM") == hip.FUSED_MAX_M
-    assert const("kFusedMaxMLongRows") == hip.FUSED_MAX_M_LONG_ROWS
-    assert const("kFusedMaxMSquare") == hip.FUSED_MAX_M_SQUARE
-    assert const("kFusedTallWeights") == hip.FUSED_TALL_WEIGHTS
-    assert const("kStreamOnlyMaxM") == hip.STREAM_ONLY_MAX_M
-    assert const("kSmTailMaxM") == hip.SM_TAIL_MAX_M and const("kSmMinRows") == hip.SM_MIN_ROWS
-    assert const("kFusedMaxMBs32") == hip.FUSED_MAX_M_BS32
-    assert const("kReferenceCustomMaxM") == hip._REFERENCE_CUSTOM_MAX_M
-    # fp32 activations: fused up to 4 rows in both
-    assert const("kFusedMaxMFp32") == 4
     import torch
 
+    from bitsandbytes_amd import cextension as ce
+    from bitsandbytes_amd.backends import hip
+
     assert hip._gemm_4bit_route(torch.float32, 4, 64, 64, 64) == "fused" and hip._gemm_4bit_route(torch.float32, 5, 64, 64, 64) == "unfused"
-    # K = 64 is not a multiple of 256: the MFMA kernels do not serve it, the streaming kernel's passes stop at STREAM_ONLY_MAX_M
-    assert hip._gemm_4bit_route(torch.bfloat16, hip.STREAM_ONLY_MAX_M, 64, 64, 64) == "fused"
-    assert hip._gemm_4bit_route(torch.bfloat16, hip.STREAM_ONLY_MAX_M + 1, 64, 64, 64) == "unfused"
-    # (round 6: K % 64 == 0 rows on >= SM_MIN_ROWS-row matrices take the streaming MFMA kernel's row passes up to SM_TAIL_MAX_M rows)
+    # K = 64 is not a multiple of 256: the MFMA kernels do not serve it, the streaming kernel's passes stop at 16 rows
+    assert hip._gemm_4bit_route(torch.bfloat16, 16, 64, 64, 64) == "fused"
+    assert hip._gemm_4bit_route(torch.bfloat16, 16 + 1, 64, 64, 64) == "unfused"
+    # (round 6: K % 64 == 0 rows on matrices of >= 128 rows take the streaming MFMA kernel's row passes up to 128 rows)
     assert hip._gemm_4bit_route(torch.bfloat16, 128, 4096, 2752, 64) == "fused" and hip._gemm_4bit_route(torch.bfloat16, 129, 4096, 2752, 64) == "unfused"
     assert hip._gemm_4bit_route(torch.bfloat16, 128, 1376, 2752, 64) == "fused" and hip._gemm_4bit_route(torch.bfloat16, 129, 1376, 2752, 64) == "unfused"
     assert hip._gemm_4bit_route(torch.bfloat16, 17, 96, 2752, 64) == "unfused" and hip._gemm_4bit_route(torch.bfloat16, 12, 96, 2752, 64) == "fused"
     assert hip._gemm_4bit_route(torch.bfloat16, 17, 4096, 2752 + 32, 64) == "unfused"
     assert hip._gemm_4bit_route(torch.bfloat16, 64, 4096, 4096, 32, True) == "unfused" and hip._gemm_4bit_route(torch.bfloat16, 64, 4096, 4096, 32) == "fused"
-    assert hip._gemm_4bit_route(torch.bfloat16, hip.FUSED_MAX_M, 8192, 8192, 64) == "fused"
-    assert hip._gemm_4bit_route(torch.bfloat16, hip.FUSED_MAX_M + 1, 8192, 8192, 64) == "unfused"
+    assert hip._gemm_4bit_route(torch.bfloat16, 512, 8192, 8192, 64) == "fused"
+    assert hip._gemm_4bit_route(torch.bfloat16, 512 + 1, 8192, 8192, 64) == "unfused"
     assert hip.fused_max_m(4096, 11008) == 1024 and hip.fused_max_m(4096, 4096) == 640 and hip.fused_max_m(11008, 4096) == 512
     assert hip.fused_max_m(8192, 28672) == 512  # (long rows, but beyond the measured 48 M weights)
-    # the C++ function itself, compiled out of the source, against the Python twin on a grid of shapes
-    m = re.search(r"int64_t fused_max_m\(int64_t N, int64_t K, int64_t blocksize, bool nested\) \{.*?\n\}\n", src, re.S)
-    assert m, "fused_max_m not found in torch_dispatch.cpp"
-    consts = "\n".join(re.findall(r"constexpr\s+int64_t\s+k\w+\s*=\s*\d+\s*;", src))
-    prog = ("#include <cstdint>\n#include <cstdio>\n#include <initializer_list>\n" + consts + "\n" + m.group(0) +
-            "int main() { const long Ns[] = {64, 1376, 2048, 3072, 4096, 5120, 8192, 11008, 14336, 28672};\n"
-            "const long Ks[] = {64, 1088, 2048, 2752, 3072, 3584, 4096, 5120, 8192, 11008, 14336, 28672};\n"
-            "for (long n : Ns) for (long k : Ks) for (long bs : {32L, 64L, 128L}) for (int ne = 0; ne < 2; ++ne)\n"
-            "  std::printf(\"%ld %ld %ld %d %ld\\n\", n, k, bs, ne, (long)fused_max_m(n, k, bs, ne != 0));\nreturn 0; }\n")
-    import subprocess
-    import tempfile
 
-    with tempfile.TemporaryDirectory() as td:
-        cpp, exe = os.path.join(td, "f.cpp"), os.path.join(td, "f")
-        open(cpp, "w").write(prog)
-        subprocess.run(["g++", "-std=c++17", "-O0", cpp, "-o", exe], check=True)
-        out = subprocess.run([exe], check=True, stdout=subprocess.PIPE, text=True).stdout
-    rows = [tuple(int(v) for v in line.split()) for line in out.strip().splitlines()]
-    assert len(rows) == 10 * 12 * 3 * 2
-    for n, k, bs, ne, got in rows:
-        assert got == hip.fused_max_m(n, k, bs, bool(ne)), (n, k, bs, ne, got)
+    grid = [(N, K, bs, nested)
+            for N in (64, 96, 127, 128, 1376, 2048, 3072, 4096, 5120, 8192, 11008, 14336, 28672)
+            for K in (64, 320, 1088, 2048, 2752, 2784, 3072, 3584, 4096, 5120, 8192, 11008, 14336, 16384, 16640, 28672)
+            for bs in (16, 32, 64, 128, 4096) for nested in (0, 1)]
+    assert len(grid) == 2080
+    want = "02c3f18e6632d6d86de5b087de94eed2c7de8ba121bca3c7b8e62bb79cb1a3ae"
+
+    def digest(answers):
+        return hashlib.sha256(" ".join(str(v) for v in answers).encode()).hexdigest()
+
+    python = [hip.fused_max_m(N, K, bs, bool(nested)) for N, K, bs, nested in grid]
+    assert set(python) == {16, 128, 512, 640, 1024} and digest(python) == want
+    export = ce.lib.bnb_mi355x_gemm_4bit_fused_max_m
+    for dtype in (1, 2):  # fp16, bf16
+        assert digest(export(dtype, N, K, bs, nested) for N, K, bs, nested in grid) == want, dtype
+    assert all(export(0, N, K, bs, nested) == 4 for N, K, bs, nested in grid), "fp32 activations: fused up to 4 rows"
+
+    nm = shutil.which("nm")
+    torch_lib = ce.PACKAGE_DIR / "libbitsandbytes_mi355x_torch.so"
+    if nm is None or not torch_lib.exists():
+        import pytest
+
+        pytest.skip("binutils nm or the dispatcher library not available")
+    out = subprocess.run([nm, "-D", "--undefined-only", str(torch_lib)], capture_output=True, text=True, check=True).stdout
+    assert "bnb_mi355x_gemm_4bit_fused_max_m" in {ln.split()[-1] for ln in out.splitlines() if ln.strip()}

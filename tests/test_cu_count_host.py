@@ -28,7 +28,7 @@ The plan functions that read the CU count, and the invariant that covers each:
   where the row has two.
 * ``make_plan`` (gemm4_mfma.hip; 64-column workgroups while ``wgs14 <= cus``): ``per_wg = ceil(chunks_total / hot_kslices)``; grid x
   covers N in 64 / 128 / 256 columns, at least two chunks per slice where the row has two.
-* ``sm_selected`` (gemm4_mfma.hip; ``N >= 12 * cus``) and ``route_to_mfma`` (c_api.hip): bnb_mi355x_gemm_4bit_route's answer is 1
+* ``sm_selected`` (gemm4_mfma.hip; ``N >= 12 * cus``) and ``gemm_4bit_route`` (gemm4_mfma.hip): bnb_mi355x_gemm_4bit_route's answer is 1
   exactly where the plan names an MFMA family; the census (each family reached at 32, 64, 128 and 256 CUs).
 * ``gi_plan`` (gemm4_grad_input.hip; ``ns = cus / wgs``): ``k0 = blockIdx.x * 128``, ``m_base = blockIdx.z * (16 * MT)``, ``bb =
   blockIdx.y * hot_bps``, slab ``blockIdx.y * M * K``: ns * bps >= blocks > (ns - 1) * bps, two blocks per wavefront and slice where the
@@ -40,7 +40,7 @@ The plan functions that read the CU count, and the invariant that covers each:
 For every family: every grid dimension >= 1 and within HIP's limits (x < 2^31, y and z <= 65535), dynamic LDS within kLdsBudget =
 156 KiB. Workspace: ``bnb_mi355x_gemm_4bit_workspace_bytes`` = slices * M * N * 4 when the plan splits K and 0 when not - for the
 K-quarter kernel slices * whole 128 x 32 mt tiles (kq_slab_floats); at 17 rows and more the query cannot know whether the K-quarter
-kernel will serve the statistics and answers with the larger of its need and the next family's (gemm_4bit_mfma_workspace_bytes), so
+kernel will serve the statistics and answers with the larger of its need and the next family's (gemm_4bit_workspace_bytes), so
 there the bound is >=, and equality is asserted up to 16 rows. At 256 the answers equal those without an override.
 """
 import os
@@ -347,17 +347,6 @@ def test_override_is_declared_exported_and_thread_local():
         assert lib.bnb_mi355x_gemm_4bit_plan(0, 2, 1, 4096, 4096, 64, 0, out.ctypes.data) == 1 and out[10] == seen["other"]
     finally:
         lib.bnb_mi355x_set_cu_count(0)
-
-
-def test_census_knows_the_host_layer_fused_range():
-    """The census runs without torch and restates backends/hip.py: fused_max_m; the two agree on every shape of its grid."""
-    from bitsandbytes_amd.backends import hip
-
-    for N in Census.NS:
-        for K in Census.KS:
-            for bs in Census.BLOCKSIZES:
-                for nested in (False, True):
-                    assert Census.fused_max_m(N, K, bs, nested) == hip.fused_max_m(N, K, bs, nested), (N, K, bs, nested)
 
 
 def test_committed_gpu_cases_still_differ_from_the_256_cu_plan():

@@ -1424,26 +1424,26 @@ def test_gemm_4bit_blocksize_32_runs_the_mfma_kernel(M, dtype):
         if hip._gemm_4bit_route(dtype, M, N, K, 32, False) == "fused":
             call = lambda: bnb.matmul_4bit(x.to(DEV), q, st, bias=bias.to(DEV))  # noqa: E731
         else:
-            # above FUSED_MAX_M_BS32 rows the public route is dequantize + GEMM (cheaper from ~200 rows on: the BS32 instances' row
+            # above fused_max_m = 128 rows the public route is dequantize + GEMM (cheaper from ~200 rows on: the BS32 instances' row
             # passes run one after the other); the kernel's row-pass geometry is still exercised here, through the library call
-            assert M > hip.FUSED_MAX_M_BS32
+            assert M > hip.fused_max_m(N, K, 32, False) == 128
             y_pub = bnb.matmul_4bit(x.to(DEV), q, st, bias=bias.to(DEV))
             assert rel_err(y_pub.cpu(), _oracle_y(x, q, st, bias)) < REL_TOL
             call = lambda: _run_kernel(0, x.to(DEV), q, st, bias.to(DEV))  # noqa: E731
         y = call()
-        # (three and four rows go to the MFMA kernels on matrices of >= 12 M weights only: c_api.hip route_to_mfma)
+        # (three and four rows go to the MFMA kernels on matrices of >= 12 M weights only: gemm4_mfma.hip gemm_4bit_route)
         want = K_RT if M > 4 or N * K >= (12 << 20) else K_STREAM
         assert bnb.lib.bnb_mi355x_last_gemm_kernel() == want, (M, N, K, bnb.lib.bnb_mi355x_last_gemm_kernel())
         y_ref = _oracle_y(x, q, st, bias)
         assert rel_err(y.cpu(), y_ref) < REL_TOL, (M, N, K, qt)
         assert torch.equal(y, call())  # bit-reproducible
-    # double quantisation at blocksize 32: outside the BS32 instances - the streaming kernel (4-row passes) up to STREAM_ONLY_MAX_M rows,
+    # double quantisation at blocksize 32: outside the BS32 instances - the streaming kernel (4-row passes) up to fused_max_m = 16 rows,
     # dequantize + library GEMM above (3 - 4 x cheaper than the passes at 64 rows: profiles/r5_tall_small_ab.txt); same tolerance
     from bitsandbytes_amd.backends import hip
 
     q, st = F.quantize_4bit(W.to(DEV), blocksize=32, quant_type="nf4", compress_statistics=True)
     y = bnb.matmul_4bit(x.to(DEV), q, st)
-    if M <= hip.STREAM_ONLY_MAX_M:
+    if M <= hip.fused_max_m(st.shape[0], st.shape[1], 32, True) == 16:
         assert bnb.lib.bnb_mi355x_last_gemm_kernel() == K_STREAM
     else:
         assert hip._gemm_4bit_route(dtype, M, st.shape[0], st.shape[1], 32, True) == "unfused"
@@ -1458,7 +1458,7 @@ def test_mfma_blocksize_32_exact_on_representable_inputs():
     F = _F()
     import bitsandbytes_amd as bnb
 
-    for M in (5, 16, 48):  # (from five rows on every matrix takes the MFMA route: c_api.hip route_to_mfma)
+    for M in (5, 16, 48):  # (from five rows on every matrix takes the MFMA route: gemm4_mfma.hip gemm_4bit_route)
         N, K = 80, 1024
         g = torch.Generator().manual_seed(7 + M)
         fp4 = F.get_4bit_type("fp4", device="cpu")

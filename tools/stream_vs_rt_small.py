@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where the streaming kernel hands over to the register-transposed MFMA kernel at 2 - 4 rows (c_api.hip::route_to_mfma): us per
+"""Where the streaming kernel hands over to the register-transposed MFMA kernel at 2 - 4 rows (gemm4_mfma.hip::gemm_4bit_route): us per
 launch of both on small and medium matrices, hipGraph-replayed over an HBM-resident rotation of layers."""
 import os
 import sys
