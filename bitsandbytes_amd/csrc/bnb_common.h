@@ -331,6 +331,34 @@ template <int C> __device__ __forceinline__ void wave_sum_n(float (&v)[C]) {
     }
 }
 
+// wave_sum_n with the four rows combined in the vector unit: the same four row steps, then two more DPP adds instead of
+// four v_readlane and three adds on SGPR values (a VALU instruction takes one SGPR operand: the compiler adds moves).
+//   row_bcast:15, row mask 0xA: lane 15 of row 0 / 2 into every lane of row 1 / 3 -> row 1 = r1 + r0, row 3 = r3 + r2
+//   row_bcast:31, row mask 0xC: lane 31 into every lane of rows 2 and 3          -> row 3 = (r3 + r2) + (r1 + r0)
+// The association is wave_sum_n's, (r0 + r1) + (r2 + r3), and fp32 addition is commutative: the same bits. The sum is valid
+// in LANE 63 ONLY (rows 0 - 2 hold partial sums). Needs the full wave active. Spelled in asm: the rows that the mask leaves
+// out keep the destination, which the builtin can only express through a copy; written by hand, the DPP read of a VGPR that
+// the VALU has just written needs its two wait states by hand as well (s_nop 1).
+template <int C> __device__ __forceinline__ void wave_sum_n_lane63(float (&v)[C]) {
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+        v[c] = dpp_add<0xB1>(v[c]);
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+        v[c] = dpp_add<0x4E>(v[c]);
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+        v[c] = dpp_add<0x141>(v[c]);
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+        v[c] = dpp_add<0x140>(v[c]);
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+        asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\ts_nop 1\n\t"
+            "v_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
+            : "+v"(v[c]));
+}
+
 // CU-count override (bnb_mi355x_set_cu_count: tests and tools - every setting computes correct results). A knob like the ones above:
 // thread-local, 0 = ask the device. The launch plans of the calling thread are then made for a device of that many compute units -
 // what a partitioned MI355X presents (DPX / QPX / CPX: 128 / 64 / 32) - whatever device runs them.

@@ -57,7 +57,8 @@ enum StreamFlags : int {
     kLateArgs = 256, // sweep-only: the epilogue's out / bias pointers loaded where they are used (the form up to round 6; A/B runs)
     kGated = 512,    // rows are (gate, up) pairs of ONE interleaved [2F, K] matrix: out[m, i] = silu(row 2 i) * (row 2 i + 1), [M, F]
     kLora = 1024,    // LoRA adapter term as the epilogue: out[m, n] = T((acc + bias[n]) + scaling * sum_j t[m, j] * B_l[n, j]) - see lora_dot
-    kLoraIds = 2048  // (with kLora) mixed-adapter batch: row m takes B_l and scaling from adapter ids[m] of a stack; a row without one is plain
+    kLoraIds = 2048, // (with kLora) mixed-adapter batch: row m takes B_l and scaling from adapter ids[m] of a stack; a row without one is plain
+    kReadlaneSum = 4096 // sweep-only: the MB = 1 row sum combined through v_readlane / SGPRs and stored by lane 0 (the form up to this flag; A/B runs)
 };
 
 // One weight matrix of a launch.
@@ -212,12 +213,12 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
     // the host keeps the first row and the row count of every workgroup even (make_geometry, pairs), so a (gate, up) pair never
     // straddles two workgroups.
     constexpr bool GATED = (FLAGS & kGated) != 0;
-    static_assert(!GATED || (!PEER && !GROUPED && !NESTED && !CODEPTR && !(FLAGS & kLateArgs) && TypeInfo<T>::bytes == 2),
+    static_assert(!GATED || (!PEER && !GROUPED && !NESTED && !CODEPTR && !(FLAGS & (kLateArgs | kReadlaneSum)) && TypeInfo<T>::bytes == 2),
                   "the gated form: one matrix, fp32 absmax, literal table, 16-bit activations");
     static_assert(!PEER || (MB == 1 && !MULTI && !GROUPED && WAVES == 16), "the peer-chain form is the M = 1, single-phase kernel");
     // LoRA epilogue (bnb_mi355x_gemm_4bit_lora): everything in front of the epilogue is the plain kernel's, fp32 absmax or nested statistics
     constexpr bool LORA = (FLAGS & kLora) != 0;
-    static_assert(!LORA || (!PEER && !GROUPED && !GATED && !CODEPTR && !(FLAGS & kLateArgs) && TypeInfo<T>::bytes == 2),
+    static_assert(!LORA || (!PEER && !GROUPED && !GATED && !CODEPTR && !(FLAGS & (kLateArgs | kReadlaneSum)) && TypeInfo<T>::bytes == 2),
                   "the LoRA form: one matrix, literal table, 16-bit activations");
     // mixed-adapter form (bnb_mi355x_gemm_4bit_lora_ids): a compile-time variant of the LoRA epilogue - the uniform instances' code is untouched
     constexpr bool LORA_IDS = (FLAGS & kLoraIds) != 0;
@@ -232,6 +233,9 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
                   "the exact-geometry form is the M = 1, single-phase kernel for 16-bit activations");
     // the epilogue's pointers are requested in the prologue (see there); kLateArgs keeps the old form for A/B runs
     constexpr bool EARLY_ARGS = !GROUPED && !(FLAGS & kLateArgs);
+    // one activation row: the wave reduction of an item is finished in the vector unit and lane 63 stores the partial
+    // (wave_sum_n_lane63); kReadlaneSum keeps the readlane form for A/B runs, MB > 1 keeps it for good
+    constexpr bool LANE_SUM = MB == 1 && !(FLAGS & kReadlaneSum);
     constexpr int THREADS = WAVES * 64;
     constexpr int TB = TypeInfo<T>::bytes;
     constexpr int CH = 2 * TB;  // 16-byte chunks of activations per lane and segment (= 1-KiB DMA pieces per segment)
@@ -544,11 +548,14 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(WAVE
                 v[u * MB + m] = PRESCALE ? sum : sum * scale_u[u];
             }
         }
-        wave_sum_n<IL * MB>(v);
+        if constexpr (LANE_SUM)
+            wave_sum_n_lane63<IL * MB>(v);
+        else
+            wave_sum_n<IL * MB>(v);
 #pragma unroll
         for (int u = 0; u < IL; ++u) {
             const int rl = g + (i0 + u) * G;
-            if (lane == 0 && (EXACT || rl < rl_end)) {
+            if (lane == (LANE_SUM ? 63 : 0) && (EXACT || rl < rl_end)) {
 #pragma unroll
                 for (int m = 0; m < MB; ++m)
                     part[(rl * S + seg) * MB + m] = v[u * MB + m];
@@ -1149,7 +1156,10 @@ template <typename T, int MB, int WAVES, int NS, int FLAGS> constexpr bool has_e
 // stream tuning knob `nt`, values above 1 (A/B of the fixed-cost levers, tools/stream_fixed_cost_ab.py): 2 = the general instance where
 // the exact one would be selected, 3 = the general instance with the epilogue's pointers loaded late (bf16, NF4 fp32-absmax and
 // FP4 nested only: the two sweep instances)
-constexpr int kTuneGeneral = 2, kTuneLateArgs = 3;
+// 4 = the readlane row sum (kReadlaneSum) on the instance the launch would select anyway, exact or general, 5 = on the general
+// instance where the exact one would run (the same two sweep configurations; A/B of the lever: tools/stream_post_barrier_ab.py)
+constexpr int kTuneGeneral = 2, kTuneLateArgs = 3, kTuneReadlane = 4, kTuneReadlaneGeneral = 5;
+constexpr bool knob_forces_general(int knob) { return knob == kTuneGeneral || knob == kTuneLateArgs || knob == kTuneReadlaneGeneral; }
 
 template <typename T, int MB, int WAVES, int NS, int FLAGS> void launch_one(const StreamArgs& a, hipStream_t stream) {
     const Geometry ge = tuned_geometry(a.rows_total, a.K, MB, WAVES, TypeInfo<T>::bytes, (FLAGS & kGrouped) != 0, (FLAGS & kGated) != 0);
@@ -1175,9 +1185,17 @@ template <typename T, int MB, int WAVES, int NS, int FLAGS> void launch_one(cons
         if constexpr (kLateTwin) {
             if (knob == kTuneLateArgs && ge.P == 1)
                 return go(gemv4_stream_kernel<T, MB, WAVES, NS, FLAGS | kLateArgs>);
+            // (the readlane twins live on the same two configurations; nested statistics have no exact instance)
+            if ((knob == kTuneReadlane || knob == kTuneReadlaneGeneral) && ge.P == 1) {
+                if constexpr (has_exact_twin<T, MB, WAVES, NS, FLAGS>()) {
+                    if (knob == kTuneReadlane && exact_geometry(ge, a.M, a.rows_total, a.K, NS))
+                        return go(gemv4_stream_kernel<T, MB, WAVES, NS, FLAGS | kExact | kReadlaneSum>);
+                }
+                return go(gemv4_stream_kernel<T, MB, WAVES, NS, FLAGS | kReadlaneSum>);
+            }
         }
         if constexpr (has_exact_twin<T, MB, WAVES, NS, FLAGS>()) {
-            if (knob != kTuneGeneral && knob != kTuneLateArgs && exact_geometry(ge, a.M, a.rows_total, a.K, NS))
+            if (!knob_forces_general(knob) && exact_geometry(ge, a.M, a.rows_total, a.K, NS))
                 return go(gemv4_stream_kernel<T, MB, WAVES, NS, FLAGS | kExact>);
         }
     }
@@ -1588,8 +1606,7 @@ void peer_chain_read(void* const* bufs, void* epoch_word, int world, int rank, i
 bool gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, bool nested) {
     const int knob = g_tune.nt.load(std::memory_order_relaxed);
     if (nested || (dtype != 1 && dtype != 2) || M != 1 || N <= 0 || K <= 0 || K % 32 != 0 || blocksize < 32 || !is_pow2(blocksize) ||
-        g_tune.waves.load(std::memory_order_relaxed) == 8 || g_tune.ns.load(std::memory_order_relaxed) != 0 || knob == 0 || knob == kTuneGeneral ||
-        knob == kTuneLateArgs)
+        g_tune.waves.load(std::memory_order_relaxed) == 8 || g_tune.ns.load(std::memory_order_relaxed) != 0 || knob == 0 || knob_forces_general(knob))
         return false;
     const Geometry ge = make_geometry(N, K, 1, 16, 2, false, g_tune.sw.load(std::memory_order_relaxed), g_tune.rows.load(std::memory_order_relaxed));
     return exact_geometry(ge, M, N, K, kRing);

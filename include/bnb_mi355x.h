@@ -365,7 +365,9 @@ void bnb_mi355x_set_stream_tuning(int ring_depth, int segments, int rows_per_wor
  * 1 = the exact-geometry instance (M = 1, 16-bit activations, fp32 absmax (nested = 0), K = 4096, rows that divide evenly over
  * workgroups and row groups: csrc/gemv4_stream.hip exact_geometry), 0 = the general one. Host logic only (the launcher's own
  * geometry and rule, no launch). Stream tuning `nontemporal` = 2 forces the general instance, 3 the general instance with the
- * epilogue's pointers loaded late (A/B runs: tools/stream_fixed_cost_ab.py). */
+ * epilogue's pointers loaded late (A/B runs: tools/stream_fixed_cost_ab.py); 4 keeps the selection and runs the instance with the
+ * row sum combined through v_readlane (the form before the in-lane sum), 5 does so on the general instance (A/B runs:
+ * tools/stream_post_barrier_ab.py; bf16, NF4 fp32 absmax and FP4 nested only). */
 int bnb_mi355x_gemv_4bit_stream_exact(int dtype, int M, int N, int K, int blocksize, int nested);
 
 /* Test and tool infrastructure: the launch geometry of a streaming-kernel call (csrc/gemv4_stream.hip), without the call. Host logic
