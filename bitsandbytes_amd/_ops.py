@@ -660,3 +660,41 @@ def _(A, B, shapeB: Sequence[int], absmax, blocksize: int, quant_type: str, lora
     N, _, _, _ = _check_gemm_4bit_lora_ids(A, B, shapeB, absmax, blocksize, quant_type, lora_t, lora_b, scalings, ids, bias, absmax_8bit, absmax_code,
                                            absmax_offset)
     return torch.empty((*A.shape[:-1], N), dtype=A.dtype, device=A.device)
+
+
+# ---------------------------------------------------------------------------------------------- moe_topk
+# Not a reference op: the scoring and top-k half of a mixture-of-experts router, ONE launch (csrc/moe_route.hip) between the router
+# matmul and gemm_4bit_experts / gemm_4bit_experts_ffn. logits [*, E], 16/32-bit float, contiguous; all arithmetic in fp32:
+#   p = softmax(logits) or sigmoid(logits) (scoring "softmax" / "sigmoid");  key = p (+ select_bias: fp32 [E], selection only)
+#   ids [*, top_k] int32: the experts of largest key, best first, the lower index on ties, NaN keys last - always distinct and in [0, E)
+#   weights [*, top_k] fp32: p[ids], divided by their sum in slot order if `renormalize` (no epsilon), then times `scale`
+# Served for 1 <= E <= 1024 and 1 <= top_k <= min(E, 16) (backends/hip.py: moe_topk_supported); anything else raises. Nothing is read
+# on the host. Inference only: no autograd formula.
+torch.library.define("bitsandbytes_amd::moe_topk",
+                     "(Tensor logits, int top_k, str scoring, bool renormalize, float scale, Tensor? select_bias=None) -> (Tensor, Tensor)")
+
+MOE_SCORING_CODES = {"softmax": 0, "sigmoid": 1}
+
+
+def _check_moe_topk(logits, top_k, scoring, select_bias):
+    """Argument checks shared by the fake kernel and the device kernel; returns (rows, E)."""
+    torch._check(scoring in MOE_SCORING_CODES, lambda: f"scoring must be 'softmax' or 'sigmoid', got {scoring!r}")
+    torch._check(logits.dtype in _FLOAT_DTYPES, lambda: f"logits must be a 16/32-bit float tensor, got {logits.dtype}")
+    torch._check(logits.dim() >= 1 and logits.shape[-1] >= 1, lambda: f"logits must be [*, E] with E >= 1, got {tuple(logits.shape)}")
+    E = int(logits.shape[-1])
+    torch._check(1 <= int(top_k) <= E, lambda: f"top_k must be in [1, E] = [1, {E}], got {top_k}")
+    torch._check(logits.is_contiguous(), lambda: "logits must be contiguous")
+    if select_bias is not None:
+        torch._check(select_bias.dtype == torch.float32 and tuple(select_bias.shape) == (E,) and select_bias.device == logits.device
+                     and select_bias.is_contiguous(),
+                     lambda: f"select_bias must be a contiguous float32 tensor [E] = [{E}] on the logits' device, got {select_bias.dtype} "
+                             f"{tuple(select_bias.shape)}")
+    return logits.numel() // E, E
+
+
+@register_fake("bitsandbytes_amd::moe_topk")
+def _(logits, top_k: int, scoring: str, renormalize: bool, scale: float, select_bias=None):
+    _check_moe_topk(logits, top_k, scoring, select_bias)
+    lead = tuple(logits.shape[:-1])
+    return (torch.empty((*lead, int(top_k)), dtype=torch.int32, device=logits.device),
+            torch.empty((*lead, int(top_k)), dtype=torch.float32, device=logits.device))

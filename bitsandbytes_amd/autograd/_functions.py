@@ -16,6 +16,7 @@ from warnings import warn
 import torch
 
 from .. import functional as F
+from .._ops import MOE_SCORING_CODES
 
 
 def _is_compiling() -> bool:
@@ -502,6 +503,84 @@ def lora_shrink_ids(x: torch.Tensor, lora_A: torch.Tensor, adapter_ids: torch.Te
     if splits is None:
         return t
     return tuple(p.contiguous() for p in t.split(splits, dim=-1))
+
+
+def _moe_topk_composition(logits, top_k, scoring, renormalize, scale, select_bias):
+    """:func:`moe_topk` from torch operations, with the kernel's selection rule: fp32 scores, the lower index on ties, NaN keys behind
+    every other key in ascending index (two stable sorts - ``torch.topk`` promises no order among equal keys and puts NaN first)."""
+    p = torch.softmax(logits.float(), dim=-1) if scoring == "softmax" else torch.sigmoid(logits.float())
+    key = p if select_bias is None else p + select_bias.to(device=p.device, dtype=torch.float32)
+    nan = torch.isnan(key)
+    order = torch.sort(torch.where(nan, torch.full_like(key, float("-inf")), key), dim=-1, descending=True, stable=True).indices
+    last = torch.sort(nan.gather(-1, order).to(torch.uint8), dim=-1, stable=True).indices
+    ids = order.gather(-1, last)[..., :top_k]
+    w = p.gather(-1, ids)
+    if renormalize:
+        w = w / w.sum(dim=-1, keepdim=True)
+    return ids.to(torch.int32), w * float(scale)
+
+
+def moe_topk(logits: torch.Tensor, top_k: int, scoring: str = "softmax", renormalize: bool = True, scale: float = 1.0,
+             select_bias: Optional[torch.Tensor] = None):
+    """The scoring and top-k half of a mixture-of-experts router: ``(ids, weights)`` from router ``logits`` ``[*, E]``, as ONE launch.
+    ``ids``: ``[*, top_k]`` int32, ``weights``: ``[*, top_k]`` fp32 - what :func:`moe_ffn_4bit` and :func:`matmul_4bit_experts` take as
+    ``expert_ids`` and ``routing_weights`` / ``row_scale``, with no conversion in between.
+
+    ``p = softmax(logits)`` (Mixtral, Qwen) or ``sigmoid(logits)`` (DeepSeek-V3, GLM) in fp32; the selection key is ``p``, or
+    ``p + select_bias`` (``[E]``, ``e_score_correction_bias``: it takes part in the selection only). Slot 0 holds the best expert; on
+    equal keys the lower index goes first; a NaN key goes behind every other key, so the ids of a row are always distinct and in
+    ``[0, E)``. ``weights = p[ids]``, divided by their sum if ``renormalize`` (no epsilon: a zero sum gives inf or NaN, as IEEE division
+    does), then times ``scale``. A row's result depends on that row alone.
+
+    The launch serves device tensors with ``E <= 1024`` and ``top_k <= 16`` (``backends.hip.moe_topk_supported``). Every other call -
+    CPU tensors, more experts or slots, compilation - composes softmax / sigmoid, two stable sorts and a gather: the same ids wherever
+    the keys are not within rounding of each other, weights equal to fp32 rounding. Neither path reads data on the host, so both can
+    be captured in a graph. Group-limited routing (``n_group`` / ``topk_group``) is not served. Inference only."""
+    if scoring not in MOE_SCORING_CODES:
+        raise ValueError(f"moe_topk: scoring must be 'softmax' or 'sigmoid', got {scoring!r}")
+    if logits.dim() < 1 or logits.shape[-1] < 1 or not logits.is_floating_point():
+        raise ValueError(f"moe_topk: logits must be a float tensor [*, E] with E >= 1, got {logits.dtype} {tuple(logits.shape)}")
+    E, top_k = int(logits.shape[-1]), int(top_k)
+    if not 1 <= top_k <= E:
+        raise ValueError(f"moe_topk: top_k must be in [1, E] = [1, {E}], got {top_k}")
+    if select_bias is not None and tuple(select_bias.shape) != (E,):
+        raise ValueError(f"moe_topk: select_bias must be [E] = [{E}], got {tuple(select_bias.shape)}")
+    if torch.is_grad_enabled() and (logits.requires_grad or (select_bias is not None and select_bias.requires_grad)):
+        raise RuntimeError("moe_topk is inference only (no autograd formula): call it under torch.no_grad() or with detached inputs")
+    rows = logits.numel() // E
+    if logits.device.type == "cuda" and rows > 0 and not _is_compiling() and (select_bias is None or select_bias.device == logits.device):
+        from ..backends import hip
+
+        if hip.moe_topk_supported(logits.dtype, rows, E, top_k):
+            sb = None if select_bias is None else select_bias.to(torch.float32).contiguous()
+            return torch.ops.bitsandbytes_amd.moe_topk.default(logits.contiguous(), top_k, scoring, bool(renormalize), float(scale), sb)
+    return _moe_topk_composition(logits, top_k, scoring, bool(renormalize), scale, select_bias)
+
+
+def moe_route(x: torch.Tensor, router_weight: torch.Tensor, top_k: int, *, bias: Optional[torch.Tensor] = None, scoring: str = "softmax",
+              renormalize: bool = True, scale: float = 1.0, select_bias: Optional[torch.Tensor] = None, return_logits: bool = False):
+    """A whole mixture-of-experts router, ``(ids, weights) = moe_topk(x @ router_weight.T (+ bias), ...)``, in TWO launches where both
+    halves are served: the logits come from :func:`lora_shrink` - ``x @ Wr^T`` with ``[E, K]`` weights is exactly its shape class, and
+    it falls back to ``F.linear`` by its own measured predicate -, or from ``F.linear`` when the gate has a logit ``bias``; then
+    :func:`moe_topk`. ``x``: ``[*, K]``; ``router_weight``: ``[E, K]``, an ``nn.Linear`` gate's weight as stored. Returns ``(ids, weights)``
+    ``[*, top_k]``, and the logits ``[*, E]`` behind them with ``return_logits``. With :func:`moe_ffn_4bit` behind it a decode step's
+    MoE block is four launches and one slot sum. Inference only.
+
+    Dtypes: the two-launch form needs ``router_weight`` in ``x``'s 16-bit dtype. A gate kept in another dtype (fp32 under bf16
+    activations, as several MoE models do) is never rounded: ``x`` - the small operand - is cast to the weight's dtype, one extra
+    launch, and ``F.linear`` computes the logits in that dtype. ``select_bias`` should be fp32: another dtype is cast on every call."""
+    if router_weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != router_weight.shape[1]:
+        raise ValueError(f"moe_route: router_weight must be [E, K] and x [*, K], got {tuple(router_weight.shape)} and {tuple(x.shape)}")
+    if bias is not None and tuple(bias.shape) != (router_weight.shape[0],):
+        raise ValueError(f"moe_route: bias must be [E] = [{router_weight.shape[0]}], got {tuple(bias.shape)}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, router_weight, bias)):
+        raise RuntimeError("moe_route is inference only (no autograd formula): call it under torch.no_grad() or with detached inputs")
+    if bias is None and router_weight.dtype == x.dtype:
+        logits = lora_shrink(x, router_weight)
+    else:
+        logits = torch.nn.functional.linear(x.to(router_weight.dtype), router_weight, None if bias is None else bias.to(router_weight.dtype))
+    ids, weights = moe_topk(logits, top_k, scoring=scoring, renormalize=renormalize, scale=scale, select_bias=select_bias)
+    return (ids, weights, logits) if return_logits else (ids, weights)
 
 
 def matmul_4bit_grouped(A: torch.Tensor, weights, quant_states, biases=None, outs=None):

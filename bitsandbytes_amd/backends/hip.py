@@ -21,9 +21,9 @@ from warnings import warn
 
 import torch
 
-from .._ops import (GATED_CODES, _check_gemm_4bit_experts, _check_gemm_4bit_experts_ffn, _check_gemm_4bit_gated, _check_gemm_4bit_lora,
-                     _check_gemm_4bit_lora_ids,
-                     _check_lora_shrink, _check_lora_shrink_ids, register_kernel)
+from .._ops import (GATED_CODES, MOE_SCORING_CODES, _check_gemm_4bit_experts, _check_gemm_4bit_experts_ffn, _check_gemm_4bit_gated,
+                     _check_gemm_4bit_lora, _check_gemm_4bit_lora_ids,
+                     _check_lora_shrink, _check_lora_shrink_ids, _check_moe_topk, register_kernel)
 from ..cextension import lib
 
 _DT_NAME = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}
@@ -724,6 +724,38 @@ def _(x, lora_a, ids, splits: Optional[Sequence[int]] = None):
         lib.bnb_mi355x_lora_shrink_ids(_DT_CODE[x.dtype], x.data_ptr(), lora_a.data_ptr(), ids.data_ptr(), ids.element_size(), out.data_ptr(),
                                        M, A_n, R, K, table, n, _stream(x))
     return out
+
+
+# ------------------------------------------------------------------------------------------ moe_topk
+def moe_topk_supported(dtype: torch.dtype, rows: int, experts: int, top_k: int) -> bool:
+    """Whether ``bitsandbytes_amd::moe_topk`` has a kernel for ``rows`` rows of ``experts`` logits and ``top_k`` slots: 16/32-bit float
+    logits, ``1 <= experts <= 1024``, ``1 <= top_k <= min(experts, 16)``, ``rows >= 1``, minus the classes the measurements exclude
+    (pure host logic of the library; no device is queried)."""
+    if dtype not in _DT_CODE or max(rows, experts, top_k) >= 2**31 or min(rows, experts, top_k) < 0:
+        return False
+    return bool(lib.bnb_mi355x_moe_topk_supported(_DT_CODE[dtype], rows, experts, top_k))
+
+
+@register_kernel("bitsandbytes_amd::moe_topk", "cuda")
+def _(logits, top_k: int, scoring: str, renormalize: bool, scale: float, select_bias=None):
+    """One launch of csrc/moe_route.hip; nothing is read on the host."""
+    from ..cextension import MoeTopkArgs
+
+    rows, E = _check_moe_topk(logits, top_k, scoring, select_bias)
+    lead = tuple(logits.shape[:-1])
+    ids = torch.empty((*lead, int(top_k)), dtype=torch.int32, device=logits.device)
+    weights = torch.empty((*lead, int(top_k)), dtype=torch.float32, device=logits.device)
+    if rows == 0:
+        return ids, weights
+    if not moe_topk_supported(logits.dtype, rows, E, int(top_k)):
+        raise ValueError(f"moe_topk: no kernel for rows={rows}, experts={E}, top_k={top_k}, dtype={logits.dtype} (1 <= experts <= 1024, "
+                         "1 <= top_k <= min(experts, 16)); compose softmax / sigmoid and a stable sort - bitsandbytes_amd.moe_topk does")
+    with _device_of(logits):
+        args = MoeTopkArgs(ct.sizeof(MoeTopkArgs), _DT_CODE[logits.dtype], MOE_SCORING_CODES[scoring], 1 if renormalize else 0, rows, E,
+                           int(top_k), float(scale), logits.data_ptr(), _ptr(select_bias), ids.data_ptr(), weights.data_ptr(), _stream(logits))
+        if lib.bnb_mi355x_moe_topk(ct.byref(args)) != 0:
+            raise RuntimeError(f"moe_topk: the library refused rows={rows}, experts={E}, top_k={top_k}, dtype={logits.dtype}")
+    return ids, weights
 
 
 def gemm_4bit_grouped(A: torch.Tensor, mats, blocksize: int, quant_type: str, outs=None):

@@ -44,6 +44,16 @@ _VOID_P = ct.c_void_p
 _I32 = ct.c_int32
 
 
+class MoeTopkArgs(ct.Structure):
+    """``bnb_mi355x_moe_topk_args`` of include/bnb_mi355x.h: the argument block of ``bnb_mi355x_moe_topk``. ``struct_bytes`` is
+    ``ctypes.sizeof(MoeTopkArgs)``; the library refuses a block of another size."""
+
+    _fields_ = [("struct_bytes", ct.c_size_t), ("logits_dtype", ct.c_int), ("scoring", ct.c_int), ("renormalize", ct.c_int),
+                ("rows", ct.c_int), ("experts", ct.c_int), ("top_k", ct.c_int), ("scale", ct.c_float),
+                ("logits", ct.c_void_p), ("select_bias", ct.c_void_p), ("ids", ct.c_void_p), ("weights", ct.c_void_p),
+                ("stream", ct.c_void_p)]
+
+
 def _declare(dll: ct.CDLL) -> None:
     def sig(names, argtypes, restype=None):
         for n in names:
@@ -103,6 +113,9 @@ def _declare(dll: ct.CDLL) -> None:
     # (dtype, x, lora_a, ids, index_bytes, t, M, A_n, R, K, splits (host int[n_splits] or NULL), n_splits, stream)
     sig(["bnb_mi355x_lora_shrink_ids"], [_I32] + [_VOID_P] * 3 + [_I32, _VOID_P] + [_I32] * 4 + [_VOID_P, _I32, _VOID_P])
     sig(["bnb_mi355x_lora_shrink_ids_supported"], [_I32] * 5, _I32)  # (dtype, M, A_n, R, K)
+    # (one argument block, passed with ctypes.byref(MoeTopkArgs(...)); non-zero: refused, nothing launched)
+    sig(["bnb_mi355x_moe_topk"], [_VOID_P], _I32)
+    sig(["bnb_mi355x_moe_topk_supported"], [_I32] * 4, _I32)  # (logits_dtype, rows, experts, top_k)
     # (dtype, A, count, B[], absmax[], absmax_8bit[], absmax_code[], absmax_offset[], out[], bias[], N[], M, K, blocksize, quant_type, stream)
     sig(["bnb_mi355x_gemm_4bit_grouped"], [_I32, _VOID_P, _I32] + [_VOID_P] * 8 + [_I32] * 4 + [_VOID_P])
     sig(["bnb_mi355x_gemm_4bit_grouped_route"], [_I32, _I32, _VOID_P, _I32, _I32, _I32], _I32)  # (dtype, count, N[], M, K, blocksize)
@@ -175,6 +188,7 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_gemm_4bit_lora_ids", "bnb_mi355x_gemm_4bit_lora_ids_supported",
        "bnb_mi355x_lora_shrink", "bnb_mi355x_lora_shrink_supported",
        "bnb_mi355x_lora_shrink_ids", "bnb_mi355x_lora_shrink_ids_supported",
+       "bnb_mi355x_moe_topk", "bnb_mi355x_moe_topk_supported",
        "bnb_mi355x_gemm_4bit_grad_input", "bnb_mi355x_gemm_4bit_grad_input_workspace_bytes", "bnb_mi355x_gemm_4bit_grad_input_supported",
        "bnb_mi355x_peer_buffer_bytes", "bnb_mi355x_peer_alloc", "bnb_mi355x_peer_free", "bnb_mi355x_peer_export", "bnb_mi355x_peer_open",
        "bnb_mi355x_peer_close", "bnb_mi355x_peer_allgather", "bnb_mi355x_peer_status",

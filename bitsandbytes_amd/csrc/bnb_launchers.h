@@ -164,6 +164,19 @@ bool lora_shrink_ids_supported(int dtype, int M, int A_n, int R, int K);
 bool lora_shrink_ids(int dtype, const void* x, const void* lora_a, const void* ids, int index_bytes, void* t, int M, int A_n, int R, int K,
                      const int* splits, int n_splits, hipStream_t stream);
 
+// moe_route.hip (the router's scoring + top-k launch; the fields of bnb_mi355x_moe_topk_args, include/bnb_mi355x.h)
+struct MoeTopkCall {
+    int dtype, scoring, renormalize; // logits: 0 fp32, 1 fp16, 2 bf16; 0 softmax, 1 sigmoid
+    int rows, experts, top_k;
+    float scale;
+    const void* logits;       // [rows, experts]
+    const float* select_bias; // [experts] or nullptr
+    int* ids;                 // [rows, top_k]
+    float* weights;           // [rows, top_k]
+};
+bool moe_topk_supported(int dtype, int rows, int experts, int top_k);
+bool moe_topk(const MoeTopkCall& call, hipStream_t stream);
+
 // c_api.hip (g_last_gemm_kernel, defined there as well, is declared in bnb_common.h)
 #ifdef BNB_PROFILING
 extern unsigned long long* g_dbg_buf; // profiling builds only: device buffer for the kernels' s_memtime stamps

@@ -352,6 +352,27 @@ void bnb_mi355x_lora_shrink_ids(int dtype, const void* x, const void* lora_a, co
 }
 int bnb_mi355x_lora_shrink_ids_supported(int dtype, int M, int A_n, int R, int K) { return lora_shrink_ids_supported(dtype, M, A_n, R, K) ? 1 : 0; }
 
+// ------------------------------------------------------------------ MoE router: scoring + top-k (the launch in front of gemm_4bit_experts)
+// Takes an argument block and REFUSES (message, non-zero, nothing launched) instead of ending the process.
+int bnb_mi355x_moe_topk(const bnb_mi355x_moe_topk_args* args) {
+    if (args == nullptr || args->struct_bytes != sizeof(bnb_mi355x_moe_topk_args)) {
+        fprintf(stderr, "bitsandbytes_amd: moe_topk: struct_bytes is %zu, this library's bnb_mi355x_moe_topk_args has %zu\n",
+                args == nullptr ? static_cast<size_t>(0) : args->struct_bytes, sizeof(bnb_mi355x_moe_topk_args));
+        return 1;
+    }
+    const MoeTopkCall call = {args->logits_dtype, args->scoring, args->renormalize != 0 ? 1 : 0, args->rows, args->experts, args->top_k,
+                              args->scale,        args->logits,  args->select_bias,              args->ids,  args->weights};
+    if (!moe_topk(call, S(args->stream))) {
+        fprintf(stderr, "bitsandbytes_amd: moe_topk: no kernel for logits_dtype %d, scoring %d, rows=%d, experts=%d, top_k=%d (fp32 / fp16 / bf16 logits, scoring 0 / 1, rows >= 0, 1 <= experts <= 1024, 1 <= top_k <= min(experts, 16); logits / ids / weights not NULL; every pointer aligned to its element)\n",
+                args->logits_dtype, args->scoring, args->rows, args->experts, args->top_k);
+        return 1;
+    }
+    return 0;
+}
+int bnb_mi355x_moe_topk_supported(int logits_dtype, int rows, int experts, int top_k) {
+    return moe_topk_supported(logits_dtype, rows, experts, top_k) ? 1 : 0;
+}
+
 // ------------------------------------------------------------------ peer chain (the all-gather fused into the gemv launches)
 static uint32_t peer_chain_spin_bound() {
     // a re-fetch is s_sleep 4 (256 cycles) + a system-scope load round trip: ~1 us. BNB_MI355X_PEER_WAIT_POLLS as in peer_gather.hip

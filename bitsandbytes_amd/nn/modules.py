@@ -18,6 +18,7 @@ import torch
 from torch import nn
 
 from .. import functional as F
+from .._ops import MOE_SCORING_CODES
 from ..autograd import matmul_4bit
 from ..functional import QuantState
 
@@ -664,6 +665,55 @@ class LinearNF4(Linear4bit):
                  quant_storage=torch.uint8, device=None):
         super().__init__(input_features, output_features, bias, compute_dtype, compress_statistics, "nf4",
                          quant_storage, device)
+
+
+class MoERouter(nn.Module):
+    """The router (gate) of a mixture-of-experts block: ``forward(x)`` returns ``(ids, weights)``, ``[*, top_k]`` int32 and fp32 on
+    ``x``'s device - what :func:`bitsandbytes_amd.moe_ffn_4bit` takes as ``expert_ids`` and ``routing_weights`` - in two launches where
+    :func:`bitsandbytes_amd.moe_route` is served. ``scoring``: ``"softmax"`` (Mixtral, Qwen) or ``"sigmoid"`` (DeepSeek-V3, GLM);
+    ``renormalize`` / ``scale``: the chosen scores divided by their sum, then times ``scale`` (``routed_scaling_factor``).
+
+    State-dict keys: ``weight`` ``[num_experts, hidden]`` - an ``nn.Linear`` gate's checkpoint loads as it is -, ``bias``
+    ``[num_experts]`` with ``bias=True`` (added to the logits), and ``e_score_correction_bias`` ``[num_experts]`` fp32 with
+    ``select_bias=True`` (added to the scores for the selection only). Inference only: the parameters do not require gradients.
+
+    Dtypes: ``e_score_correction_bias`` STAYS fp32 under ``.to(dtype)`` / ``.half()`` / ``.bfloat16()`` (the kernel reads fp32; a cast
+    would cost its precision and a launch per call) - only its device follows the module. The two-launch form needs ``weight`` in
+    ``x``'s 16-bit dtype; a gate kept in fp32 under 16-bit activations computes its logits in fp32 from ``x`` cast up, through
+    ``F.linear`` (:func:`bitsandbytes_amd.moe_route`)."""
+
+    def __init__(self, hidden: int, num_experts: int, top_k: int, scoring: str = "softmax", renormalize: bool = True, scale: float = 1.0,
+                 bias: bool = False, select_bias: bool = False, device=None, dtype=None):
+        super().__init__()
+        if scoring not in MOE_SCORING_CODES:
+            raise ValueError(f"MoERouter: scoring must be 'softmax' or 'sigmoid', got {scoring!r}")
+        if not 1 <= int(top_k) <= int(num_experts):
+            raise ValueError(f"MoERouter: top_k must be in [1, num_experts] = [1, {num_experts}], got {top_k}")
+        self.hidden, self.num_experts, self.top_k = int(hidden), int(num_experts), int(top_k)
+        self.scoring, self.renormalize, self.scale = scoring, bool(renormalize), float(scale)
+        self.weight = nn.Parameter(torch.empty(self.num_experts, self.hidden, device=device, dtype=dtype), requires_grad=False)
+        nn.init.normal_(self.weight, std=self.hidden ** -0.5)
+        self.register_parameter("bias", nn.Parameter(torch.zeros(self.num_experts, device=device, dtype=dtype), requires_grad=False) if bias else None)
+        self.register_buffer("e_score_correction_bias", torch.zeros(self.num_experts, device=device, dtype=torch.float32) if select_bias else None)
+
+    def _apply(self, fn, recurse=True):
+        kept = self.e_score_correction_bias
+        super()._apply(fn, recurse)
+        if kept is not None and self.e_score_correction_bias.dtype != torch.float32:
+            # a dtype cast: the selection bias keeps its fp32 values and only follows the device
+            self.e_score_correction_bias = kept.to(self.e_score_correction_bias.device)
+        return self
+
+    def forward(self, x: torch.Tensor):
+        from ..autograd import moe_route
+
+        return moe_route(x, self.weight, self.top_k, bias=self.bias, scoring=self.scoring, renormalize=self.renormalize, scale=self.scale,
+                         select_bias=self.e_score_correction_bias)
+
+    def extra_repr(self) -> str:
+        return (f"hidden={self.hidden}, num_experts={self.num_experts}, top_k={self.top_k}, scoring={self.scoring!r}, "
+                f"renormalize={self.renormalize}, scale={self.scale}, bias={self.bias is not None}, "
+                f"select_bias={self.e_score_correction_bias is not None}")
 
 
 class Embedding4bit(nn.Embedding):

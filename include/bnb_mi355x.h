@@ -262,6 +262,47 @@ int bnb_mi355x_lora_shrink_supported(int dtype, int M, int R, int K);
 void bnb_mi355x_lora_shrink_ids(int dtype, const void* x, const void* lora_a, const void* ids, int index_bytes, void* t, int M, int A_n, int R, int K, const int* splits, int n_splits, bnb_stream_t stream);
 int bnb_mi355x_lora_shrink_ids_supported(int dtype, int M, int A_n, int R, int K);
 
+/* MoE router, scoring and top-k: the launch between the router matmul (logits = x * Wr^T, the caller's launch: the shape class of
+ * bnb_mi355x_lora_shrink with R = experts) and bnb_mi355x_gemm_4bit_experts / _ffn, which take ids and weights as written here.
+ * Per row of logits [rows, experts] (row-major, fp32 / fp16 / bf16), all arithmetic in fp32:
+ *     p_j = softmax(l)_j = expf(l_j - max l) / Z          scoring 0; Z summed lane-local over j = lane + 64 i in ascending i, then over
+ *                                                          the 64 lanes by the xor butterfly 32, 16, ... 1
+ *     p_j = 1 / (1 + expf(-l_j))                           scoring 1 (sigmoid)
+ *     c_j = p_j, or p_j + select_bias[j]                   the selection key (select_bias: fp32 [experts], DeepSeek-V3 / GLM's
+ *                                                          e_score_correction_bias; it takes part in the selection only)
+ *     ids[r, 0 ... top_k) = the experts of largest key, best first. a goes before b when c_a > c_b, or c_a == c_b and a < b (ties:
+ *                           the lower index). A NaN key goes behind every other key; NaN keys among themselves by ascending index.
+ *                           The ids of a row are therefore always distinct and in [0, experts), whatever the logits hold.
+ *     weights[r, s] = p_ids[r,s]                           the UNBIASED score, fp32
+ *                     / (w_0 + w_1 + ... + w_top_k-1)      if renormalize: summed in slot order. No epsilon: a zero sum gives what IEEE
+ *                                                          division gives (inf, or NaN for 0 / 0)
+ *                     * scale                              always (routed_scaling_factor; 1.0f is exact)
+ * A row's result depends on that row alone: not on rows, on the row's place or on the grid. One launch, one wavefront per row, four
+ * per workgroup, no LDS, no workspace, no traffic between workgroups; nothing is read on the host, so the call can be captured.
+ * 1 <= experts <= 1024 (any value, not only multiples of 8 or 64), 1 <= top_k <= min(experts, 16), rows >= 0; every pointer aligned
+ * to its element (2 or 4 bytes), nothing more. Group-limited routing (n_group / topk_group) is not served.
+ * The call takes ONE pointer to an argument block; struct_bytes must be sizeof of the block the caller was compiled with, so a
+ * caller built against another version of this header is refused instead of misread. Returns 0 after the launch (rows == 0: 0, nothing
+ * launched). A call outside the preconditions - wrong struct_bytes, a NULL logits / ids / weights, a dtype, scoring, experts or top_k
+ * out of range, rows < 0, a misaligned pointer - prints one line on stderr, launches nothing and returns non-zero; unlike the void
+ * entry points above it does NOT end the process. bnb_mi355x_moe_topk_supported (pure host logic, aligned pointers assumed)
+ * answers 1 where the preconditions hold and rows >= 1, minus the classes in which the launch measured behind the torch composition
+ * it replaces (none excluded so far). */
+typedef struct bnb_mi355x_moe_topk_args {
+    size_t struct_bytes;            /* sizeof of this struct as the caller was compiled */
+    int logits_dtype;               /* 0 fp32, 1 fp16, 2 bf16 */
+    int scoring;                    /* 0 softmax, 1 sigmoid */
+    int renormalize;
+    int rows, experts, top_k;
+    float scale;
+    const void* logits;             /* [rows, experts] row-major */
+    const float* select_bias;       /* [experts] or NULL */
+    int* ids; float* weights;       /* [rows, top_k] each */
+    bnb_stream_t stream;
+} bnb_mi355x_moe_topk_args;
+int bnb_mi355x_moe_topk(const bnb_mi355x_moe_topk_args* args);
+int bnb_mi355x_moe_topk_supported(int logits_dtype, int rows, int experts, int top_k);
+
 /* Grouped gemm_4bit: `count` weight matrices applied to the SAME activations A[M, K] in one launch -
  *   out[i][M, N[i]] = A * dequant(B[i])^T (+ bias[i])        i = 0 .. count-1
  * (the Q/K/V projections of an attention block, the gate/up projections of an MLP: reference callers issue one
