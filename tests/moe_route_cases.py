@@ -2,7 +2,8 @@
 router's scoring + top-k launch (``bitsandbytes_amd::moe_topk``, csrc/moe_route.hip) and the public ``moe_topk`` / ``moe_route``.
 
 Grid: E x S x T x logits dtype x scoring x renormalize x select_bias, S <= E, thinned PAIRWISE (:func:`pairwise`): every value pair of
-every two axes that can occur together occurs in at least one case.
+every two axes that can occur together occurs in at least one case. The cover of the first grid (FIRST_ES) leads unchanged; a cover of
+the pairs that involve a later expert count (LATER_ES) follows it.
 
 Rankings are unambiguous BY CONSTRUCTION, so that float64 is the one right answer for the ids and a float32 implementation has to
 reproduce it exactly:
@@ -14,7 +15,15 @@ reproduce it exactly:
     0.999, so keys of different bias classes are more than 1e-3 apart, and the bias reorders the selection (a background expert with
     +1 goes before every high expert with 0) while the weights stay the unbiased scores.
 :func:`assert_unambiguous` checks the outcome in float64 for every row: two keys come from identical (logit, bias) pairs or differ by
-more than 1e-3. No row is dropped or redrawn."""
+more than 1e-3. No row is dropped or redrawn.
+
+Which inputs pin which rule. This grid pins the ids and the weights of ordinary rows in every template instance (E of FIRST_ES and
+LATER_ES: NI = 1, 2, 4, 8, 16 at both edges of an instance, :func:`lane_slots`), with ties among the ~20 high experts at random
+places. What a random row does not reach is built on purpose in tests/moe_route_edge_cases.py: a winner at every (lane, slot)
+position; one lane that supplies every winner; rows that are one tie; -inf, +inf and NaN logits and selection biases, where the
+order is "finite keys, then -inf keys, then NaN keys, each by index"; every 16-bit logit value through to_f32, expf and the
+division; a batch longer than the chip holds at once; and the Python entry on views. The tolerance for weights is the same
+everywhere: WEIGHT_FACTOR times the torch composition's error on the same GPU, floor WEIGHT_FLOOR."""
 from __future__ import annotations
 
 import functools
@@ -24,7 +33,9 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-ES = (1, 8, 60, 64, 72, 128, 1024)
+FIRST_ES = (1, 8, 60, 64, 72, 128, 1024)            # the grid of the first 29 cases: NI = 1, 2, 16
+LATER_ES = (65, 129, 160, 256, 257, 384, 512, 513)  # appended: NI = 2, 4, 8, 16 at their edges; DeepSeek-V2 / -V3 and Kimi-K2's E
+ES = FIRST_ES + LATER_ES
 SS = (1, 2, 8, 16)
 TS = (1, 3, 16, 37)
 DTYPES = (torch.float32, torch.float16, torch.bfloat16)
@@ -60,6 +71,13 @@ class RouteCase(NamedTuple):
 
 
 AXES = (ES, SS, TS, DTYPES, SCORINGS, (True, False), (False, True))
+FIRST_AXES = (FIRST_ES,) + AXES[1:]
+
+
+def lane_slots(E: int) -> int:
+    """NI of csrc/moe_route.hip: the experts a lane holds, ceil(E / 64) rounded up to a power of two."""
+    per_lane = (E + 63) // 64
+    return next(n for n in (1, 2, 4, 8, 16) if per_lane <= n)
 
 
 def valid(combo) -> bool:
@@ -76,17 +94,31 @@ def all_pairs():
     return out
 
 
-def pairwise():
-    """Greedy pairwise cover of the valid combinations, in a fixed order (a pure function of AXES)."""
-    axis_pairs = tuple(itertools.combinations(range(len(AXES)), 2))
-    pairs_of = {c: frozenset((a, c[a], b, c[b]) for a, b in axis_pairs) for c in itertools.product(*AXES) if valid(c)}
+def _greedy(axes, wanted):
+    """Greedy cover, in a fixed order (a pure function of its arguments), of those value pairs of the valid combinations of `axes`
+    that `wanted` accepts; only combinations that hold such a pair are candidates."""
+    axis_pairs = tuple(itertools.combinations(range(len(axes)), 2))
+    pairs_of = {}
+    for c in itertools.product(*axes):
+        if valid(c):
+            mine = frozenset(q for q in ((a, c[a], b, c[b]) for a, b in axis_pairs) if wanted(q))
+            if mine:
+                pairs_of[c] = mine
     todo = set().union(*pairs_of.values())
     chosen = []
     while todo:
         best = max(pairs_of, key=lambda c: len(pairs_of[c] & todo))   # (the first of equals: dicts keep insertion order)
         chosen.append(best)
         todo -= pairs_of[best]
-    return tuple(RouteCase(*c) for c in chosen)
+    return chosen
+
+
+def pairwise():
+    """The pairwise cover of the first grid (FIRST_ES: the 29 cases the kernel came with, unchanged and in their order), then a
+    greedy cover of every value pair that involves one of LATER_ES. Together: every pair of AXES."""
+    first = _greedy(FIRST_AXES, lambda q: True)
+    later = _greedy(AXES, lambda q: q[0] == 0 and q[1] in LATER_ES)
+    return tuple(RouteCase(*c) for c in first + later)
 
 
 CASES = pairwise()
@@ -176,3 +208,32 @@ def build(case: RouteCase) -> Built:
 
 def max_rel_err(w: torch.Tensor, w64: torch.Tensor) -> float:
     return float(((w.double().cpu() - w64).abs() / w64.abs()).max())
+
+
+class CountedEntry:
+    """Counts the calls of bnb_mi355x_moe_topk that the Python layer makes while it is active."""
+
+    def __enter__(self):
+        from bitsandbytes_amd.backends import hip
+
+        self.hip, self.real, self.calls = hip, hip.lib, 0
+        outer = self
+
+        class Proxy:
+            def __getattr__(self, name):
+                fn = getattr(outer.real, name)
+                if name != "bnb_mi355x_moe_topk":
+                    return fn
+
+                def counted(*args):
+                    outer.calls += 1
+                    return fn(*args)
+
+                return counted
+
+        hip.lib = Proxy()
+        return self
+
+    def __exit__(self, *exc):
+        self.hip.lib = self.real
+        return False

@@ -6,7 +6,7 @@
 * weights: against float64 on the same logits, at most four times the error of torch's own fp32 composition on this GPU, with a
   floor of 2^-20 (moe_route_cases: WEIGHT_FACTOR, WEIGHT_FLOOR);
 * a row's bits do not depend on the batch: every row of a 37-row call equals the 1-row call on that row;
-* a NaN or +inf logit stays in its row, and that row's ids stay distinct and in range;
+* a NaN or +inf logit stays in its row, and that row's ids are the documented ranking (NaN keys last, by index);
 * the C entry point between guard bands at a 1-element offset: bands and input untouched, every output byte written;
 * graph replay of ``moe_route``; its logits are ``lora_shrink``'s; its outputs feed ``moe_ffn_4bit`` with no conversion.
 The preconditions of the cases are asserted on the CPU by tests/test_moe_route_host.py.
@@ -55,33 +55,7 @@ def _result(case):
     return ids.cpu(), w.cpu(), cids.cpu(), cw.cpu()
 
 
-class _CountedEntry:
-    """Counts the calls of bnb_mi355x_moe_topk that the Python layer makes while it is active."""
-
-    def __enter__(self):
-        from bitsandbytes_amd.backends import hip
-
-        self.hip, self.real, self.calls = hip, hip.lib, 0
-        outer = self
-
-        class Proxy:
-            def __getattr__(self, name):
-                fn = getattr(outer.real, name)
-                if name != "bnb_mi355x_moe_topk":
-                    return fn
-
-                def counted(*args):
-                    outer.calls += 1
-                    return fn(*args)
-
-                return counted
-
-        hip.lib = Proxy()
-        return self
-
-    def __exit__(self, *exc):
-        self.hip.lib = self.real
-        return False
+_CountedEntry = C.CountedEntry
 
 
 # ------------------------------------------------------------------------------------------ ids and weights
@@ -150,6 +124,9 @@ def test_a_non_finite_logit_stays_in_its_row(scoring, poison):
         assert torch.equal(w[others].view(torch.int32), clean_w[others].view(torch.int32))
         got = ids[row].tolist()
         assert len(set(got)) == case.S and all(0 <= i < case.E for i in got), got
+        # ... and they are the documented ranking: NaN keys last by index (a poisoned softmax row is all NaN: 0, 1, ..., S - 1)
+        want_ids, _ = C.reference(dirty[row:row + 1].cpu(), case.S, scoring, True, case.scale, b.bias)
+        assert got == want_ids[0].tolist(), (got, want_ids[0].tolist())
         if scoring == "sigmoid" and poison == float("inf"):   # sigmoid(+inf) = 1: an ordinary score, and the best one of its bias class
             assert bool(torch.isfinite(w[row]).all())
 

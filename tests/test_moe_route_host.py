@@ -4,6 +4,7 @@ preconditions of every case tests/test_gpu_moe_route.py runs: rankings that are 
 import copy
 import ctypes as ct
 import fnmatch
+import hashlib
 import inspect
 import os
 import re
@@ -177,7 +178,12 @@ def test_fake_kernel_rejects_bad_arguments():
 
 # ------------------------------------------------------------------------------------------ the cases and the composition
 def test_the_grid_is_covered_pairwise():
-    assert C.CASES == C.pairwise() and len({c.name for c in C.CASES}) == len(C.CASES) <= 48
+    assert C.CASES == C.pairwise() and len({c.name for c in C.CASES}) == len(C.CASES) == 61
+    # the 29 cases of the first grid lead, in their order; every later case holds one of the later expert counts
+    assert all(c.E in C.FIRST_ES for c in C.CASES[:29]) and all(c.E in C.LATER_ES for c in C.CASES[29:])
+    first = [c.name for c in C.CASES[:29]]
+    assert (first[0], first[28]) == ("E1-S1-T1-float32-softmax-renorm-nobias", "E8-S1-T1-float32-softmax-renorm-nobias")
+    assert hashlib.sha256("\n".join(first).encode()).hexdigest()[:16] == "d563656429d4b8f8", "the first 29 cases changed"
     covered = set()
     for c in C.CASES:
         assert c.S <= c.E and c.E in C.ES and c.S in C.SS and c.T in C.TS
@@ -186,6 +192,17 @@ def test_the_grid_is_covered_pairwise():
     # what a pair cover promises: every value of every axis, and the corners the kernel's structure names
     assert {c.E for c in C.CASES} == set(C.ES) and {c.dtype for c in C.CASES} == set(C.DTYPES)
     assert any(c.E == 1024 and c.S == 16 for c in C.CASES) and any(c.E == 60 and c.T == 37 for c in C.CASES)
+
+
+def test_every_template_instance_is_launched_with_both_scorings_and_all_dtypes():
+    """moe_topk_kernel<T, NI> exists for NI = 1, 2, 4, 8, 16 experts per lane; the case list reaches each of them with both scorings
+    and with all three logits dtypes, at the first and the last E of the instance where the grid holds one."""
+    assert [C.lane_slots(E) for E in (1, 64, 65, 128, 129, 256, 257, 512, 513, 1024)] == [1, 1, 2, 2, 4, 4, 8, 8, 16, 16]
+    assert {C.lane_slots(c.E) for c in C.CASES} == {1, 2, 4, 8, 16}
+    for ni in (1, 2, 4, 8, 16):
+        mine = [c for c in C.CASES if C.lane_slots(c.E) == ni]
+        assert {c.scoring for c in mine} == set(C.SCORINGS) and {c.dtype for c in mine} == set(C.DTYPES), ni
+        assert {c.renormalize for c in mine} == {True, False} and {c.bias for c in mine} == {True, False}, ni
 
 
 @pytest.mark.parametrize("case", C.CASES, ids=lambda c: c.name)
