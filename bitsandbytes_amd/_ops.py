@@ -698,3 +698,40 @@ def _(logits, top_k: int, scoring: str, renormalize: bool, scale: float, select_
     lead = tuple(logits.shape[:-1])
     return (torch.empty((*lead, int(top_k)), dtype=torch.int32, device=logits.device),
             torch.empty((*lead, int(top_k)), dtype=torch.float32, device=logits.device))
+
+
+# ---------------------------------------------------------------------------------------------- moe_topk_grouped
+# Not a reference op: moe_topk with group-limited routing (DeepSeek-V2 / -V3 / R1, GLM-4.5), still ONE launch (csrc/moe_route.hip).
+# The experts are n_group contiguous groups of G = E / n_group. A group's score is its first key in the order of the selection
+# (group_score "max") or first + second key, one fp32 add ("top2sum", G >= 2); the topk_group groups first in that order on
+# (score, group index) stay, and ids / weights are moe_topk's over the experts of those groups only - an expert of a dropped group
+# never takes part (it is not a key of 0). n_group == 1 or topk_group == n_group: the bits of moe_topk.
+# Served for E % n_group == 0, 1 <= topk_group <= n_group <= 64, E <= 1024 and 1 <= top_k <= min(topk_group * G, 16)
+# (backends/hip.py: moe_topk_grouped_supported); anything else raises. Nothing is read on the host. Inference only.
+torch.library.define("bitsandbytes_amd::moe_topk_grouped",
+                     "(Tensor logits, int top_k, int n_group, int topk_group, str group_score, str scoring, bool renormalize, float scale, "
+                     "Tensor? select_bias=None) -> (Tensor, Tensor)")
+
+MOE_GROUP_SCORE_CODES = {"max": 0, "top2sum": 1}
+
+
+def _check_moe_topk_grouped(logits, top_k, n_group, topk_group, group_score, scoring, select_bias):
+    """Argument checks shared by the fake kernel and the device kernel; returns (rows, E)."""
+    torch._check(group_score in MOE_GROUP_SCORE_CODES, lambda: f"group_score must be 'max' or 'top2sum', got {group_score!r}")
+    rows, E = _check_moe_topk(logits, top_k, scoring, select_bias)
+    n_group, topk_group = int(n_group), int(topk_group)
+    torch._check(n_group >= 1 and E % n_group == 0, lambda: f"n_group must be >= 1 and divide E = {E}, got {n_group}")
+    torch._check(1 <= topk_group <= n_group, lambda: f"topk_group must be in [1, n_group] = [1, {n_group}], got {topk_group}")
+    G = E // n_group
+    torch._check(G >= 2 or group_score != "top2sum", lambda: f"group_score 'top2sum' needs groups of at least 2 experts, got E / n_group = {G}")
+    torch._check(int(top_k) <= topk_group * G,
+                 lambda: f"top_k must be at most topk_group * E / n_group = {topk_group * G} (the experts of the kept groups), got {top_k}")
+    return rows, E
+
+
+@register_fake("bitsandbytes_amd::moe_topk_grouped")
+def _(logits, top_k: int, n_group: int, topk_group: int, group_score: str, scoring: str, renormalize: bool, scale: float, select_bias=None):
+    _check_moe_topk_grouped(logits, top_k, n_group, topk_group, group_score, scoring, select_bias)
+    lead = tuple(logits.shape[:-1])
+    return (torch.empty((*lead, int(top_k)), dtype=torch.int32, device=logits.device),
+            torch.empty((*lead, int(top_k)), dtype=torch.float32, device=logits.device))

@@ -16,7 +16,7 @@ from warnings import warn
 import torch
 
 from .. import functional as F
-from .._ops import MOE_SCORING_CODES
+from .._ops import MOE_GROUP_SCORE_CODES, MOE_SCORING_CODES
 
 
 def _is_compiling() -> bool:
@@ -505,19 +505,45 @@ def lora_shrink_ids(x: torch.Tensor, lora_A: torch.Tensor, adapter_ids: torch.Te
     return tuple(p.contiguous() for p in t.split(splits, dim=-1))
 
 
-def _moe_topk_composition(logits, top_k, scoring, renormalize, scale, select_bias):
-    """:func:`moe_topk` from torch operations, with the kernel's selection rule: fp32 scores, the lower index on ties, NaN keys behind
-    every other key in ascending index (two stable sorts - ``torch.topk`` promises no order among equal keys and puts NaN first)."""
-    p = torch.softmax(logits.float(), dim=-1) if scoring == "softmax" else torch.sigmoid(logits.float())
-    key = p if select_bias is None else p + select_bias.to(device=p.device, dtype=torch.float32)
+def _moe_selection_order(key, dropped=None):
+    """The indices of ``key``'s last dimension in the order of the router's selection: larger key first, the lower index on ties, NaN
+    keys behind every other key in ascending index, ``dropped`` entries (bool, optional) behind all of those (two stable sorts -
+    ``torch.topk`` promises no order among equal keys and puts NaN first)."""
     nan = torch.isnan(key)
     order = torch.sort(torch.where(nan, torch.full_like(key, float("-inf")), key), dim=-1, descending=True, stable=True).indices
-    last = torch.sort(nan.gather(-1, order).to(torch.uint8), dim=-1, stable=True).indices
-    ids = order.gather(-1, last)[..., :top_k]
+    rank = nan.gather(-1, order).to(torch.uint8)
+    if dropped is not None:
+        rank = torch.where(dropped.gather(-1, order), torch.full_like(rank, 2), rank)
+    return order.gather(-1, torch.sort(rank, dim=-1, stable=True).indices)
+
+
+def _moe_topk_composition(logits, top_k, scoring, renormalize, scale, select_bias, groups=None):
+    """:func:`moe_topk` from torch operations, with the kernel's selection rule: fp32 scores, the lower index on ties, NaN keys behind
+    every other key in ascending index. ``groups = (n_group, topk_group, group_score)``: the group stage of :func:`moe_topk_grouped`
+    in front of the selection - the experts of dropped groups do not take part."""
+    p = torch.softmax(logits.float(), dim=-1) if scoring == "softmax" else torch.sigmoid(logits.float())
+    key = p if select_bias is None else p + select_bias.to(device=p.device, dtype=torch.float32)
+    dropped = None
+    if groups is not None:
+        n_group, topk_group, group_score = groups
+        by_group = key.reshape(*key.shape[:-1], n_group, key.shape[-1] // n_group)
+        best = by_group.gather(-1, _moe_selection_order(by_group)[..., :2 if group_score == "top2sum" else 1])
+        group_key = best[..., 0] + best[..., 1] if group_score == "top2sum" else best[..., 0]
+        kept = _moe_selection_order(group_key)[..., :topk_group]
+        dropped = torch.ones_like(group_key, dtype=torch.bool).scatter_(-1, kept, False)
+        dropped = dropped.unsqueeze(-1).expand(by_group.shape).reshape(key.shape)
+    ids = _moe_selection_order(key, dropped)[..., :top_k]
     w = p.gather(-1, ids)
     if renormalize:
         w = w / w.sum(dim=-1, keepdim=True)
     return ids.to(torch.int32), w * float(scale)
+
+
+def _moe_topk_grouped_composition(logits, top_k, n_group, topk_group, group_score, scoring, renormalize, scale, select_bias):
+    """:func:`moe_topk_grouped` from torch operations, by the kernel's rules (csrc/moe_route.hip); no data is read on the host. Where
+    every group stays (``topk_group == n_group``) it is :func:`_moe_topk_composition` itself."""
+    groups = (n_group, topk_group, group_score) if topk_group < n_group else None
+    return _moe_topk_composition(logits, top_k, scoring, renormalize, scale, select_bias, groups)
 
 
 def moe_topk(logits: torch.Tensor, top_k: int, scoring: str = "softmax", renormalize: bool = True, scale: float = 1.0,
@@ -535,7 +561,7 @@ def moe_topk(logits: torch.Tensor, top_k: int, scoring: str = "softmax", renorma
     The launch serves device tensors with ``E <= 1024`` and ``top_k <= 16`` (``backends.hip.moe_topk_supported``). Every other call -
     CPU tensors, more experts or slots, compilation - composes softmax / sigmoid, two stable sorts and a gather: the same ids wherever
     the keys are not within rounding of each other, weights equal to fp32 rounding. Neither path reads data on the host, so both can
-    be captured in a graph. Group-limited routing (``n_group`` / ``topk_group``) is not served. Inference only."""
+    be captured in a graph. Group-limited routing (``n_group`` / ``topk_group``): :func:`moe_topk_grouped`. Inference only."""
     if scoring not in MOE_SCORING_CODES:
         raise ValueError(f"moe_topk: scoring must be 'softmax' or 'sigmoid', got {scoring!r}")
     if logits.dim() < 1 or logits.shape[-1] < 1 or not logits.is_floating_point():
@@ -557,6 +583,19 @@ def moe_topk(logits: torch.Tensor, top_k: int, scoring: str = "softmax", renorma
     return _moe_topk_composition(logits, top_k, scoring, bool(renormalize), scale, select_bias)
 
 
+def _moe_router_logits(name, x, router_weight, bias):
+    """The argument checks and the logits of :func:`moe_route` / :func:`moe_route_grouped` (``name``: the caller, for the messages)."""
+    if router_weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != router_weight.shape[1]:
+        raise ValueError(f"{name}: router_weight must be [E, K] and x [*, K], got {tuple(router_weight.shape)} and {tuple(x.shape)}")
+    if bias is not None and tuple(bias.shape) != (router_weight.shape[0],):
+        raise ValueError(f"{name}: bias must be [E] = [{router_weight.shape[0]}], got {tuple(bias.shape)}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, router_weight, bias)):
+        raise RuntimeError(f"{name} is inference only (no autograd formula): call it under torch.no_grad() or with detached inputs")
+    if bias is None and router_weight.dtype == x.dtype:
+        return lora_shrink(x, router_weight)
+    return torch.nn.functional.linear(x.to(router_weight.dtype), router_weight, None if bias is None else bias.to(router_weight.dtype))
+
+
 def moe_route(x: torch.Tensor, router_weight: torch.Tensor, top_k: int, *, bias: Optional[torch.Tensor] = None, scoring: str = "softmax",
               renormalize: bool = True, scale: float = 1.0, select_bias: Optional[torch.Tensor] = None, return_logits: bool = False):
     """A whole mixture-of-experts router, ``(ids, weights) = moe_topk(x @ router_weight.T (+ bias), ...)``, in TWO launches where both
@@ -569,17 +608,71 @@ def moe_route(x: torch.Tensor, router_weight: torch.Tensor, top_k: int, *, bias:
     Dtypes: the two-launch form needs ``router_weight`` in ``x``'s 16-bit dtype. A gate kept in another dtype (fp32 under bf16
     activations, as several MoE models do) is never rounded: ``x`` - the small operand - is cast to the weight's dtype, one extra
     launch, and ``F.linear`` computes the logits in that dtype. ``select_bias`` should be fp32: another dtype is cast on every call."""
-    if router_weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != router_weight.shape[1]:
-        raise ValueError(f"moe_route: router_weight must be [E, K] and x [*, K], got {tuple(router_weight.shape)} and {tuple(x.shape)}")
-    if bias is not None and tuple(bias.shape) != (router_weight.shape[0],):
-        raise ValueError(f"moe_route: bias must be [E] = [{router_weight.shape[0]}], got {tuple(bias.shape)}")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, router_weight, bias)):
-        raise RuntimeError("moe_route is inference only (no autograd formula): call it under torch.no_grad() or with detached inputs")
-    if bias is None and router_weight.dtype == x.dtype:
-        logits = lora_shrink(x, router_weight)
-    else:
-        logits = torch.nn.functional.linear(x.to(router_weight.dtype), router_weight, None if bias is None else bias.to(router_weight.dtype))
+    logits = _moe_router_logits("moe_route", x, router_weight, bias)
     ids, weights = moe_topk(logits, top_k, scoring=scoring, renormalize=renormalize, scale=scale, select_bias=select_bias)
+    return (ids, weights, logits) if return_logits else (ids, weights)
+
+
+def moe_topk_grouped(logits: torch.Tensor, top_k: int, n_group: int, topk_group: int, group_score: str = "top2sum", scoring: str = "sigmoid",
+                     renormalize: bool = True, scale: float = 1.0, select_bias: Optional[torch.Tensor] = None):
+    """:func:`moe_topk` with group-limited routing - the router of DeepSeek-V2, DeepSeek-V3 / R1 and GLM-4.5 - still as ONE launch.
+    Scores, keys (``p``, or ``p + select_bias``), the order of the selection, weights, shapes and dtypes are :func:`moe_topk`'s. In
+    addition the ``E`` experts are ``n_group`` contiguous groups of ``G = E / n_group``:
+
+    * a group's score is its first key in the order of the selection (``group_score="max"``: DeepSeek-V2's ``group_limited_greedy``)
+      or the sum of its first two keys, one fp32 add (``"top2sum"``: DeepSeek-V3 / GLM's ``noaux_tc``; needs ``G >= 2``);
+    * the ``topk_group`` groups that go first in the same order - ties to the lower group, a NaN score last - stay;
+    * the ``top_k`` experts are chosen among the experts of those groups only, ``top_k <= topk_group * G``.
+
+    With ``n_group == 1`` or ``topk_group == n_group`` the result has the bits of :func:`moe_topk`. Two deliberate differences from
+    the Hugging Face modelling code: an expert of a dropped group NEVER takes part - HF fills its key with ``0.0``, which goes before a
+    kept expert whose biased key is negative; DeepSeek's own inference code fills ``-inf``, as here -, and the renormalisation sum has
+    no ``1e-20`` added (no epsilon anywhere in this router).
+
+    The launch serves device tensors with ``E <= 1024``, ``n_group <= 64`` and ``top_k <= 16``
+    (``backends.hip.moe_topk_grouped_supported``); every other call - CPU tensors, larger sizes, compilation - composes the same rules
+    from torch operations with stable sorts. Neither path reads data on the host. Inference only."""
+    if scoring not in MOE_SCORING_CODES:
+        raise ValueError(f"moe_topk_grouped: scoring must be 'softmax' or 'sigmoid', got {scoring!r}")
+    if group_score not in MOE_GROUP_SCORE_CODES:
+        raise ValueError(f"moe_topk_grouped: group_score must be 'max' or 'top2sum', got {group_score!r}")
+    if logits.dim() < 1 or logits.shape[-1] < 1 or not logits.is_floating_point():
+        raise ValueError(f"moe_topk_grouped: logits must be a float tensor [*, E] with E >= 1, got {logits.dtype} {tuple(logits.shape)}")
+    E, top_k, n_group, topk_group = int(logits.shape[-1]), int(top_k), int(n_group), int(topk_group)
+    if n_group < 1 or E % n_group != 0:
+        raise ValueError(f"moe_topk_grouped: n_group must be >= 1 and divide E = {E}, got {n_group}")
+    if not 1 <= topk_group <= n_group:
+        raise ValueError(f"moe_topk_grouped: topk_group must be in [1, n_group] = [1, {n_group}], got {topk_group}")
+    G = E // n_group
+    if group_score == "top2sum" and G < 2:
+        raise ValueError(f"moe_topk_grouped: group_score 'top2sum' needs groups of at least 2 experts, got E / n_group = {G}")
+    if not 1 <= top_k <= topk_group * G:
+        raise ValueError(f"moe_topk_grouped: top_k must be in [1, topk_group * E / n_group] = [1, {topk_group * G}], got {top_k}")
+    if select_bias is not None and tuple(select_bias.shape) != (E,):
+        raise ValueError(f"moe_topk_grouped: select_bias must be [E] = [{E}], got {tuple(select_bias.shape)}")
+    if torch.is_grad_enabled() and (logits.requires_grad or (select_bias is not None and select_bias.requires_grad)):
+        raise RuntimeError("moe_topk_grouped is inference only (no autograd formula): call it under torch.no_grad() or with detached inputs")
+    rows = logits.numel() // E
+    if logits.device.type == "cuda" and rows > 0 and not _is_compiling() and (select_bias is None or select_bias.device == logits.device):
+        from ..backends import hip
+
+        if hip.moe_topk_grouped_supported(logits.dtype, rows, E, top_k, n_group, topk_group, group_score):
+            sb = None if select_bias is None else select_bias.to(torch.float32).contiguous()
+            return torch.ops.bitsandbytes_amd.moe_topk_grouped.default(logits.contiguous(), top_k, n_group, topk_group, group_score, scoring,
+                                                                       bool(renormalize), float(scale), sb)
+    return _moe_topk_grouped_composition(logits, top_k, n_group, topk_group, group_score, scoring, bool(renormalize), scale, select_bias)
+
+
+def moe_route_grouped(x: torch.Tensor, router_weight: torch.Tensor, top_k: int, n_group: int, topk_group: int, *,
+                      group_score: str = "top2sum", bias: Optional[torch.Tensor] = None, scoring: str = "sigmoid", renormalize: bool = True,
+                      scale: float = 1.0, select_bias: Optional[torch.Tensor] = None, return_logits: bool = False):
+    """:func:`moe_route` with group-limited routing: ``moe_topk_grouped(x @ router_weight.T (+ bias), ...)``, two launches where both
+    halves are served. The logits come exactly as in :func:`moe_route` (:func:`lora_shrink`, or ``F.linear`` for a gate with a logit
+    ``bias`` or of another dtype than ``x``); the second launch is :func:`moe_topk_grouped`. Returns ``(ids, weights)`` ``[*, top_k]``,
+    and the logits behind them with ``return_logits``. Inference only."""
+    logits = _moe_router_logits("moe_route_grouped", x, router_weight, bias)
+    ids, weights = moe_topk_grouped(logits, top_k, n_group, topk_group, group_score=group_score, scoring=scoring, renormalize=renormalize,
+                                    scale=scale, select_bias=select_bias)
     return (ids, weights, logits) if return_logits else (ids, weights)
 
 

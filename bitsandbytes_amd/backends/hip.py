@@ -21,7 +21,7 @@ from warnings import warn
 
 import torch
 
-from .._ops import (GATED_CODES, MOE_SCORING_CODES, _check_gemm_4bit_experts, _check_gemm_4bit_experts_ffn, _check_gemm_4bit_gated,
+from .._ops import (GATED_CODES, MOE_GROUP_SCORE_CODES, MOE_SCORING_CODES, _check_moe_topk_grouped, _check_gemm_4bit_experts, _check_gemm_4bit_experts_ffn, _check_gemm_4bit_gated,
                      _check_gemm_4bit_lora, _check_gemm_4bit_lora_ids,
                      _check_lora_shrink, _check_lora_shrink_ids, _check_moe_topk, register_kernel)
 from ..cextension import lib
@@ -755,6 +755,44 @@ def _(logits, top_k: int, scoring: str, renormalize: bool, scale: float, select_
                            int(top_k), float(scale), logits.data_ptr(), _ptr(select_bias), ids.data_ptr(), weights.data_ptr(), _stream(logits))
         if lib.bnb_mi355x_moe_topk(ct.byref(args)) != 0:
             raise RuntimeError(f"moe_topk: the library refused rows={rows}, experts={E}, top_k={top_k}, dtype={logits.dtype}")
+    return ids, weights
+
+
+# ------------------------------------------------------------------------------------------ moe_topk_grouped
+def moe_topk_grouped_supported(dtype: torch.dtype, rows: int, experts: int, top_k: int, n_group: int, topk_group: int,
+                               group_score: str = "top2sum") -> bool:
+    """Whether ``bitsandbytes_amd::moe_topk_grouped`` has a kernel for the class: 16/32-bit float logits, ``experts % n_group == 0``,
+    ``1 <= topk_group <= n_group <= 64``, ``1 <= experts <= 1024``, ``1 <= top_k <= min(topk_group * experts / n_group, 16)``, groups of
+    at least two experts for ``"top2sum"``, ``rows >= 1``, minus the classes the measurements exclude (pure host logic of the library)."""
+    sizes = (rows, experts, top_k, n_group, topk_group)
+    if dtype not in _DT_CODE or group_score not in MOE_GROUP_SCORE_CODES or max(sizes) >= 2**31 or min(sizes) < 0:
+        return False
+    return bool(lib.bnb_mi355x_moe_topk_grouped_supported(_DT_CODE[dtype], rows, experts, top_k, n_group, topk_group,
+                                                          MOE_GROUP_SCORE_CODES[group_score]))
+
+
+@register_kernel("bitsandbytes_amd::moe_topk_grouped", "cuda")
+def _(logits, top_k: int, n_group: int, topk_group: int, group_score: str, scoring: str, renormalize: bool, scale: float, select_bias=None):
+    """One launch of csrc/moe_route.hip; nothing is read on the host."""
+    from ..cextension import MoeTopkGroupedArgs
+
+    rows, E = _check_moe_topk_grouped(logits, top_k, n_group, topk_group, group_score, scoring, select_bias)
+    lead = tuple(logits.shape[:-1])
+    ids = torch.empty((*lead, int(top_k)), dtype=torch.int32, device=logits.device)
+    weights = torch.empty((*lead, int(top_k)), dtype=torch.float32, device=logits.device)
+    if rows == 0:
+        return ids, weights
+    if not moe_topk_grouped_supported(logits.dtype, rows, E, int(top_k), int(n_group), int(topk_group), group_score):
+        raise ValueError(f"moe_topk_grouped: no kernel for rows={rows}, experts={E}, top_k={top_k}, n_group={n_group}, topk_group={topk_group}, "
+                         f"dtype={logits.dtype} (1 <= experts <= 1024, n_group <= 64, 1 <= top_k <= 16); compose it from torch operations - "
+                         "bitsandbytes_amd.moe_topk_grouped does")
+    with _device_of(logits):
+        args = MoeTopkGroupedArgs(ct.sizeof(MoeTopkGroupedArgs), _DT_CODE[logits.dtype], MOE_SCORING_CODES[scoring], 1 if renormalize else 0,
+                                  rows, E, int(top_k), int(n_group), int(topk_group), MOE_GROUP_SCORE_CODES[group_score], float(scale),
+                                  logits.data_ptr(), _ptr(select_bias), ids.data_ptr(), weights.data_ptr(), _stream(logits))
+        if lib.bnb_mi355x_moe_topk_grouped(ct.byref(args)) != 0:
+            raise RuntimeError(f"moe_topk_grouped: the library refused rows={rows}, experts={E}, top_k={top_k}, n_group={n_group}, "
+                               f"topk_group={topk_group}, dtype={logits.dtype}")
     return ids, weights
 
 

@@ -54,6 +54,17 @@ class MoeTopkArgs(ct.Structure):
                 ("stream", ct.c_void_p)]
 
 
+class MoeTopkGroupedArgs(ct.Structure):
+    """``bnb_mi355x_moe_topk_grouped_args`` of include/bnb_mi355x.h: the argument block of ``bnb_mi355x_moe_topk_grouped``
+    (``group_score``: 0 max, 1 top2sum). ``struct_bytes`` is ``ctypes.sizeof(MoeTopkGroupedArgs)``."""
+
+    _fields_ = [("struct_bytes", ct.c_size_t), ("logits_dtype", ct.c_int), ("scoring", ct.c_int), ("renormalize", ct.c_int),
+                ("rows", ct.c_int), ("experts", ct.c_int), ("top_k", ct.c_int), ("n_group", ct.c_int), ("topk_group", ct.c_int),
+                ("group_score", ct.c_int), ("scale", ct.c_float),
+                ("logits", ct.c_void_p), ("select_bias", ct.c_void_p), ("ids", ct.c_void_p), ("weights", ct.c_void_p),
+                ("stream", ct.c_void_p)]
+
+
 def _declare(dll: ct.CDLL) -> None:
     def sig(names, argtypes, restype=None):
         for n in names:
@@ -116,6 +127,9 @@ def _declare(dll: ct.CDLL) -> None:
     # (one argument block, passed with ctypes.byref(MoeTopkArgs(...)); non-zero: refused, nothing launched)
     sig(["bnb_mi355x_moe_topk"], [_VOID_P], _I32)
     sig(["bnb_mi355x_moe_topk_supported"], [_I32] * 4, _I32)  # (logits_dtype, rows, experts, top_k)
+    sig(["bnb_mi355x_moe_topk_grouped"], [_VOID_P], _I32)  # (ctypes.byref(MoeTopkGroupedArgs(...)))
+    # (logits_dtype, rows, experts, top_k, n_group, topk_group, group_score)
+    sig(["bnb_mi355x_moe_topk_grouped_supported"], [_I32] * 7, _I32)
     # (dtype, A, count, B[], absmax[], absmax_8bit[], absmax_code[], absmax_offset[], out[], bias[], N[], M, K, blocksize, quant_type, stream)
     sig(["bnb_mi355x_gemm_4bit_grouped"], [_I32, _VOID_P, _I32] + [_VOID_P] * 8 + [_I32] * 4 + [_VOID_P])
     sig(["bnb_mi355x_gemm_4bit_grouped_route"], [_I32, _I32, _VOID_P, _I32, _I32, _I32], _I32)  # (dtype, count, N[], M, K, blocksize)
@@ -189,6 +203,7 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_lora_shrink", "bnb_mi355x_lora_shrink_supported",
        "bnb_mi355x_lora_shrink_ids", "bnb_mi355x_lora_shrink_ids_supported",
        "bnb_mi355x_moe_topk", "bnb_mi355x_moe_topk_supported",
+       "bnb_mi355x_moe_topk_grouped", "bnb_mi355x_moe_topk_grouped_supported",
        "bnb_mi355x_gemm_4bit_grad_input", "bnb_mi355x_gemm_4bit_grad_input_workspace_bytes", "bnb_mi355x_gemm_4bit_grad_input_supported",
        "bnb_mi355x_peer_buffer_bytes", "bnb_mi355x_peer_alloc", "bnb_mi355x_peer_free", "bnb_mi355x_peer_export", "bnb_mi355x_peer_open",
        "bnb_mi355x_peer_close", "bnb_mi355x_peer_allgather", "bnb_mi355x_peer_status",

@@ -176,6 +176,13 @@ struct MoeTopkCall {
 };
 bool moe_topk_supported(int dtype, int rows, int experts, int top_k);
 bool moe_topk(const MoeTopkCall& call, hipStream_t stream);
+// (group-limited routing: the fields of bnb_mi355x_moe_topk_grouped_args)
+struct MoeTopkGroupedCall {
+    MoeTopkCall base;
+    int n_group, topk_group, group_score; // group_score: 0 "max", 1 "top2sum"
+};
+bool moe_topk_grouped_supported(int dtype, int rows, int experts, int top_k, int n_group, int topk_group, int group_score);
+bool moe_topk_grouped(const MoeTopkGroupedCall& call, hipStream_t stream);
 
 // c_api.hip (g_last_gemm_kernel, defined there as well, is declared in bnb_common.h)
 #ifdef BNB_PROFILING

@@ -372,6 +372,26 @@ int bnb_mi355x_moe_topk(const bnb_mi355x_moe_topk_args* args) {
 int bnb_mi355x_moe_topk_supported(int logits_dtype, int rows, int experts, int top_k) {
     return moe_topk_supported(logits_dtype, rows, experts, top_k) ? 1 : 0;
 }
+// (group-limited routing: the same conventions, a block of its own)
+int bnb_mi355x_moe_topk_grouped(const bnb_mi355x_moe_topk_grouped_args* args) {
+    if (args == nullptr || args->struct_bytes != sizeof(bnb_mi355x_moe_topk_grouped_args)) {
+        fprintf(stderr, "bitsandbytes_amd: moe_topk_grouped: struct_bytes is %zu, this library's bnb_mi355x_moe_topk_grouped_args has %zu\n",
+                args == nullptr ? static_cast<size_t>(0) : args->struct_bytes, sizeof(bnb_mi355x_moe_topk_grouped_args));
+        return 1;
+    }
+    const MoeTopkGroupedCall call = {{args->logits_dtype, args->scoring, args->renormalize != 0 ? 1 : 0, args->rows, args->experts, args->top_k,
+                                      args->scale, args->logits, args->select_bias, args->ids, args->weights},
+                                     args->n_group, args->topk_group, args->group_score};
+    if (!moe_topk_grouped(call, S(args->stream))) {
+        fprintf(stderr, "bitsandbytes_amd: moe_topk_grouped: no kernel for logits_dtype %d, scoring %d, rows=%d, experts=%d, top_k=%d, n_group=%d, topk_group=%d, group_score=%d (fp32 / fp16 / bf16 logits, scoring 0 / 1, rows >= 0, 1 <= experts <= 1024, experts %% n_group == 0, 1 <= topk_group <= n_group <= 64, group_score 0 (max) / 1 (top2sum: experts / n_group >= 2), 1 <= top_k <= min(topk_group * experts / n_group, 16); logits / ids / weights not NULL; every pointer aligned to its element)\n",
+                args->logits_dtype, args->scoring, args->rows, args->experts, args->top_k, args->n_group, args->topk_group, args->group_score);
+        return 1;
+    }
+    return 0;
+}
+int bnb_mi355x_moe_topk_grouped_supported(int logits_dtype, int rows, int experts, int top_k, int n_group, int topk_group, int group_score) {
+    return moe_topk_grouped_supported(logits_dtype, rows, experts, top_k, n_group, topk_group, group_score) ? 1 : 0;
+}
 
 // ------------------------------------------------------------------ peer chain (the all-gather fused into the gemv launches)
 static uint32_t peer_chain_spin_bound() {

@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from .. import functional as F
-from .._ops import MOE_SCORING_CODES
+from .._ops import MOE_GROUP_SCORE_CODES, MOE_SCORING_CODES
 from ..autograd import matmul_4bit
 from ..functional import QuantState
 
@@ -672,6 +672,8 @@ class MoERouter(nn.Module):
     ``x``'s device - what :func:`bitsandbytes_amd.moe_ffn_4bit` takes as ``expert_ids`` and ``routing_weights`` - in two launches where
     :func:`bitsandbytes_amd.moe_route` is served. ``scoring``: ``"softmax"`` (Mixtral, Qwen) or ``"sigmoid"`` (DeepSeek-V3, GLM);
     ``renormalize`` / ``scale``: the chosen scores divided by their sum, then times ``scale`` (``routed_scaling_factor``).
+    ``n_group`` > 1: group-limited routing (DeepSeek-V2 / -V3, GLM) - the best ``topk_group`` of ``n_group`` contiguous expert groups,
+    ranked by ``group_score`` (``"max"`` or ``"top2sum"``), then the top-k among their experts (:func:`bitsandbytes_amd.moe_route_grouped`).
 
     State-dict keys: ``weight`` ``[num_experts, hidden]`` - an ``nn.Linear`` gate's checkpoint loads as it is -, ``bias``
     ``[num_experts]`` with ``bias=True`` (added to the logits), and ``e_score_correction_bias`` ``[num_experts]`` fp32 with
@@ -683,12 +685,24 @@ class MoERouter(nn.Module):
     ``F.linear`` (:func:`bitsandbytes_amd.moe_route`)."""
 
     def __init__(self, hidden: int, num_experts: int, top_k: int, scoring: str = "softmax", renormalize: bool = True, scale: float = 1.0,
-                 bias: bool = False, select_bias: bool = False, device=None, dtype=None):
+                 bias: bool = False, select_bias: bool = False, device=None, dtype=None, n_group: int = 1, topk_group: int = 1,
+                 group_score: str = "top2sum"):
         super().__init__()
         if scoring not in MOE_SCORING_CODES:
             raise ValueError(f"MoERouter: scoring must be 'softmax' or 'sigmoid', got {scoring!r}")
         if not 1 <= int(top_k) <= int(num_experts):
             raise ValueError(f"MoERouter: top_k must be in [1, num_experts] = [1, {num_experts}], got {top_k}")
+        self.n_group, self.topk_group, self.group_score = int(n_group), int(topk_group), group_score
+        if self.n_group > 1:
+            if group_score not in MOE_GROUP_SCORE_CODES:
+                raise ValueError(f"MoERouter: group_score must be 'max' or 'top2sum', got {group_score!r}")
+            if int(num_experts) % self.n_group != 0 or not 1 <= self.topk_group <= self.n_group:
+                raise ValueError(f"MoERouter: n_group must divide num_experts = {num_experts} and topk_group be in [1, n_group], got "
+                                 f"n_group={n_group}, topk_group={topk_group}")
+            G = int(num_experts) // self.n_group
+            if int(top_k) > self.topk_group * G or (group_score == "top2sum" and G < 2):
+                raise ValueError(f"MoERouter: top_k must be at most topk_group * num_experts / n_group = {self.topk_group * G}, and "
+                                 f"'top2sum' needs groups of at least 2 experts; got top_k={top_k}, {G} experts a group")
         self.hidden, self.num_experts, self.top_k = int(hidden), int(num_experts), int(top_k)
         self.scoring, self.renormalize, self.scale = scoring, bool(renormalize), float(scale)
         self.weight = nn.Parameter(torch.empty(self.num_experts, self.hidden, device=device, dtype=dtype), requires_grad=False)
@@ -705,15 +719,22 @@ class MoERouter(nn.Module):
         return self
 
     def forward(self, x: torch.Tensor):
-        from ..autograd import moe_route
+        from ..autograd import moe_route, moe_route_grouped
 
+        if self.n_group > 1:
+            return moe_route_grouped(x, self.weight, self.top_k, self.n_group, self.topk_group, group_score=self.group_score, bias=self.bias,
+                                     scoring=self.scoring, renormalize=self.renormalize, scale=self.scale,
+                                     select_bias=self.e_score_correction_bias)
         return moe_route(x, self.weight, self.top_k, bias=self.bias, scoring=self.scoring, renormalize=self.renormalize, scale=self.scale,
                          select_bias=self.e_score_correction_bias)
 
     def extra_repr(self) -> str:
-        return (f"hidden={self.hidden}, num_experts={self.num_experts}, top_k={self.top_k}, scoring={self.scoring!r}, "
+        text = (f"hidden={self.hidden}, num_experts={self.num_experts}, top_k={self.top_k}, scoring={self.scoring!r}, "
                 f"renormalize={self.renormalize}, scale={self.scale}, bias={self.bias is not None}, "
                 f"select_bias={self.e_score_correction_bias is not None}")
+        if self.n_group > 1:
+            text += f", n_group={self.n_group}, topk_group={self.topk_group}, group_score={self.group_score!r}"
+        return text
 
 
 class Embedding4bit(nn.Embedding):

@@ -280,7 +280,7 @@ int bnb_mi355x_lora_shrink_ids_supported(int dtype, int M, int A_n, int R, int K
  * A row's result depends on that row alone: not on rows, on the row's place or on the grid. One launch, one wavefront per row, four
  * per workgroup, no LDS, no workspace, no traffic between workgroups; nothing is read on the host, so the call can be captured.
  * 1 <= experts <= 1024 (any value, not only multiples of 8 or 64), 1 <= top_k <= min(experts, 16), rows >= 0; every pointer aligned
- * to its element (2 or 4 bytes), nothing more. Group-limited routing (n_group / topk_group) is not served.
+ * to its element (2 or 4 bytes), nothing more. Group-limited routing (n_group / topk_group): bnb_mi355x_moe_topk_grouped, below.
  * The call takes ONE pointer to an argument block; struct_bytes must be sizeof of the block the caller was compiled with, so a
  * caller built against another version of this header is refused instead of misread. Returns 0 after the launch (rows == 0: 0, nothing
  * launched). A call outside the preconditions - wrong struct_bytes, a NULL logits / ids / weights, a dtype, scoring, experts or top_k
@@ -302,6 +302,36 @@ typedef struct bnb_mi355x_moe_topk_args {
 } bnb_mi355x_moe_topk_args;
 int bnb_mi355x_moe_topk(const bnb_mi355x_moe_topk_args* args);
 int bnb_mi355x_moe_topk_supported(int logits_dtype, int rows, int experts, int top_k);
+/* Group-limited routing - the router of DeepSeek-V2, DeepSeek-V3 / R1 and GLM-4.5 - as the same ONE launch. Scores, keys, the order
+ * of the selection, weights, layouts and every convention of the call: as for bnb_mi355x_moe_topk, above. In addition the experts
+ * are n_group contiguous groups of G = experts / n_group: group g holds the experts g G ... g G + G - 1.
+ *     group score, group_score 0 (max):      the first key of the group in the order of the selection (DeepSeek-V2)
+ *                  group_score 1 (top2sum):  first key + second key, one fp32 add (DeepSeek-V3 / GLM); needs G >= 2
+ *     the topk_group groups that go first in the same order, taken on the pair group score / group index, stay: ties go to the
+ *     lower group, a NaN score goes last
+ *     ids = top_k rounds of the selection over the experts of the groups that stay. An expert of a dropped group never takes part:
+ *     it is not a key of 0, so it never goes before an expert of a kept group whose biased key is negative
+ * Any G is served, also one that is no power of two and no divisor of 64. With n_group == 1 or topk_group == n_group the result has
+ * the bits of bnb_mi355x_moe_topk. experts % n_group == 0, 1 <= topk_group <= n_group <= 64, 1 <= experts <= 1024,
+ * 1 <= top_k <= min of topk_group * G and 16. A call outside the preconditions prints one line on stderr, launches nothing and returns
+ * non-zero. bnb_mi355x_moe_topk_grouped_supported answers 1 where the preconditions hold and rows >= 1, minus the classes in which
+ * the launch measured behind the torch composition it replaces (none excluded so far). */
+typedef struct bnb_mi355x_moe_topk_grouped_args {
+    size_t struct_bytes;            /* sizeof of this struct as the caller was compiled */
+    int logits_dtype;               /* 0 fp32, 1 fp16, 2 bf16 */
+    int scoring;                    /* 0 softmax, 1 sigmoid */
+    int renormalize;
+    int rows, experts, top_k;
+    int n_group, topk_group;
+    int group_score;                /* 0 max, 1 top2sum */
+    float scale;
+    const void* logits;             /* [rows, experts] row-major */
+    const float* select_bias;       /* [experts] or NULL */
+    int* ids; float* weights;       /* [rows, top_k] each */
+    bnb_stream_t stream;
+} bnb_mi355x_moe_topk_grouped_args;
+int bnb_mi355x_moe_topk_grouped(const bnb_mi355x_moe_topk_grouped_args* args);
+int bnb_mi355x_moe_topk_grouped_supported(int logits_dtype, int rows, int experts, int top_k, int n_group, int topk_group, int group_score);
 
 /* Grouped gemm_4bit: `count` weight matrices applied to the SAME activations A[M, K] in one launch -
  *   out[i][M, N[i]] = A * dequant(B[i])^T (+ bias[i])        i = 0 .. count-1
