@@ -453,6 +453,38 @@ def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str,
     return torch.empty((*ids.shape, width), dtype=A.dtype, device=A.device)
 
 
+# ---------------------------------------------------------------------------------------------- gemm_4bit_experts_combine
+# The down projection of an expert FFN with the routing-weighted slot sum in the launch (token-major grid):
+#   out[t, :] = sum over the slots s with 0 <= ids[t, s] < E:  weights[t, s] * (A[t, s] @ dequantize_4bit(B)[ids[t, s]].T (+ bias[ids[t, s]]))
+# A [T, S, K], ids and weights [T, S] (weights fp32 or A's dtype) on the device and read there only; out [T, N]: fp32 sums in a fixed
+# order, ONE rounding. A slot with an id outside [0, E) contributes nothing whatever its weight. 1 <= S <= 16. Inference only.
+torch.library.define(
+    "bitsandbytes_amd::gemm_4bit_experts_combine",
+    "(Tensor A, Tensor B, int[] shapeB, Tensor absmax, Tensor ids, Tensor weights, int blocksize, str quant_type, Tensor? bias=None, "
+    "Tensor? absmax_8bit=None, Tensor? absmax_code=None, Tensor? absmax_offset=None) -> Tensor",
+)
+
+
+def _check_gemm_4bit_experts_combine(A, B, shapeB, absmax, ids, weights, blocksize, quant_type, bias, absmax_8bit, absmax_code,
+                                     absmax_offset):
+    """The checks of gemm_4bit_experts and those of the slot sum; returns (E, N, K)."""
+    E, N, K, _ = _check_gemm_4bit_experts(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code, absmax_offset)
+    torch._check(A.dim() == 3 and ids.dim() == 2, lambda: f"A must be [T, S, K] and ids [T, S], got {A.dim()} and {ids.dim()} dims")
+    torch._check(tuple(weights.shape) == tuple(ids.shape),
+                 lambda: f"weights must have the shape of ids {tuple(ids.shape)}, got {tuple(weights.shape)}")
+    torch._check(weights.dtype in (torch.float32, A.dtype), lambda: f"weights must be float32 or {A.dtype}, got {weights.dtype}")
+    torch._check(weights.device == A.device, lambda: "weights must live on A's device")
+    return E, N, K
+
+
+@register_fake("bitsandbytes_amd::gemm_4bit_experts_combine")
+def _(A, B, shapeB: Sequence[int], absmax, ids, weights, blocksize: int, quant_type: str, bias=None, absmax_8bit=None, absmax_code=None,
+      absmax_offset=None):
+    _, N, _ = _check_gemm_4bit_experts_combine(A, B, shapeB, absmax, ids, weights, blocksize, quant_type, bias, absmax_8bit, absmax_code,
+                                               absmax_offset)
+    return torch.empty((ids.shape[0], N), dtype=A.dtype, device=A.device)
+
+
 # ---------------------------------------------------------------------------------------------- gemm_4bit_gated
 # Not a reference op: the gate / up projections of a dense gated-SiLU FFN (Llama, Mistral, Qwen, Phi-3) with the activation as the
 # matmul's epilogue. B is the quantize_4bit result of ONE interleaved [2 F, K] matrix - gate row i at row 2 i, up row i at row 2 i + 1

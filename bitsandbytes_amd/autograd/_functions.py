@@ -221,6 +221,63 @@ def matmul_4bit_experts(
               bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code, absmax_offset=quant_state.offset, **extra)
 
 
+def _combine_served(h: torch.Tensor, quant_state: F.QuantState, S: int) -> bool:
+    """Whether the token-major launch serves this down projection - decided from shapes and dtypes only."""
+    if h.device.type != "cuda" or (quant_state.nested and quant_state.state2.blocksize != 256):
+        return False
+    from ..backends import hip
+
+    E, N, K = (int(v) for v in quant_state.shape)
+    return hip.gemm_4bit_experts_combine_supported(h.dtype, E, N, K, quant_state.blocksize, S)
+
+
+def matmul_4bit_experts_combine(
+    h: torch.Tensor,
+    packed: torch.Tensor,
+    quant_state: F.QuantState,
+    expert_ids: torch.Tensor,
+    routing_weights: torch.Tensor,
+    bias: Optional[torch.Tensor] = None,
+):
+    """``y[t] = sum_s routing_weights[t, s] * (h[t, s] @ dequant(packed)[expert_ids[t, s]].T (+ bias[expert_ids[t, s]]))`` in ONE
+    launch - the down projection of a mixture-of-experts decode step with the slot sum as its epilogue. ``packed`` / ``quant_state``:
+    one ``quantize_4bit`` over the ``[E, N, K]`` stack; ``h``: ``[T, S, K]``; ``expert_ids`` and ``routing_weights``: ``[T, S]`` ON THE
+    DEVICE (int32 / int64; fp32 or ``h``'s dtype), read by the kernel only, so the call can be captured in a graph and replayed with
+    other values in the same buffers; ``bias``: optional ``[E, N]``. Returns ``[T, N]``: the sums are fp32 in a fixed order (a function
+    of ``K`` and the blocksize alone), the slots are added in ascending order, and the result is rounded ONCE. A slot whose id is
+    outside ``[0, E)`` contributes nothing whatever its weight; a token without a valid slot gives zeros. ``1 <= S <= 16``; a geometry
+    the kernel does not serve raises ``ValueError``. Inference only: there is no autograd formula."""
+    if quant_state is None:
+        raise ValueError("quant_state is required")
+    if len(quant_state.shape) != 3:
+        raise ValueError(f"matmul_4bit_experts_combine: quant_state.shape must be 3D [E, N, K], got {list(quant_state.shape)}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (h, bias, routing_weights)):
+        raise RuntimeError("matmul_4bit_experts_combine is inference only (no autograd formula): call it under torch.no_grad() "
+                           "or with detached inputs")
+    if h.shape[-1] != quant_state.shape[2]:
+        raise ValueError(
+            f"matmul_4bit_experts_combine: h inner dim ({h.shape[-1]}) must equal quant_state.shape[2] ({quant_state.shape[2]}); "
+            "expert tensors in [E, K, N] orientation (contraction over the unpacked dimension) are not supported")
+    if h.dim() != 3 or expert_ids.dim() != 2 or tuple(routing_weights.shape) != tuple(expert_ids.shape):
+        raise ValueError(f"matmul_4bit_experts_combine: h must be [T, S, K], expert_ids and routing_weights [T, S], got "
+                         f"{tuple(h.shape)}, {tuple(expert_ids.shape)} and {tuple(routing_weights.shape)}")
+    if h.device.type == "cuda" and not _combine_served(h, quant_state, int(expert_ids.shape[1])):
+        if quant_state.nested and quant_state.state2.blocksize != 256:
+            raise NotImplementedError("nested quantization with state2.blocksize != 256 is not supported")
+        raise ValueError(f"matmul_4bit_experts_combine: no kernel for quant_state.shape={list(quant_state.shape)}, "
+                         f"blocksize={quant_state.blocksize}, dtype={h.dtype}, S={int(expert_ids.shape[1])}")
+    packed = packed.view(-1, 1)
+    if h.device.type == "cuda" and not _is_compiling():
+        h, packed = _aligned16(h), _aligned16(packed)
+    op = torch.ops.bitsandbytes_amd.gemm_4bit_experts_combine.default
+    if not quant_state.nested:
+        return op(h, packed, quant_state.shape, quant_state.absmax, expert_ids, routing_weights, quant_state.blocksize,
+                  quant_state.quant_type, bias=bias)
+    return op(h, packed, quant_state.shape, quant_state.state2.absmax, expert_ids, routing_weights, quant_state.blocksize,
+              quant_state.quant_type, bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code,
+              absmax_offset=quant_state.offset)
+
+
 def moe_ffn_4bit(
     x: torch.Tensor,
     gate_up: torch.Tensor,
@@ -233,7 +290,7 @@ def moe_ffn_4bit(
     down_bias: Optional[torch.Tensor] = None,
     gated: str = "chunked",
 ):
-    """The expert FFN block of a mixture-of-experts decode step, two launches and one slot sum::
+    """The expert FFN block of a mixture-of-experts decode step, two launches and one slot sum (:func:`moe_ffn_4bit_fused`: two launches)::
 
         h[t, s] = silu(g) * u,  (g, u) = x[t] @ dequant(gate_up)[expert_ids[t, s]].T (+ gate_up_bias)      [T, S, I]
         y[t]    = sum_s routing_weights[t, s] * (h[t, s] @ dequant(down)[expert_ids[t, s]].T (+ down_bias))  [T, H]
@@ -242,13 +299,41 @@ def moe_ffn_4bit(
     ``"interleaved"`` (:func:`matmul_4bit_experts`); ``down`` / ``down_state``: the same over ``[E, H, I]``. ``x``: ``[T, H]`` (or
     ``[T, S, H]``); ``expert_ids`` and ``routing_weights``: ``[T, S]`` on the device, the weights fp32 or of ``x``'s dtype. Neither is
     read on the host, so the block can be captured in a graph and replayed with other ids and weights in the same buffers. A slot
-    whose id is outside ``[0, E)`` contributes zeros whatever its weight. Inference only."""
+    whose id is outside ``[0, E)`` contributes zeros whatever its weight. Inference only.
+
+    The down launch writes ``[T, S, H]``, each slot rounded to ``x``'s dtype, and torch's ``sum`` adds the slots."""
+    return _moe_ffn_4bit(x, gate_up, gate_up_state, down, down_state, expert_ids, routing_weights, gate_up_bias, down_bias, gated, "sum")
+
+
+def moe_ffn_4bit_fused(
+    x: torch.Tensor,
+    gate_up: torch.Tensor,
+    gate_up_state: F.QuantState,
+    down: torch.Tensor,
+    down_state: F.QuantState,
+    expert_ids: torch.Tensor,
+    routing_weights: torch.Tensor,
+    gate_up_bias: Optional[torch.Tensor] = None,
+    down_bias: Optional[torch.Tensor] = None,
+    gated: str = "chunked",
+):
+    """:func:`moe_ffn_4bit` in TWO launches: the down projection and the slot sum are one token-major launch
+    (:func:`matmul_4bit_experts_combine`) where that kernel serves the geometry - fp32 slot sum, one rounding, no ``[T, S, H]``
+    tensor, so in 16 bits not the bits of :func:`moe_ffn_4bit` -, and :func:`moe_ffn_4bit`'s path where it does not. Same arguments.
+    (``nn.parametrize.moe_ffn_4bit(..., combine="fused")`` is this function on parametrized expert tensors.)"""
+    return _moe_ffn_4bit(x, gate_up, gate_up_state, down, down_state, expert_ids, routing_weights, gate_up_bias, down_bias, gated, "fused")
+
+
+def _moe_ffn_4bit(x, gate_up, gate_up_state, down, down_state, expert_ids, routing_weights, gate_up_bias, down_bias, gated, combine):
     if gated not in ("chunked", "interleaved"):
         raise ValueError(f"moe_ffn_4bit: gated must be 'chunked' or 'interleaved', got {gated!r}")
     if expert_ids.dim() != 2 or tuple(routing_weights.shape) != tuple(expert_ids.shape):
         raise ValueError(f"moe_ffn_4bit: expert_ids and routing_weights must both be [T, S], got {tuple(expert_ids.shape)} and "
                          f"{tuple(routing_weights.shape)}")
     h = matmul_4bit_experts(x, gate_up, gate_up_state, expert_ids, bias=gate_up_bias, gated=gated)
+    if (combine == "fused" and h.numel() > 0 and routing_weights.dtype in (torch.float32, h.dtype)
+            and (down_bias is None or down_bias.dtype == h.dtype) and _combine_served(h, down_state, int(expert_ids.shape[1]))):
+        return matmul_4bit_experts_combine(h, down, down_state, expert_ids, routing_weights, bias=down_bias)
     y = matmul_4bit_experts(h, down, down_state, expert_ids, bias=down_bias, row_scale=routing_weights)
     return y[:, 0] if y.shape[1] == 1 else y.sum(dim=1)
 

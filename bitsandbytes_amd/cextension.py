@@ -65,6 +65,16 @@ class MoeTopkGroupedArgs(ct.Structure):
                 ("stream", ct.c_void_p)]
 
 
+class ExpertsCombineArgs(ct.Structure):
+    """``bnb_mi355x_gemm_4bit_experts_combine_args`` of include/bnb_mi355x.h; ``struct_bytes`` is ``ctypes.sizeof(ExpertsCombineArgs)``."""
+
+    _fields_ = [("struct_bytes", ct.c_size_t), ("dtype", ct.c_int), ("quant_type", ct.c_int), ("blocksize", ct.c_int),
+                ("index_bytes", ct.c_int), ("weights_dtype", ct.c_int), ("S", ct.c_int), ("E", ct.c_int), ("N", ct.c_int), ("K", ct.c_int),
+                ("T", ct.c_long), ("h", ct.c_void_p), ("B", ct.c_void_p), ("absmax", ct.c_void_p), ("absmax_8bit", ct.c_void_p),
+                ("absmax_code", ct.c_void_p), ("absmax_offset", ct.c_void_p), ("bias", ct.c_void_p), ("ids", ct.c_void_p),
+                ("weights", ct.c_void_p), ("out", ct.c_void_p), ("stream", ct.c_void_p)]
+
+
 def _declare(dll: ct.CDLL) -> None:
     def sig(names, argtypes, restype=None):
         for n in names:
@@ -108,6 +118,10 @@ def _declare(dll: ct.CDLL) -> None:
     sig(["bnb_mi355x_gemm_4bit_experts_ffn"],
         [_I32, _VOID_P, ct.c_long] + [_VOID_P] * 7 + [_I32, _VOID_P, _I32, _I32, _VOID_P, ct.c_long] + [_I32] * 6 + [_VOID_P])
     sig(["bnb_mi355x_gemm_4bit_experts_ffn_supported"], [_I32] * 6, _I32)
+    # (one argument block, passed with ctypes.byref(ExpertsCombineArgs(...)); non-zero: refused, nothing launched)
+    sig(["bnb_mi355x_gemm_4bit_experts_combine"], [_VOID_P], _I32)
+    sig(["bnb_mi355x_gemm_4bit_experts_combine_supported"], [_I32] * 6, _I32)  # (dtype, E, N, K, blocksize, S)
+    sig(["bnb_mi355x_gemm_4bit_experts_combine_plan"], [ct.c_long, _I32, _I32, _I32, _VOID_P], _I32)  # (T, S, N, K, out4: int32[4] on the host)
     # (dtype, A, B, absmax, out, bias, M, N = 2 F, K, blocksize, quant_type, stream)
     sig(["bnb_mi355x_gemm_4bit_gated"], [_I32] + [_VOID_P] * 5 + [_I32] * 5 + [_VOID_P])
     sig(["bnb_mi355x_gemm_4bit_gated_supported"], [_I32] * 5, _I32)
@@ -197,6 +211,8 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_gemm_4bit_grouped", "bnb_mi355x_gemm_4bit_grouped_route",
        "bnb_mi355x_gemm_4bit_experts", "bnb_mi355x_gemm_4bit_experts_supported",
        "bnb_mi355x_gemm_4bit_experts_ffn", "bnb_mi355x_gemm_4bit_experts_ffn_supported",
+       "bnb_mi355x_gemm_4bit_experts_combine", "bnb_mi355x_gemm_4bit_experts_combine_supported",
+       "bnb_mi355x_gemm_4bit_experts_combine_plan",
        "bnb_mi355x_gemm_4bit_gated", "bnb_mi355x_gemm_4bit_gated_supported",
        "bnb_mi355x_gemm_4bit_lora", "bnb_mi355x_gemm_4bit_lora_supported",
        "bnb_mi355x_gemm_4bit_lora_ids", "bnb_mi355x_gemm_4bit_lora_ids_supported",

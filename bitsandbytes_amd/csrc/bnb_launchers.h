@@ -157,6 +157,13 @@ void gemm_4bit_experts_ffn(int dtype, const void* A, long a_slot_stride, const u
                            const void* row_scale, int row_scale_dtype, int gated, void* out, long P, int S, int E, int N, int K, int blocksize,
                            int quant_type, hipStream_t stream);
 
+// gemm4_experts_combine.hip (token-major MoE down projection, the routing-weighted slot sum in the launch)
+bool gemm_4bit_experts_combine_supported(int dtype, long E, long N, long K, int blocksize, int S);
+bool gemm_4bit_experts_combine_plan(long T, int S, int N, int K, int* out4);
+bool gemm_4bit_experts_combine(int dtype, const void* h, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                               const float* absmax_offset, const void* bias, const void* ids, int index_bytes, const void* w, int w_dtype,
+                               void* out, long T, int S, int E, int N, int K, int blocksize, int quant_type, hipStream_t stream);
+
 // lora_shrink.hip
 bool lora_shrink_supported(int dtype, int M, int R, int K);
 bool lora_shrink(int dtype, const void* x, const void* lora_a, void* t, int M, int R, int K, const int* splits, int n_splits, hipStream_t stream);

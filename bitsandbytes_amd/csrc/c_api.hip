@@ -263,6 +263,28 @@ void bnb_mi355x_gemm_4bit_experts_ffn(int dtype, const void* A, long a_slot_stri
 int bnb_mi355x_gemm_4bit_experts_ffn_supported(int dtype, int E, int N, int K, int blocksize, int gated) {
     return gemm_4bit_experts_ffn_supported(dtype, E, N, K, blocksize, gated) ? 1 : 0;
 }
+// (one argument block, as for bnb_mi355x_moe_topk: non-zero = refused, nothing launched, the process goes on)
+int bnb_mi355x_gemm_4bit_experts_combine(const bnb_mi355x_gemm_4bit_experts_combine_args* args) {
+    if (args == nullptr || args->struct_bytes != sizeof(bnb_mi355x_gemm_4bit_experts_combine_args)) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_experts_combine: struct_bytes is %zu, this library's bnb_mi355x_gemm_4bit_experts_combine_args has %zu\n",
+                args == nullptr ? static_cast<size_t>(0) : args->struct_bytes, sizeof(bnb_mi355x_gemm_4bit_experts_combine_args));
+        return 1;
+    }
+    if (!gemm_4bit_experts_combine(args->dtype, args->h, args->B, args->absmax, args->absmax_8bit, args->absmax_code, args->absmax_offset, args->bias,
+                                   args->ids, args->index_bytes, args->weights, args->weights_dtype, args->out, args->T, args->S, args->E, args->N,
+                                   args->K, args->blocksize, args->quant_type, S(args->stream))) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_experts_combine: no kernel for dtype %d, T=%ld, S=%d, E=%d, N=%d, K=%d, blocksize=%d, quant_type %d, index_bytes %d, weights_dtype %d (1 <= S <= 16, K <= 65536, blocksize a power of two >= 32 dividing K, FP4 / NF4, weights fp32 or of dtype; h, B, absmax, ids, weights, out not NULL; h and B 16-byte aligned)\n",
+                args->dtype, args->T, args->S, args->E, args->N, args->K, args->blocksize, args->quant_type, args->index_bytes, args->weights_dtype);
+        return 1;
+    }
+    return 0;
+}
+int bnb_mi355x_gemm_4bit_experts_combine_plan(long T, int slots, int N, int K, int* out4) {
+    return gemm_4bit_experts_combine_plan(T, slots, N, K, out4) ? 1 : 0;
+}
+int bnb_mi355x_gemm_4bit_experts_combine_supported(int dtype, int E, int N, int K, int blocksize, int slots) {
+    return gemm_4bit_experts_combine_supported(dtype, E, N, K, blocksize, slots) ? 1 : 0;
+}
 
 // ------------------------------------------------------------------ gated gemm_4bit (dense FFN: silu(gate) * up as the epilogue)
 void bnb_mi355x_gemm_4bit_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N,

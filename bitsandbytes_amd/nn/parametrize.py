@@ -17,6 +17,7 @@ import torch.nn.utils.parametrize as P
 from .. import functional as F
 from ..autograd._functions import matmul_4bit_experts as _matmul_4bit_experts
 from ..autograd._functions import moe_ffn_4bit as _moe_ffn_4bit
+from ..autograd._functions import moe_ffn_4bit_fused as _moe_ffn_4bit_fused
 
 
 class Bnb4bitParametrization(nn.Module):
@@ -138,14 +139,17 @@ def matmul_4bit_experts(module: nn.Module, param_name: str, x: torch.Tensor, exp
 
 def moe_ffn_4bit(module: nn.Module, gate_up_name: str, down_name: str, x: torch.Tensor, expert_ids: torch.Tensor,
                  routing_weights: torch.Tensor, gate_up_bias: Optional[torch.Tensor] = None,
-                 down_bias: Optional[torch.Tensor] = None, gated: str = "chunked") -> torch.Tensor:
+                 down_bias: Optional[torch.Tensor] = None, gated: str = "chunked", combine: str = "sum") -> torch.Tensor:
     """The gated-SiLU expert FFN block of a decode step on parametrized ``[E, 2 I, H]`` / ``[E, H, I]`` expert tensors, from the
     packed bytes: two launches and one slot sum (:func:`bitsandbytes_amd.moe_ffn_4bit`; ``x`` ``[T, H]``, ``expert_ids`` and
     ``routing_weights`` ``[T, S]`` on the device; returns ``[T, H]``). Where the kernel does not serve one of the two geometries the
     block is composed of :func:`matmul_4bit_experts` of this module and torch's ``silu``, ``*`` and ``sum`` - also without looking at
-    the ids or the weights on the host. Inference only."""
+    the ids or the weights on the host. ``combine="fused"``: the down projection and the slot sum as one launch where the library
+    serves it (:func:`bitsandbytes_amd.moe_ffn_4bit_fused`). Inference only."""
     if gated not in ("chunked", "interleaved"):
         raise ValueError(f"moe_ffn_4bit: gated must be 'chunked' or 'interleaved', got {gated!r}")
+    if combine not in ("sum", "fused"):
+        raise ValueError(f"moe_ffn_4bit: combine must be 'sum' or 'fused', got {combine!r}")
     gu_packed, gu_state = _expert_state(module, gate_up_name, "moe_ffn_4bit")
     dn_packed, dn_state = _expert_state(module, down_name, "moe_ffn_4bit")
     if expert_ids.dim() != 2 or tuple(routing_weights.shape) != tuple(expert_ids.shape):
@@ -162,8 +166,9 @@ def moe_ffn_4bit(module: nn.Module, gate_up_name: str, down_name: str, x: torch.
 
     if (x.is_cuda and routing_weights.dtype in (torch.float32, x.dtype) and served(gu_packed, gu_state, gated)
             and served(dn_packed, dn_state, "none")):
-        return _moe_ffn_4bit(x, gu_packed.data, gu_state, dn_packed.data, dn_state, expert_ids, routing_weights,
-                             gate_up_bias=gate_up_bias, down_bias=down_bias, gated=gated)
+        block = _moe_ffn_4bit_fused if combine == "fused" else _moe_ffn_4bit
+        return block(x, gu_packed.data, gu_state, dn_packed.data, dn_state, expert_ids, routing_weights,
+                     gate_up_bias=gate_up_bias, down_bias=down_bias, gated=gated)
     with torch.no_grad():
         h = matmul_4bit_experts(module, gate_up_name, x, expert_ids, bias=gate_up_bias)
         g, u = (h[..., 0::2], h[..., 1::2]) if gated == "interleaved" else h.chunk(2, dim=-1)

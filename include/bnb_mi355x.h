@@ -155,7 +155,7 @@ int bnb_mi355x_gemm_4bit_fused_max_m(int dtype, int N, int K, int blocksize, int
  * kernel (gemv4_stream_kernel), 2 generic scalar kernel (odd shapes), 3 register-transposed MFMA kernel (gemm4_mfma_rt_kernel),
  * 4 producer/consumer MFMA kernel (gemm4_mfma_pc_kernel), 6 K-quarter MFMA kernel (gemm4_mfma_kq_kernel),
  * 7 streaming MFMA kernel (gemm4_mfma_sm_kernel: 2 ... 16 rows, one persistent workgroup per CU), 9 expert-indexed kernel
- * (gemm4_experts_kernel: bnb_mi355x_gemm_4bit_experts). Debug / test query:
+ * (gemm4_experts_kernel: bnb_mi355x_gemm_4bit_experts), 10 token-major expert kernel (bnb_mi355x_gemm_4bit_experts_combine). Debug / test query:
  * a test that forces a kernel with bnb_mi355x_set_tuning asserts here that it ran (a geometry the forced kernel does not
  * serve falls back to another family by design). */
 int bnb_mi355x_last_gemm_kernel(void);
@@ -189,6 +189,43 @@ int bnb_mi355x_gemm_4bit_experts_supported(int dtype, int E, int N, int K, int b
  * expert. bnb_mi355x_gemm_4bit_experts_ffn_supported: the predicate above, and N even when gated != 0 (pure host logic). */
 void bnb_mi355x_gemm_4bit_experts_ffn(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax_8bit, const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes, const void* row_scale, int row_scale_dtype, int gated, void* out, long P, int S, int E, int N, int K, int blocksize, int quant_type, bnb_stream_t stream);
 int bnb_mi355x_gemm_4bit_experts_ffn_supported(int dtype, int E, int N, int K, int blocksize, int gated);
+/* Token-major MoE down projection with the routing-weighted slot sum in the launch (family 10, gemm4_experts_combine_kernel):
+ *   out[t, 0:N] = T( sum over s < S with 0 <= ids[t, s] < E, ascending:  w[t, s] * ( h[t, s, :] * dequant(B[ids[t, s]])^T + bias[ids[t, s], 0:N] ) )
+ * B and the statistics as for bnb_mi355x_gemm_4bit_experts; h [T, S, K] of dtype, ids [T, S] (index_bytes 4 / 8) and weights [T, S]
+ * (fp32: weights_dtype 0, or weights_dtype == dtype) on the DEVICE, read by the kernel only; out [T, N]. The grid is (N tile, token):
+ * all slots of a token meet in one workgroup, so the sum is in fp32 in ascending slot order with ONE rounding - no [T, S, N] tensor,
+ * no workspace, no memset, no atomics; the order of every fp32 addition depends on (K, blocksize) alone. A slot whose id is outside
+ * [0, E) contributes nothing and its weight is never multiplied in; a token without a valid slot gets zeros. 1 <= S <= 16, K <= 65536,
+ * blocksize a power of two >= 32 dividing K, h and B 16-byte aligned. One pointer to an argument block, the convention of
+ * bnb_mi355x_moe_topk: struct_bytes = sizeof of the block; returns 0 after the launch (T == 0: 0, nothing launched); a call outside
+ * the preconditions - where bnb_mi355x_gemm_4bit_experts_combine_supported (pure host logic) answers 0, a NULL or misaligned pointer -
+ * prints one line on stderr, launches nothing, returns non-zero and does NOT end the process. */
+typedef struct bnb_mi355x_gemm_4bit_experts_combine_args {
+    size_t struct_bytes;            /* sizeof of this struct as the caller was compiled */
+    int dtype;                      /* 0 fp32, 1 fp16, 2 bf16: h, bias, out */
+    int quant_type, blocksize;
+    int index_bytes;                /* 4 / 8: ids int32 / int64 */
+    int weights_dtype;              /* 0 fp32, or dtype */
+    int S, E, N, K;
+    long T;
+    const void* h;                  /* [T, S, K] */
+    const uint8_t* B;               /* [E, N, K] packed */
+    const float* absmax;
+    const uint8_t* absmax_8bit;     /* nested statistics, or NULL */
+    const float* absmax_code;
+    const float* absmax_offset;
+    const void* bias;               /* [E, N] or NULL */
+    const void* ids;                /* [T, S] */
+    const void* weights;            /* [T, S] */
+    void* out;                      /* [T, N] */
+    bnb_stream_t stream;
+} bnb_mi355x_gemm_4bit_experts_combine_args;
+int bnb_mi355x_gemm_4bit_experts_combine(const bnb_mi355x_gemm_4bit_experts_combine_args* args);
+int bnb_mi355x_gemm_4bit_experts_combine_supported(int dtype, int E, int N, int K, int blocksize, int S);
+/* Debug / test query (host logic and the CU count of the current device or bnb_mi355x_set_cu_count's override): the launch plan of
+ * the call above for T tokens - out4 = {L lanes per row, Q rounds, segments, rows per workgroup}. Returns 1, or 0 outside
+ * T >= 1, 1 <= S <= 16, N >= 1, K a multiple of 32 up to 65536. */
+int bnb_mi355x_gemm_4bit_experts_combine_plan(long T, int S, int N, int K, int* out4);
 /* Dense gated-SiLU FFN: the fused matmul over ONE interleaved matrix B [N = 2 F, K] - gate row i at row 2 i, up row i at row 2 i + 1;
  * bias, if given, [N] in the same layout - with silu(gate) * up as its epilogue. A is [M, K], out is [M, F]:
  *     g = T(acc_g + bias_g), u = T(acc_u + bias_u), out[m, i] = T(float(T(silu(g))) * float(u)),  silu(g) = g / (1 + expf(-g)) in fp32

@@ -7,9 +7,13 @@ Method (tools/bench_experts.py): every leg is a hipGraph of >= 64 blocks that ro
 that the weights selected by one pass over the rotation exceed the 256 MiB Infinity Cache; HIP events around `reps` replays
 (regions >= 10 ms); the legs alternate inside one process, order reversed every round; median and min ... max of the rounds. Legs:
   fused    moe_ffn_4bit(x, gate_up, ..., down, ..., ids, w)                                                    3 launches (2 at S = 1)
+  fused2   moe_ffn_4bit_fused(...): the down projection       and the slot sum as the token-major launch     2 launches
   parent   matmul_4bit_experts -> chunk / F.silu / * -> matmul_4bit_experts -> * w -> sum                       6 launches
   gated    the first launch of `fused` alone, writing [T, S, I]
   plain    the first launch of `parent` alone, writing [T, S, 2I]
+  down+sum the down stage of `fused` alone on a random h [T, S, I]: the row-scale launch and torch's sum           2 launches
+  combine  the down stage of `fused2` alone: matmul_4bit_experts_combine                                           1 launch
+A shape whose rotation does not fit in memory is skipped with a line that says so.
 The table is written to profiles/moe_ffn_bench.txt (--out), replacing the file.
     python tools/bench_moe_ffn.py [--rounds 5] [--quick] [--out profiles/moe_ffn_bench.txt]"""
 import argparse
@@ -31,11 +35,14 @@ from tools.bench_experts import BS, CACHE_BYTES, capture, timed  # noqa: E402
 SHAPES = [
     ("Mixtral 8 x 28672 x 4096 + 8 x 4096 x 14336", 8, 14336, 4096, 2, (1, 4, 16)),
     ("128 x 1536 x 2048 + 128 x 2048 x 768", 128, 768, 2048, 8, (1, 4, 8)),
+    ("256 x 4096 x 7168 + 256 x 7168 x 2048", 256, 2048, 7168, 8, (1, 4, 8)),
 ]
 
 
 def quantized(E, N, K, gen):
-    W = (torch.randn(E, N, K, device="cuda", generator=gen) / K ** 0.5).bfloat16()
+    W = torch.empty(E, N, K, device="cuda", dtype=torch.bfloat16)
+    for e in range(E):   # (expert by expert: no fp32 copy of a whole 256-expert stack)
+        W[e] = torch.randn(N, K, device="cuda", generator=gen) / K ** 0.5
     packed, st = F.quantize_4bit(W, blocksize=BS, quant_type="nf4")
     del W
     return packed, st
@@ -58,17 +65,25 @@ def main():
     say(f"# us per block / per launch: median (min ... max) of {args.rounds} rounds; NF4, blocksize {BS}, plain statistics, bf16; "
         "x is [T, H], routing weights fp32")
     say(f"{'shape':>44s} {'T':>2s} {'S':>2s} {'fused block':>24s} {'parent block':>24s} {'saved':>7s} {'ratio':>6s} "
-        f"{'gated launch':>24s} {'plain launch':>24s} {'gated-plain':>11s}")
+        f"{'gated launch':>24s} {'plain launch':>24s} {'gated-plain':>11s} {'fused2 block':>24s} {'down+sum':>24s} {'combine':>24s} "
+        f"{'down saved':>10s}")
     gen = torch.Generator(device="cuda").manual_seed(0)
     for label, E, I, H, S, Ts in SHAPES:
         per_block = (2 * I * H + H * I) // 2 + (2 * I * H + H * I) // BS * 4     # one expert's bytes of both stacks
         L = max(2, min(48, math.ceil(1.25 * CACHE_BYTES / (min(S, E) * per_block))))
-        stacks = [quantized(E, 2 * I, H, gen) + quantized(E, H, I, gen) for _ in range(L)]
+        try:
+            stacks = [quantized(E, 2 * I, H, gen) + quantized(E, H, I, gen) for _ in range(L)]
+        except torch.OutOfMemoryError:
+            say(f"{label:>44s}: skipped, a rotation of {L} stack pairs does not fit in memory")
+            stacks = None
+            torch.cuda.empty_cache()
+            continue
         calls = L * math.ceil(64 / L)
         for T in (Ts[:1] if args.quick else Ts):
             x = torch.randn(T, H, device="cuda", generator=gen).bfloat16()
             ids = torch.stack([torch.randperm(E, device="cuda", generator=gen)[:S] for _ in range(T)]).to(torch.int32)
             w = torch.softmax(torch.randn(T, S, device="cuda", generator=gen), dim=-1)
+            h = torch.randn(T, S, I, device="cuda", generator=gen).bfloat16()
 
             def fused():
                 for c in range(calls):
@@ -92,7 +107,22 @@ def main():
                     gu, gs, _, _ = stacks[c % L]
                     bnb.matmul_4bit_experts(x, gu, gs, ids)
 
-            legs = [fused, parent, gated, plain]
+            def fused2():
+                for c in range(calls):
+                    gu, gs, dn, ds = stacks[c % L]
+                    bnb.moe_ffn_4bit_fused(x, gu, gs, dn, ds, ids, w)
+
+            def down_sum():
+                for c in range(calls):
+                    _, _, dn, ds = stacks[c % L]
+                    bnb.matmul_4bit_experts(h, dn, ds, ids, row_scale=w).sum(dim=1)
+
+            def combine():
+                for c in range(calls):
+                    _, _, dn, ds = stacks[c % L]
+                    bnb.matmul_4bit_experts_combine(h, dn, ds, ids, w)
+
+            legs = [fused, parent, gated, plain, fused2, down_sum, combine]
             graphs = [capture(fn) for fn in legs]
             samples = [[] for _ in legs]
             reps = [max(2, int(10000.0 / (timed(g, calls, 1) * calls)) + 1) for g in graphs]
@@ -103,7 +133,7 @@ def main():
             cols = [f"{statistics.median(s):8.2f} ({min(s):.2f}...{max(s):.2f})" for s in samples]
             med = [statistics.median(s) for s in samples]
             say(f"{label:>44s} {T:>2d} {S:>2d} {cols[0]:>24s} {cols[1]:>24s} {med[1] - med[0]:7.2f} {med[1] / med[0]:5.2f}x "
-                f"{cols[2]:>24s} {cols[3]:>24s} {med[2] - med[3]:+11.2f}")
+                f"{cols[2]:>24s} {cols[3]:>24s} {med[2] - med[3]:+11.2f} {cols[4]:>24s} {cols[5]:>24s} {cols[6]:>24s} {med[5] - med[6]:10.2f}")
             del graphs
         del stacks
         torch.cuda.empty_cache()
