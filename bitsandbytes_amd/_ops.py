@@ -485,6 +485,36 @@ def _(A, B, shapeB: Sequence[int], absmax, ids, weights, blocksize: int, quant_t
     return torch.empty((ids.shape[0], N), dtype=A.dtype, device=A.device)
 
 
+# ---------------------------------------------------------------------------------------------- gemm_4bit_experts_gate_up
+# The gate / up projection of an expert FFN with gated SiLU in the launch (token-major grid): B is [E, 2 I, K] in the chunked or the
+# interleaved layout of gemm_4bit_experts_ffn, A [T, K] - ONE activation row per token, shared by its S slots -, ids [T, S] on the
+# device and read there only; out[t, s, :] = silu(g) * u [T, S, I] with the gated arithmetic of gemm_4bit_experts_ffn; a slot with an
+# id outside [0, E) gives zeros. 1 <= S <= 16. Inference only.
+torch.library.define(
+    "bitsandbytes_amd::gemm_4bit_experts_gate_up",
+    "(Tensor A, Tensor B, int[] shapeB, Tensor absmax, Tensor ids, int blocksize, str quant_type, Tensor? bias=None, "
+    "Tensor? absmax_8bit=None, Tensor? absmax_code=None, Tensor? absmax_offset=None, str gated=\"chunked\") -> Tensor",
+)
+
+
+def _check_gemm_4bit_experts_gate_up(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code, absmax_offset,
+                                     gated):
+    """The checks of gemm_4bit_experts and those of the shared activation row and the gated layout; returns (E, N, K)."""
+    E, N, K, _ = _check_gemm_4bit_experts(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code, absmax_offset)
+    torch._check(A.dim() == 2 and ids.dim() == 2, lambda: f"A must be [T, K] and ids [T, S], got {A.dim()} and {ids.dim()} dims")
+    torch._check(gated in ("chunked", "interleaved"), lambda: f"gated must be 'chunked' or 'interleaved', got {gated!r}")
+    torch._check(N % 2 == 0, lambda: f"a gated call needs an even number of weight rows per expert (gate + up), got N = {N}")
+    return E, N, K
+
+
+@register_fake("bitsandbytes_amd::gemm_4bit_experts_gate_up")
+def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str, bias=None, absmax_8bit=None, absmax_code=None,
+      absmax_offset=None, gated: str = "chunked"):
+    _, N, _ = _check_gemm_4bit_experts_gate_up(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code,
+                                               absmax_offset, gated)
+    return torch.empty((*ids.shape, N // 2), dtype=A.dtype, device=A.device)
+
+
 # ---------------------------------------------------------------------------------------------- gemm_4bit_gated
 # Not a reference op: the gate / up projections of a dense gated-SiLU FFN (Llama, Mistral, Qwen, Phi-3) with the activation as the
 # matmul's epilogue. B is the quantize_4bit result of ONE interleaved [2 F, K] matrix - gate row i at row 2 i, up row i at row 2 i + 1

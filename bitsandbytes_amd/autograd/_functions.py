@@ -278,6 +278,67 @@ def matmul_4bit_experts_combine(
               absmax_offset=quant_state.offset)
 
 
+def _gate_up_served(x: torch.Tensor, quant_state: F.QuantState, S: int, gated: str) -> bool:
+    """Whether the token-major launch serves this gate / up projection - decided from shapes and dtypes only."""
+    if x.device.type != "cuda" or x.dim() != 2 or (quant_state.nested and quant_state.state2.blocksize != 256):
+        return False
+    from ..backends import hip
+
+    E, N, K = (int(v) for v in quant_state.shape)
+    return hip.gemm_4bit_experts_gate_up_supported(x.dtype, E, N, K, quant_state.blocksize, S, gated)
+
+
+def matmul_4bit_experts_gate_up(
+    x: torch.Tensor,
+    packed: torch.Tensor,
+    quant_state: F.QuantState,
+    expert_ids: torch.Tensor,
+    bias: Optional[torch.Tensor] = None,
+    gated: str = "chunked",
+):
+    """``h[t, s] = silu(g) * u`` with ``(g, u) = x[t] @ dequant(packed)[expert_ids[t, s]].T (+ bias[expert_ids[t, s]])`` in ONE
+    token-major launch - the gate / up projection of a mixture-of-experts decode step. ``packed`` / ``quant_state``: one
+    ``quantize_4bit`` over the ``[E, 2 I, K]`` stack, ``gated="chunked"`` (gate rows ``[0, I)``, up rows ``[I, 2 I)``) or
+    ``"interleaved"`` (gate row ``2 i``, up row ``2 i + 1``); ``x``: ``[T, K]`` - one activation row per token, which a workgroup
+    loads once for all its slots (``[T, S, K]`` activations: :func:`matmul_4bit_experts`); ``expert_ids``: ``[T, S]`` int32 / int64
+    ON THE DEVICE, read by the kernel only, so the call can be captured in a graph and replayed with other ids in the same buffer;
+    ``bias``: optional ``[E, 2 I]`` in the stack's layout. Returns ``[T, S, I]`` with the gated arithmetic of
+    ``matmul_4bit_experts(..., gated=)`` (``F.silu(g) * u`` on ``g``, ``u`` rounded to ``x``'s dtype); the fp32 sums behind ``g`` and
+    ``u`` run in a fixed order, a function of ``K`` and the blocksize alone. A slot whose id is outside ``[0, E)`` gives a row of
+    zeros. ``1 <= S <= 16``; a geometry the kernel does not serve raises ``ValueError``. Inference only: there is no autograd formula."""
+    if quant_state is None:
+        raise ValueError("quant_state is required")
+    if len(quant_state.shape) != 3:
+        raise ValueError(f"matmul_4bit_experts_gate_up: quant_state.shape must be 3D [E, 2 I, K], got {list(quant_state.shape)}")
+    if gated not in ("chunked", "interleaved"):
+        raise ValueError(f"matmul_4bit_experts_gate_up: gated must be 'chunked' or 'interleaved', got {gated!r}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, bias)):
+        raise RuntimeError("matmul_4bit_experts_gate_up is inference only (no autograd formula): call it under torch.no_grad() "
+                           "or with detached inputs")
+    if x.shape[-1] != quant_state.shape[2]:
+        raise ValueError(
+            f"matmul_4bit_experts_gate_up: x inner dim ({x.shape[-1]}) must equal quant_state.shape[2] ({quant_state.shape[2]}); "
+            "expert tensors in [E, K, N] orientation (contraction over the unpacked dimension) are not supported")
+    if x.dim() != 2 or expert_ids.dim() != 2:
+        raise ValueError(f"matmul_4bit_experts_gate_up: x must be [T, K] and expert_ids [T, S], got {tuple(x.shape)} and "
+                         f"{tuple(expert_ids.shape)}")
+    if x.device.type == "cuda" and not _gate_up_served(x, quant_state, int(expert_ids.shape[1]), gated):
+        if quant_state.nested and quant_state.state2.blocksize != 256:
+            raise NotImplementedError("nested quantization with state2.blocksize != 256 is not supported")
+        raise ValueError(f"matmul_4bit_experts_gate_up: no kernel for quant_state.shape={list(quant_state.shape)}, "
+                         f"blocksize={quant_state.blocksize}, dtype={x.dtype}, S={int(expert_ids.shape[1])}")
+    packed = packed.view(-1, 1)
+    if x.device.type == "cuda" and not _is_compiling():
+        x, packed = _aligned16(x), _aligned16(packed)
+    op = torch.ops.bitsandbytes_amd.gemm_4bit_experts_gate_up.default
+    if not quant_state.nested:
+        return op(x, packed, quant_state.shape, quant_state.absmax, expert_ids, quant_state.blocksize, quant_state.quant_type,
+                  bias=bias, gated=gated)
+    return op(x, packed, quant_state.shape, quant_state.state2.absmax, expert_ids, quant_state.blocksize, quant_state.quant_type,
+              bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code, absmax_offset=quant_state.offset,
+              gated=gated)
+
+
 def moe_ffn_4bit(
     x: torch.Tensor,
     gate_up: torch.Tensor,
@@ -324,14 +385,48 @@ def moe_ffn_4bit_fused(
     return _moe_ffn_4bit(x, gate_up, gate_up_state, down, down_state, expert_ids, routing_weights, gate_up_bias, down_bias, gated, "fused")
 
 
+def moe_ffn_4bit_tokens(
+    x: torch.Tensor,
+    gate_up: torch.Tensor,
+    gate_up_state: F.QuantState,
+    down: torch.Tensor,
+    down_state: F.QuantState,
+    expert_ids: torch.Tensor,
+    routing_weights: torch.Tensor,
+    gate_up_bias: Optional[torch.Tensor] = None,
+    down_bias: Optional[torch.Tensor] = None,
+    gated: str = "chunked",
+):
+    """:func:`moe_ffn_4bit` with BOTH stages token-major, two launches: :func:`matmul_4bit_experts_gate_up`, then
+    :func:`matmul_4bit_experts_combine`. Same arguments. Each stage on its own takes what :func:`moe_ffn_4bit_fused` does where its
+    kernel declines (``x`` given as ``[T, S, H]``, ``S > 16``, ...). The gate / up launch applies the gated arithmetic of the expert-major
+    launch to fp32 sums added in another order (a function of ``K`` and the blocksize alone), so the block's result is that of
+    :func:`moe_ffn_4bit_fused` up to last-bit roundings of ``g`` and ``u`` (about 3 in 10 000 elements of ``h`` on the timed stacks). (``nn.parametrize.moe_ffn_4bit(..., combine="tokens")`` is this function on
+    parametrized expert tensors.)
+
+    Which block for which stack (measured on MI355X: bf16, NF4, blocksize 64, plain statistics; ``DESIGN.md`` §3.11b). The
+    token-major grid streams an expert's rows once per (token, slot) pair, so this is the block for many experts and single-digit
+    ``T``, where almost no two pairs share an expert: at 128 x 1536 x 2048 and 256 x 4096 x 7168 gate / up stacks with ``S = 8`` it is
+    1.5 - 2.8 x faster than :func:`moe_ffn_4bit_fused` at ``T`` = 1 ... 8 (23.5 against 45.2 us and 68.9 against 190.8 us at ``T = 1``).
+    On Mixtral's 8 experts (``S = 2``) it is ahead at ``T = 1`` only (61.8 against 64.7 us); at ``T = 4`` pick
+    :func:`moe_ffn_4bit_fused` or :func:`moe_ffn_4bit` (193 against 172 us), at ``T = 16`` :func:`moe_ffn_4bit` (709 against 387 us):
+    there tokens share experts and the expert-major grid reads each expert once. Other dtypes, nested statistics and other ``S``
+    are served but were not timed."""
+    return _moe_ffn_4bit(x, gate_up, gate_up_state, down, down_state, expert_ids, routing_weights, gate_up_bias, down_bias, gated, "tokens")
+
+
 def _moe_ffn_4bit(x, gate_up, gate_up_state, down, down_state, expert_ids, routing_weights, gate_up_bias, down_bias, gated, combine):
     if gated not in ("chunked", "interleaved"):
         raise ValueError(f"moe_ffn_4bit: gated must be 'chunked' or 'interleaved', got {gated!r}")
     if expert_ids.dim() != 2 or tuple(routing_weights.shape) != tuple(expert_ids.shape):
         raise ValueError(f"moe_ffn_4bit: expert_ids and routing_weights must both be [T, S], got {tuple(expert_ids.shape)} and "
                          f"{tuple(routing_weights.shape)}")
-    h = matmul_4bit_experts(x, gate_up, gate_up_state, expert_ids, bias=gate_up_bias, gated=gated)
-    if (combine == "fused" and h.numel() > 0 and routing_weights.dtype in (torch.float32, h.dtype)
+    if (combine == "tokens" and expert_ids.shape[0] > 0 and (gate_up_bias is None or gate_up_bias.dtype == x.dtype)
+            and _gate_up_served(x, gate_up_state, int(expert_ids.shape[1]), gated)):
+        h = matmul_4bit_experts_gate_up(x, gate_up, gate_up_state, expert_ids, bias=gate_up_bias, gated=gated)
+    else:
+        h = matmul_4bit_experts(x, gate_up, gate_up_state, expert_ids, bias=gate_up_bias, gated=gated)
+    if (combine != "sum" and h.numel() > 0 and routing_weights.dtype in (torch.float32, h.dtype)
             and (down_bias is None or down_bias.dtype == h.dtype) and _combine_served(h, down_state, int(expert_ids.shape[1]))):
         return matmul_4bit_experts_combine(h, down, down_state, expert_ids, routing_weights, bias=down_bias)
     y = matmul_4bit_experts(h, down, down_state, expert_ids, bias=down_bias, row_scale=routing_weights)

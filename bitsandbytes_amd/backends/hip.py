@@ -21,7 +21,7 @@ from warnings import warn
 
 import torch
 
-from .._ops import (GATED_CODES, MOE_GROUP_SCORE_CODES, MOE_SCORING_CODES, _check_moe_topk_grouped, _check_gemm_4bit_experts, _check_gemm_4bit_experts_combine, _check_gemm_4bit_experts_ffn, _check_gemm_4bit_gated,
+from .._ops import (GATED_CODES, MOE_GROUP_SCORE_CODES, MOE_SCORING_CODES, _check_moe_topk_grouped, _check_gemm_4bit_experts, _check_gemm_4bit_experts_combine, _check_gemm_4bit_experts_gate_up, _check_gemm_4bit_experts_ffn, _check_gemm_4bit_gated,
                      _check_gemm_4bit_lora, _check_gemm_4bit_lora_ids,
                      _check_lora_shrink, _check_lora_shrink_ids, _check_moe_topk, register_kernel)
 from ..cextension import lib
@@ -589,6 +589,50 @@ def _(A, B, shapeB: Sequence[int], absmax, ids, weights, blocksize: int, quant_t
                                   _ptr(offset32), _ptr(bias), ids.data_ptr(), weights.data_ptr(), out.data_ptr(), _stream(A))
         if lib.bnb_mi355x_gemm_4bit_experts_combine(ct.byref(args)) != 0:
             raise ValueError("gemm_4bit_experts_combine: the library refused the call (its message is on stderr)")
+    return out
+
+
+# ------------------------------------------------------------------------------------------ gemm_4bit_experts_gate_up
+def gemm_4bit_experts_gate_up_supported(dtype: torch.dtype, E: int, N: int, K: int, blocksize: int, S: int, gated: str) -> bool:
+    """Whether the token-major kernel serves this gate / up projection (N = 2 I weight rows per expert) with S slots per token (pure
+    host logic of the library)."""
+    if dtype not in _DT_CODE or gated not in GATED_CODES or max(E, N, K, S) >= 2**31 or min(E, N, K) < 1:
+        return False
+    return bool(lib.bnb_mi355x_gemm_4bit_experts_gate_up_supported(_DT_CODE[dtype], E, N, K, blocksize, S, GATED_CODES[gated]))
+
+
+@register_kernel("bitsandbytes_amd::gemm_4bit_experts_gate_up", "cuda")
+def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str, bias=None, absmax_8bit=None, absmax_code=None,
+      absmax_offset=None, gated: str = "chunked"):
+    """One launch of gemm4_experts_gate_up_kernel; ids stay on the device (nothing here reads their values)."""
+    E, N, K = _check_gemm_4bit_experts_gate_up(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code,
+                                               absmax_offset, gated)
+    T, S = ids.shape
+    if not gemm_4bit_experts_gate_up_supported(A.dtype, E, N, K, blocksize, S, gated):
+        raise ValueError(f"gemm_4bit_experts_gate_up: no kernel for E={E}, N={N}, K={K}, blocksize={blocksize}, dtype={A.dtype}, S={S}")
+    out = torch.empty((T, S, N // 2), dtype=A.dtype, device=A.device)
+    if T == 0:
+        return out
+    A = A.contiguous()
+    B = B.contiguous()
+    ids = ids.contiguous()
+    if A.data_ptr() % 16 or B.data_ptr() % 16:
+        raise ValueError("gemm_4bit_experts_gate_up: A and B must be 16-byte aligned")
+    for t in (absmax, bias, absmax_8bit, absmax_code, absmax_offset):
+        if t is not None and t.device != A.device:
+            raise ValueError("gemm_4bit_experts_gate_up: statistics and bias must live on A's device")
+    code32 = absmax_code.to(dtype=torch.float32).contiguous() if absmax_code is not None else None
+    offset32 = absmax_offset.to(dtype=torch.float32) if absmax_offset is not None else None
+    from ..cextension import ExpertsGateUpArgs
+
+    absmax, a8 = absmax.contiguous(), absmax_8bit if absmax_8bit is None else absmax_8bit.contiguous()
+    bias = bias if bias is None else bias.contiguous()
+    with _device_of(A):
+        args = ExpertsGateUpArgs(ct.sizeof(ExpertsGateUpArgs), _DT_CODE[A.dtype], _QT_CODE[quant_type], blocksize, ids.element_size(),
+                                 GATED_CODES[gated], S, E, N, K, T, A.data_ptr(), B.data_ptr(), absmax.data_ptr(), _ptr(a8), _ptr(code32),
+                                 _ptr(offset32), _ptr(bias), ids.data_ptr(), out.data_ptr(), _stream(A))
+        if lib.bnb_mi355x_gemm_4bit_experts_gate_up(ct.byref(args)) != 0:
+            raise ValueError("gemm_4bit_experts_gate_up: the library refused the call (its message is on stderr)")
     return out
 
 

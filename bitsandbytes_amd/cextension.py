@@ -75,6 +75,16 @@ class ExpertsCombineArgs(ct.Structure):
                 ("weights", ct.c_void_p), ("out", ct.c_void_p), ("stream", ct.c_void_p)]
 
 
+class ExpertsGateUpArgs(ct.Structure):
+    """``bnb_mi355x_gemm_4bit_experts_gate_up_args`` of include/bnb_mi355x.h; ``struct_bytes`` is ``ctypes.sizeof(ExpertsGateUpArgs)``."""
+
+    _fields_ = [("struct_bytes", ct.c_size_t), ("dtype", ct.c_int), ("quant_type", ct.c_int), ("blocksize", ct.c_int),
+                ("index_bytes", ct.c_int), ("gated", ct.c_int), ("S", ct.c_int), ("E", ct.c_int), ("N", ct.c_int), ("K", ct.c_int),
+                ("T", ct.c_long), ("x", ct.c_void_p), ("B", ct.c_void_p), ("absmax", ct.c_void_p), ("absmax_8bit", ct.c_void_p),
+                ("absmax_code", ct.c_void_p), ("absmax_offset", ct.c_void_p), ("bias", ct.c_void_p), ("ids", ct.c_void_p),
+                ("out", ct.c_void_p), ("stream", ct.c_void_p)]
+
+
 def _declare(dll: ct.CDLL) -> None:
     def sig(names, argtypes, restype=None):
         for n in names:
@@ -122,6 +132,10 @@ def _declare(dll: ct.CDLL) -> None:
     sig(["bnb_mi355x_gemm_4bit_experts_combine"], [_VOID_P], _I32)
     sig(["bnb_mi355x_gemm_4bit_experts_combine_supported"], [_I32] * 6, _I32)  # (dtype, E, N, K, blocksize, S)
     sig(["bnb_mi355x_gemm_4bit_experts_combine_plan"], [ct.c_long, _I32, _I32, _I32, _VOID_P], _I32)  # (T, S, N, K, out4: int32[4] on the host)
+    # (one argument block, passed with ctypes.byref(ExpertsGateUpArgs(...)); non-zero: refused, nothing launched)
+    sig(["bnb_mi355x_gemm_4bit_experts_gate_up"], [_VOID_P], _I32)
+    sig(["bnb_mi355x_gemm_4bit_experts_gate_up_supported"], [_I32] * 7, _I32)  # (dtype, E, N = 2 I, K, blocksize, S, gated)
+    sig(["bnb_mi355x_gemm_4bit_experts_gate_up_plan"], [ct.c_long, _I32, _I32, _I32, _VOID_P], _I32)  # (T, S, N, K, out4: int32[4] on the host)
     # (dtype, A, B, absmax, out, bias, M, N = 2 F, K, blocksize, quant_type, stream)
     sig(["bnb_mi355x_gemm_4bit_gated"], [_I32] + [_VOID_P] * 5 + [_I32] * 5 + [_VOID_P])
     sig(["bnb_mi355x_gemm_4bit_gated_supported"], [_I32] * 5, _I32)
@@ -213,6 +227,8 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_gemm_4bit_experts_ffn", "bnb_mi355x_gemm_4bit_experts_ffn_supported",
        "bnb_mi355x_gemm_4bit_experts_combine", "bnb_mi355x_gemm_4bit_experts_combine_supported",
        "bnb_mi355x_gemm_4bit_experts_combine_plan",
+       "bnb_mi355x_gemm_4bit_experts_gate_up", "bnb_mi355x_gemm_4bit_experts_gate_up_supported",
+       "bnb_mi355x_gemm_4bit_experts_gate_up_plan",
        "bnb_mi355x_gemm_4bit_gated", "bnb_mi355x_gemm_4bit_gated_supported",
        "bnb_mi355x_gemm_4bit_lora", "bnb_mi355x_gemm_4bit_lora_supported",
        "bnb_mi355x_gemm_4bit_lora_ids", "bnb_mi355x_gemm_4bit_lora_ids_supported",

@@ -164,6 +164,13 @@ bool gemm_4bit_experts_combine(int dtype, const void* h, const uint8_t* B, const
                                const float* absmax_offset, const void* bias, const void* ids, int index_bytes, const void* w, int w_dtype,
                                void* out, long T, int S, int E, int N, int K, int blocksize, int quant_type, hipStream_t stream);
 
+// gemm4_experts_gate_up.hip (token-major MoE gate / up projection, gated SiLU in the launch; gated: 1 chunked, 2 interleaved)
+bool gemm_4bit_experts_gate_up_supported(int dtype, long E, long N, long K, int blocksize, int S, int gated);
+bool gemm_4bit_experts_gate_up_plan(long T, int S, int N, int K, int* out4);
+bool gemm_4bit_experts_gate_up(int dtype, const void* x, const uint8_t* B, const float* absmax, const uint8_t* absmax8, const float* absmax_code,
+                               const float* absmax_offset, const void* bias, const void* ids, int index_bytes, int gated, void* out, long T, int S,
+                               int E, int N, int K, int blocksize, int quant_type, hipStream_t stream);
+
 // lora_shrink.hip
 bool lora_shrink_supported(int dtype, int M, int R, int K);
 bool lora_shrink(int dtype, const void* x, const void* lora_a, void* t, int M, int R, int K, const int* splits, int n_splits, hipStream_t stream);

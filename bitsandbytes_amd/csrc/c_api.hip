@@ -285,6 +285,28 @@ int bnb_mi355x_gemm_4bit_experts_combine_plan(long T, int slots, int N, int K, i
 int bnb_mi355x_gemm_4bit_experts_combine_supported(int dtype, int E, int N, int K, int blocksize, int slots) {
     return gemm_4bit_experts_combine_supported(dtype, E, N, K, blocksize, slots) ? 1 : 0;
 }
+// (the same convention: one argument block, non-zero = refused, nothing launched)
+int bnb_mi355x_gemm_4bit_experts_gate_up(const bnb_mi355x_gemm_4bit_experts_gate_up_args* args) {
+    if (args == nullptr || args->struct_bytes != sizeof(bnb_mi355x_gemm_4bit_experts_gate_up_args)) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_experts_gate_up: struct_bytes is %zu, this library's bnb_mi355x_gemm_4bit_experts_gate_up_args has %zu\n",
+                args == nullptr ? static_cast<size_t>(0) : args->struct_bytes, sizeof(bnb_mi355x_gemm_4bit_experts_gate_up_args));
+        return 1;
+    }
+    if (!gemm_4bit_experts_gate_up(args->dtype, args->x, args->B, args->absmax, args->absmax_8bit, args->absmax_code, args->absmax_offset, args->bias,
+                                   args->ids, args->index_bytes, args->gated, args->out, args->T, args->S, args->E, args->N, args->K, args->blocksize,
+                                   args->quant_type, S(args->stream))) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_experts_gate_up: no kernel for dtype %d, T=%ld, S=%d, E=%d, N=%d, K=%d, blocksize=%d, quant_type %d, index_bytes %d, gated %d (1 <= S <= 16, N even, K <= 65536, blocksize a power of two >= 32 dividing K, FP4 / NF4, gated 1 chunked / 2 interleaved; x, B, absmax, ids, out not NULL; x and B 16-byte aligned)\n",
+                args->dtype, args->T, args->S, args->E, args->N, args->K, args->blocksize, args->quant_type, args->index_bytes, args->gated);
+        return 1;
+    }
+    return 0;
+}
+int bnb_mi355x_gemm_4bit_experts_gate_up_plan(long T, int slots, int N, int K, int* out4) {
+    return gemm_4bit_experts_gate_up_plan(T, slots, N, K, out4) ? 1 : 0;
+}
+int bnb_mi355x_gemm_4bit_experts_gate_up_supported(int dtype, int E, int N, int K, int blocksize, int slots, int gated) {
+    return gemm_4bit_experts_gate_up_supported(dtype, E, N, K, blocksize, slots, gated) ? 1 : 0;
+}
 
 // ------------------------------------------------------------------ gated gemm_4bit (dense FFN: silu(gate) * up as the epilogue)
 void bnb_mi355x_gemm_4bit_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N,

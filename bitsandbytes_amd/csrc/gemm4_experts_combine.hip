@@ -9,7 +9,7 @@
 // The grid is (N tile, token), not (N tile, expert) as in gemm4_experts.hip: every workgroup has work, nobody scans an id list, and
 // all S slots of an output element meet in one workgroup, so the slot sum is the epilogue (fp32, ascending slot order, ONE rounding).
 //
-// Lane map, chosen from K alone (combine_plan): a lane owns 16 packed bytes (a CHUNK: 32 k, inside one quantization block since
+// Lane map, chosen from K alone (combine_plan; gemm4_token_major.h holds what the gate / up kernel shares): a lane owns 16 packed bytes (a CHUNK: 32 k, inside one quantization block since
 // blocksize >= 32) per round; L = 8 / 16 / 32 / 64 neighbouring lanes cover L consecutive chunks of ONE weight row, Q = 2 / 3 rounds
 // L chunks apart, and the 64 / L lane groups of a wavefront take 64 / L neighbouring rows of the tile. K = 768 (24 chunks) runs as
 // L = 8, Q = 3: every lane of every load is live and one wavefront-wide load fetches 128 contiguous bytes of each of 8 rows, where a
@@ -28,40 +28,15 @@
 // A slot whose id is outside [0, E) is skipped before anything of it is read - its weight is never multiplied in; a token without a
 // valid slot gets zeros, written here. Lanes behind the end of a row and row groups behind the end of the tile read in-bounds
 // addresses (chunk 0, the tile's last row) and contribute 0 / are not stored.
-#include "bnb_launchers.h"
+#include "gemm4_token_major.h"
 
 namespace bnb {
 
 namespace {
 
-constexpr int kChunkK = 32;      // k of one 16-byte load of a lane
-constexpr int kLutBytes = 65536; // 256 entries x 32 bank-private copies x 8 B: byte -> (code[hi], code[lo]) fp32
-constexpr int kCode2Bytes = 1024;
-constexpr int kWaves = 8;
-constexpr int kThreads = kWaves * 64;
-constexpr int kMaxSlots = 16;            // the router's top_k bound
-constexpr int kMaxSegs = 16;             // K <= 65536
-constexpr int kSegChunks = 128;          // L = 64, Q = 2: the segment of a long row
+using namespace token_major; // the lane map, the decode table, a row's chunks and its sum
+
 constexpr int kMaxTileRows = 64;
-constexpr size_t kPartBudget = 12 * 1024; // (slot, segment, row) sums; with table and code2 two workgroups fit a CU's 160 KiB
-
-struct CombinePlan {
-    int L, Q, SEGS;
-};
-
-// The lane map of a row length: the smallest cover L * Q of the row's chunks (ties: fewer lanes per row, so more rows per load);
-// rows longer than 192 chunks in segments of 128.
-inline CombinePlan combine_plan(int K) {
-    const int C = K / kChunkK;
-    if (C > 192)
-        return {64, 2, (C + kSegChunks - 1) / kSegChunks};
-    CombinePlan best{64, 3, 1};
-    for (int L = 64; L >= 8; L >>= 1)
-        for (int Q = 3; Q >= 2; --Q)
-            if (L * Q >= C && L * Q <= best.L * best.Q)
-                best = {L, Q, 1};
-    return best;
-}
 
 struct CombineArgs {
     const void* h;
@@ -82,54 +57,10 @@ struct CombineArgs {
     int SEGS;
 };
 
-template <typename T> __device__ __forceinline__ void load_act32(const T* src, f32x2 (&dst)[16]);
-template <> __device__ __forceinline__ void load_act32<bf16>(const bf16* src, f32x2 (&dst)[16]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const u32x4 v = reinterpret_cast<const u32x4*>(src)[q];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            dst[4 * q + i] = f32x2{__builtin_bit_cast(float, v[i] << 16), __builtin_bit_cast(float, v[i] & 0xFFFF0000u)};
-    }
-}
-template <> __device__ __forceinline__ void load_act32<f16>(const f16* src, f32x2 (&dst)[16]) {
-    using h2 = __attribute__((ext_vector_type(2))) f16;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const u32x4 v = reinterpret_cast<const u32x4*>(src)[q];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const h2 p = __builtin_bit_cast(h2, static_cast<uint32_t>(v[i]));
-            dst[4 * q + i] = f32x2{static_cast<float>(p[0]), static_cast<float>(p[1])};
-        }
-    }
-}
-template <> __device__ __forceinline__ void load_act32<float>(const float* src, f32x2 (&dst)[16]) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const f32x4 v = reinterpret_cast<const f32x4*>(src)[q];
-        dst[2 * q] = f32x2{v[0], v[1]};
-        dst[2 * q + 1] = f32x2{v[2], v[3]};
-    }
-}
-
 // id of pair i; the address is workgroup-uniform wherever this is called
 __device__ __forceinline__ long long pair_id(const CombineArgs& p, long i) {
-    return p.idx64 ? static_cast<const long long*>(p.ids)[i] : static_cast<long long>(static_cast<const int*>(p.ids)[i]);
+    return token_id(p.ids, p.idx64, i);
 }
-
-// the n-th set bit of mask (n < popcount), on uniform values
-__device__ __forceinline__ int nth_bit(uint32_t mask, int n) {
-    for (int i = 0; i < n; ++i)
-        mask &= mask - 1;
-    return __builtin_ctz(mask);
-}
-
-template <int Q> struct Stage {
-    u32x4 w[Q]; // the lane's chunk of each round
-    float s[Q]; // fp32 absmax of the chunk's block (plain) / the block's 8-bit code as an integer (nested)
-    float s2[Q]; // nested: second-level absmax of the block's group of 256
-};
 
 template <typename T, bool NESTED, int Q> __global__ __launch_bounds__(kThreads) void gemm4_experts_combine_kernel(const CombineArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -156,22 +87,7 @@ template <typename T, bool NESTED, int Q> __global__ __launch_bounds__(kThreads)
         return;
     }
 
-    // decode table: entry e8 (a packed byte) = 32 copies of (code[e8 >> 4], code[e8 & 15]) in fp32, 256 B per entry, copy c at byte
-    // 8 c. 16-byte chunk it * 512 + tid holds two copies of entry it * 32 + (tid >> 4): every ds_write_b128 of a wavefront covers 1 KiB.
-    {
-        const float lo = code_literal((tid >> 4) & 15, p.fp4 != 0);
-        constexpr int kIters = kLutBytes / 16 / kThreads;
-        static_assert(kThreads == 512 && kIters == 8, "chunk -> entry arithmetic below");
-#pragma unroll
-        for (int it = 0; it < kIters; ++it) {
-            const float hi = (tid >> 8) ? code_literal(2 * it + 1, p.fp4 != 0) : code_literal(2 * it, p.fp4 != 0);
-            *reinterpret_cast<f32x4*>(smem + (it * kThreads + tid) * 16) = f32x4{hi, lo, hi, lo};
-        }
-        if constexpr (NESTED) {
-            if (tid < 256)
-                reinterpret_cast<float*>(smem + kLutBytes)[tid] = p.absmax_code[tid];
-        }
-    }
+    build_decode_table<NESTED>(smem, tid, p.fp4 != 0, p.absmax_code);
     __syncthreads();
     const float* const code2 = reinterpret_cast<const float*>(smem + kLutBytes);
     float* const part = reinterpret_cast<float*>(smem + kLutBytes + kCode2Bytes); // [valid slot][segment][TN]
@@ -215,62 +131,11 @@ template <typename T, bool NESTED, int Q> __global__ __launch_bounds__(kThreads)
         auto load_stage = [&](int rg) -> Stage<Q> {
             int rl = rg * R + r;
             rl = rl < rows ? rl : rows - 1; // (behind the tile: the tile's last row again, never stored)
-            Stage<Q> st;
-#pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                const long elem = (row_base + rl) * p.K + kc[q];
-                st.w[q] = *reinterpret_cast<const u32x4*>(p.B + (elem >> 1));
-                const long blk = elem >> p.bs_shift;
-                if constexpr (NESTED) {
-                    st.s[q] = __builtin_bit_cast(float, static_cast<uint32_t>(p.absmax8[blk]));
-                    st.s2[q] = p.absmax[blk >> 8];
-                } else {
-                    st.s[q] = p.absmax[blk];
-                    st.s2[q] = 0.0f;
-                }
-            }
-            return st;
+            return load_row_chunks<NESTED, Q>(p.B, p.absmax, p.absmax8, (row_base + rl) * p.K, kc, p.bs_shift);
         };
 
         auto compute = [&](const Stage<Q>& st, int rg) {
-            float v = 0.0f;
-#pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                f32x2 cp[16];
-#pragma unroll
-                for (int d = 0; d < 4; ++d)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        // {lane copy offset, weight byte i, 0, 0}: byte * 256 + copy * 8
-                        const uint32_t off = __builtin_amdgcn_perm(st.w[q][d], lane_off, 0x0C0C0400u + (i << 8));
-                        cp[4 * d + i] = *reinterpret_cast<const f32x2*>(smem + off);
-                    }
-                float scale;
-                if constexpr (NESTED)
-                    scale = nested_scale(code2[__builtin_bit_cast(uint32_t, st.s[q])], st.s2[q], offset);
-                else
-                    scale = st.s[q];
-                scale = k_ok[q] ? scale : 0.0f;
-                // four scalar FMA chains: [byte parity][even k, odd k] (no packed fp32 arithmetic in this kernel, see the Makefile)
-                float acc[2][2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};
-#pragma unroll
-                for (int b = 0; b < 16; ++b) {
-                    acc[b & 1][0] = fmaf(cp[b][0], xr[q][b][0], acc[b & 1][0]);
-                    acc[b & 1][1] = fmaf(cp[b][1], xr[q][b][1], acc[b & 1][1]);
-                }
-                const float cv = rounded_f32(((acc[0][0] + acc[0][1]) + (acc[1][0] + acc[1][1])) * scale);
-                v = q == 0 ? cv : v + cv;
-            }
-            // the row's L lanes: xor butterfly, every lane of the group ends with the sum (steps behind L are skipped: uniform)
-            v = dpp_add<0xB1>(v);
-            v = dpp_add<0x4E>(v);
-            v = dpp_add<0x141>(v);
-            if (L >= 16)
-                v = dpp_add<0x140>(v);
-            if (L >= 32)
-                v += __shfl_xor(v, 16, kWave);
-            if (L == 64)
-                v += __shfl_xor(v, 32, kWave);
+            const float v = row_sum<NESTED, Q>(st, xr, k_ok, smem, code2, lane_off, offset, L);
             const int rl = rg * R + r;
             if (j == 0 && rl < rows)
                 part[(sv * p.SEGS + seg) * p.TN + rl] = v;

@@ -155,7 +155,8 @@ int bnb_mi355x_gemm_4bit_fused_max_m(int dtype, int N, int K, int blocksize, int
  * kernel (gemv4_stream_kernel), 2 generic scalar kernel (odd shapes), 3 register-transposed MFMA kernel (gemm4_mfma_rt_kernel),
  * 4 producer/consumer MFMA kernel (gemm4_mfma_pc_kernel), 6 K-quarter MFMA kernel (gemm4_mfma_kq_kernel),
  * 7 streaming MFMA kernel (gemm4_mfma_sm_kernel: 2 ... 16 rows, one persistent workgroup per CU), 9 expert-indexed kernel
- * (gemm4_experts_kernel: bnb_mi355x_gemm_4bit_experts), 10 token-major expert kernel (bnb_mi355x_gemm_4bit_experts_combine). Debug / test query:
+ * (gemm4_experts_kernel: bnb_mi355x_gemm_4bit_experts), 10 token-major expert kernel (bnb_mi355x_gemm_4bit_experts_combine),
+ * 11 token-major gate / up kernel (bnb_mi355x_gemm_4bit_experts_gate_up). Debug / test query:
  * a test that forces a kernel with bnb_mi355x_set_tuning asserts here that it ran (a geometry the forced kernel does not
  * serve falls back to another family by design). */
 int bnb_mi355x_last_gemm_kernel(void);
@@ -226,6 +227,45 @@ int bnb_mi355x_gemm_4bit_experts_combine_supported(int dtype, int E, int N, int 
  * the call above for T tokens - out4 = {L lanes per row, Q rounds, segments, rows per workgroup}. Returns 1, or 0 outside
  * T >= 1, 1 <= S <= 16, N >= 1, K a multiple of 32 up to 65536. */
 int bnb_mi355x_gemm_4bit_experts_combine_plan(long T, int S, int N, int K, int* out4);
+/* Token-major MoE gate / up projection with gated SiLU in the launch (family 11, gemm4_experts_gate_up_kernel): B is [E, N = 2 I, K],
+ * gated 1 (chunked: gate rows [0, I), up rows [I, 2 I) of every expert) or 2 (interleaved: gate row 2 i, up row 2 i + 1); bias, if
+ * given, [E, N] in the same layout. For e = ids[t, s] in [0, E):
+ *   g = T(x[t, :] * dequant(B[e])[gate row i]^T + bias_g), u = T(x[t, :] * dequant(B[e])[up row i]^T + bias_u),
+ *   out[t, s, i] = T(float(T(silu(g))) * float(u)),  silu(g) = g / (1 + expf(-g)) in fp32
+ * - the gated arithmetic of bnb_mi355x_gemm_4bit_experts_ffn; a slot whose id is outside [0, E) gets a row of zeros and nothing of it
+ * is read. x is [T, K] of dtype - ONE activation row per token, which a workgroup loads once for all S slots ([T, S, K] activations
+ * stay with bnb_mi355x_gemm_4bit_experts_ffn); ids [T, S] (index_bytes 4 / 8) on the DEVICE, read by the kernel only; out [T, S, I].
+ * The grid is (column tile, token): no workspace, no memset, no atomics; the order of every fp32 addition depends on (K, blocksize)
+ * alone. 1 <= S <= 16, N even, K <= 65536, blocksize a power of two >= 32 dividing K, x and B 16-byte aligned. The convention of
+ * bnb_mi355x_gemm_4bit_experts_combine: struct_bytes = sizeof of the block; returns 0 after the launch (T == 0: 0, nothing launched);
+ * a call outside the preconditions - where bnb_mi355x_gemm_4bit_experts_gate_up_supported (pure host logic) answers 0, a NULL or
+ * misaligned pointer - prints one line on stderr, launches nothing, returns non-zero and does NOT end the process. */
+typedef struct bnb_mi355x_gemm_4bit_experts_gate_up_args {
+    size_t struct_bytes;            /* sizeof of this struct as the caller was compiled */
+    int dtype;                      /* 0 fp32, 1 fp16, 2 bf16: x, bias, out */
+    int quant_type, blocksize;
+    int index_bytes;                /* 4 / 8: ids int32 / int64 */
+    int gated;                      /* 1 chunked, 2 interleaved */
+    int S, E, N, K;                 /* N = 2 I weight rows per expert */
+    long T;
+    const void* x;                  /* [T, K] */
+    const uint8_t* B;               /* [E, N, K] packed */
+    const float* absmax;
+    const uint8_t* absmax_8bit;     /* nested statistics, or NULL */
+    const float* absmax_code;
+    const float* absmax_offset;
+    const void* bias;               /* [E, N] or NULL */
+    const void* ids;                /* [T, S] */
+    void* out;                      /* [T, S, N / 2] */
+    bnb_stream_t stream;
+} bnb_mi355x_gemm_4bit_experts_gate_up_args;
+int bnb_mi355x_gemm_4bit_experts_gate_up(const bnb_mi355x_gemm_4bit_experts_gate_up_args* args);
+int bnb_mi355x_gemm_4bit_experts_gate_up_supported(int dtype, int E, int N, int K, int blocksize, int S, int gated);
+/* Debug / test query (host logic and the CU count of the current device or bnb_mi355x_set_cu_count's override): the launch plan of
+ * the call above for T tokens - out4 = {L lanes per row, Q rounds, segments, output columns per workgroup}; {L, Q, segments} are
+ * those of bnb_mi355x_gemm_4bit_experts_combine_plan for the same K. Returns 1, or 0 outside T >= 1, 1 <= S <= 16, N >= 2 and even,
+ * K a multiple of 32 up to 65536. */
+int bnb_mi355x_gemm_4bit_experts_gate_up_plan(long T, int S, int N, int K, int* out4);
 /* Dense gated-SiLU FFN: the fused matmul over ONE interleaved matrix B [N = 2 F, K] - gate row i at row 2 i, up row i at row 2 i + 1;
  * bias, if given, [N] in the same layout - with silu(gate) * up as its epilogue. A is [M, K], out is [M, F]:
  *     g = T(acc_g + bias_g), u = T(acc_u + bias_u), out[m, i] = T(float(T(silu(g))) * float(u)),  silu(g) = g / (1 + expf(-g)) in fp32

@@ -13,6 +13,8 @@ that the weights selected by one pass over the rotation exceed the 256 MiB Infin
   plain    the first launch of `parent` alone, writing [T, S, 2I]
   down+sum the down stage of `fused` alone on a random h [T, S, I]: the row-scale launch and torch's sum           2 launches
   combine  the down stage of `fused2` alone: matmul_4bit_experts_combine                                           1 launch
+  tokens   moe_ffn_4bit_tokens(...): both stages token-major                                                       2 launches
+  gate_up  the first launch of `tokens` alone, on the stacks of `gated`: matmul_4bit_experts_gate_up               1 launch
 A shape whose rotation does not fit in memory is skipped with a line that says so.
 The table is written to profiles/moe_ffn_bench.txt (--out), replacing the file.
     python tools/bench_moe_ffn.py [--rounds 5] [--quick] [--out profiles/moe_ffn_bench.txt]"""
@@ -66,7 +68,7 @@ def main():
         "x is [T, H], routing weights fp32")
     say(f"{'shape':>44s} {'T':>2s} {'S':>2s} {'fused block':>24s} {'parent block':>24s} {'saved':>7s} {'ratio':>6s} "
         f"{'gated launch':>24s} {'plain launch':>24s} {'gated-plain':>11s} {'fused2 block':>24s} {'down+sum':>24s} {'combine':>24s} "
-        f"{'down saved':>10s}")
+        f"{'down saved':>10s} {'tokens block':>24s} {'gate_up launch':>24s} {'gated/gate_up':>13s} {'fused2/tokens':>13s}")
     gen = torch.Generator(device="cuda").manual_seed(0)
     for label, E, I, H, S, Ts in SHAPES:
         per_block = (2 * I * H + H * I) // 2 + (2 * I * H + H * I) // BS * 4     # one expert's bytes of both stacks
@@ -122,7 +124,17 @@ def main():
                     _, _, dn, ds = stacks[c % L]
                     bnb.matmul_4bit_experts_combine(h, dn, ds, ids, w)
 
-            legs = [fused, parent, gated, plain, fused2, down_sum, combine]
+            def tokens():
+                for c in range(calls):
+                    gu, gs, dn, ds = stacks[c % L]
+                    bnb.moe_ffn_4bit_tokens(x, gu, gs, dn, ds, ids, w)
+
+            def gate_up():
+                for c in range(calls):
+                    gu, gs, _, _ = stacks[c % L]
+                    bnb.matmul_4bit_experts_gate_up(x, gu, gs, ids)
+
+            legs = [fused, parent, gated, plain, fused2, down_sum, combine, tokens, gate_up]
             graphs = [capture(fn) for fn in legs]
             samples = [[] for _ in legs]
             reps = [max(2, int(10000.0 / (timed(g, calls, 1) * calls)) + 1) for g in graphs]
@@ -133,7 +145,8 @@ def main():
             cols = [f"{statistics.median(s):8.2f} ({min(s):.2f}...{max(s):.2f})" for s in samples]
             med = [statistics.median(s) for s in samples]
             say(f"{label:>44s} {T:>2d} {S:>2d} {cols[0]:>24s} {cols[1]:>24s} {med[1] - med[0]:7.2f} {med[1] / med[0]:5.2f}x "
-                f"{cols[2]:>24s} {cols[3]:>24s} {med[2] - med[3]:+11.2f} {cols[4]:>24s} {cols[5]:>24s} {cols[6]:>24s} {med[5] - med[6]:10.2f}")
+                f"{cols[2]:>24s} {cols[3]:>24s} {med[2] - med[3]:+11.2f} {cols[4]:>24s} {cols[5]:>24s} {cols[6]:>24s} {med[5] - med[6]:10.2f} "
+                f"{cols[7]:>24s} {cols[8]:>24s} {med[2] / med[8]:12.2f}x {med[4] / med[7]:12.2f}x")
             del graphs
         del stacks
         torch.cuda.empty_cache()
