@@ -453,6 +453,26 @@ def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str,
     return torch.empty((*ids.shape, width), dtype=A.dtype, device=A.device)
 
 
+# ---------------------------------------------------------------------------------------------- gemm_4bit_experts_mfma
+# gemm_4bit_experts_ffn on the matrix pipe, for batched MoE decode: the same operands, options and output, sixteen (token, slot) pairs
+# per pass over an expert's weights instead of four. fp16 / bf16, K % 64 == 0, blocksize >= 64. The fp32 sum behind an output element
+# runs in another order than gemm_4bit_experts_ffn's (a function of K alone), so in 16 bits the two ops agree up to last-bit roundings.
+torch.library.define(
+    "bitsandbytes_amd::gemm_4bit_experts_mfma",
+    "(Tensor A, Tensor B, int[] shapeB, Tensor absmax, Tensor ids, int blocksize, str quant_type, Tensor? bias=None, "
+    "Tensor? absmax_8bit=None, Tensor? absmax_code=None, Tensor? absmax_offset=None, Tensor? row_scale=None, "
+    "str gated=\"none\") -> Tensor",
+)
+
+
+@register_fake("bitsandbytes_amd::gemm_4bit_experts_mfma")
+def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str, bias=None, absmax_8bit=None, absmax_code=None,
+      absmax_offset=None, row_scale=None, gated: str = "none"):
+    width = _check_gemm_4bit_experts_ffn(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit, absmax_code, absmax_offset,
+                                         row_scale, gated)[4]
+    return torch.empty((*ids.shape, width), dtype=A.dtype, device=A.device)
+
+
 # ---------------------------------------------------------------------------------------------- gemm_4bit_experts_combine
 # The down projection of an expert FFN with the routing-weighted slot sum in the launch (token-major grid):
 #   out[t, :] = sum over the slots s with 0 <= ids[t, s] < E:  weights[t, s] * (A[t, s] @ dequantize_4bit(B)[ids[t, s]].T (+ bias[ids[t, s]]))

@@ -433,6 +433,91 @@ def _moe_ffn_4bit(x, gate_up, gate_up_state, down, down_state, expert_ids, routi
     return y[:, 0] if y.shape[1] == 1 else y.sum(dim=1)
 
 
+def _batched_served(x: torch.Tensor, quant_state: F.QuantState, gated: str) -> bool:
+    """Whether the expert-indexed MFMA launch serves this projection - decided from shapes and dtypes only."""
+    if x.device.type != "cuda" or len(quant_state.shape) != 3 or (quant_state.nested and quant_state.state2.blocksize != 256):
+        return False
+    from ..backends import hip
+
+    E, N, K = (int(v) for v in quant_state.shape)
+    return hip.gemm_4bit_experts_mfma_supported(x.dtype, E, N, K, quant_state.blocksize, gated)
+
+
+def matmul_4bit_experts_batched(
+    x: torch.Tensor,
+    packed: torch.Tensor,
+    quant_state: F.QuantState,
+    expert_ids: torch.Tensor,
+    bias: Optional[torch.Tensor] = None,
+    gated: str = "none",
+    row_scale: Optional[torch.Tensor] = None,
+):
+    """:func:`matmul_4bit_experts` for batched decode steps - the same arguments, options and result shape, one launch of the
+    expert-indexed MFMA kernel: an expert's weights are streamed once per SIXTEEN (token, slot) pairs that select it (the rows of one
+    matrix-pipe batch) instead of once per four. fp16 / bf16, ``K % 64 == 0``, blocksize >= 64; a geometry the kernel does not serve
+    raises ``ValueError``. The fp32 sum behind an output element runs in a fixed order, a function of ``K`` alone - a row's bits do not
+    depend on the other pairs of the call -, which is not :func:`matmul_4bit_experts`'s order: in 16 bits the two agree up to
+    last-bit roundings. Ids on the device, read by the kernel only (graph capture); an id outside ``[0, E)`` gives a row of zeros.
+    Inference only: there is no autograd formula."""
+    if quant_state is None:
+        raise ValueError("quant_state is required")
+    if len(quant_state.shape) != 3:
+        raise ValueError(f"matmul_4bit_experts_batched: quant_state.shape must be 3D [E, N, K], got {list(quant_state.shape)}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, bias, row_scale)):
+        raise RuntimeError("matmul_4bit_experts_batched is inference only (no autograd formula): call it under torch.no_grad() "
+                           "or with detached inputs")
+    if x.shape[-1] != quant_state.shape[2]:
+        raise ValueError(
+            f"matmul_4bit_experts_batched: x inner dim ({x.shape[-1]}) must equal quant_state.shape[2] ({quant_state.shape[2]}); "
+            "expert tensors in [E, K, N] orientation (contraction over the unpacked dimension) are not supported")
+    if gated != "none" and row_scale is not None:
+        raise ValueError("matmul_4bit_experts_batched: gated and row_scale cannot be given together")
+    if x.device.type == "cuda" and not _batched_served(x, quant_state, gated):
+        if quant_state.nested and quant_state.state2.blocksize != 256:
+            raise NotImplementedError("nested quantization with state2.blocksize != 256 is not supported")
+        raise ValueError(f"matmul_4bit_experts_batched: no kernel for quant_state.shape={list(quant_state.shape)}, "
+                         f"blocksize={quant_state.blocksize}, dtype={x.dtype}, gated={gated!r}")
+    packed = packed.view(-1, 1)
+    if x.device.type == "cuda" and not _is_compiling():
+        x, packed = _aligned16(x), _aligned16(packed)
+    op = torch.ops.bitsandbytes_amd.gemm_4bit_experts_mfma.default
+    if not quant_state.nested:
+        return op(x, packed, quant_state.shape, quant_state.absmax, expert_ids, quant_state.blocksize, quant_state.quant_type,
+                  bias=bias, row_scale=row_scale, gated=gated)
+    return op(x, packed, quant_state.shape, quant_state.state2.absmax, expert_ids, quant_state.blocksize, quant_state.quant_type,
+              bias=bias, absmax_8bit=quant_state.absmax, absmax_code=quant_state.state2.code, absmax_offset=quant_state.offset,
+              row_scale=row_scale, gated=gated)
+
+
+def moe_ffn_4bit_batched(
+    x: torch.Tensor,
+    gate_up: torch.Tensor,
+    gate_up_state: F.QuantState,
+    down: torch.Tensor,
+    down_state: F.QuantState,
+    expert_ids: torch.Tensor,
+    routing_weights: torch.Tensor,
+    gate_up_bias: Optional[torch.Tensor] = None,
+    down_bias: Optional[torch.Tensor] = None,
+    gated: str = "chunked",
+):
+    """:func:`moe_ffn_4bit` for batched decode steps, the same arguments and the same shape of block - gated launch, row-scale launch,
+    torch's ``sum`` over the slots - with both launches on the expert-indexed MFMA kernel (:func:`matmul_4bit_experts_batched`). A stage
+    whose geometry that kernel declines (fp32, blocksize 32, ``K % 64 != 0``) runs :func:`moe_ffn_4bit`'s launch for that stage.
+    Which block at which ``T``: ``INTEGRATION.md``. (``nn.parametrize.moe_ffn_4bit(..., combine="batched")`` is this function on
+    parametrized expert tensors.)"""
+    if gated not in ("chunked", "interleaved"):
+        raise ValueError(f"moe_ffn_4bit: gated must be 'chunked' or 'interleaved', got {gated!r}")
+    if expert_ids.dim() != 2 or tuple(routing_weights.shape) != tuple(expert_ids.shape):
+        raise ValueError(f"moe_ffn_4bit: expert_ids and routing_weights must both be [T, S], got {tuple(expert_ids.shape)} and "
+                         f"{tuple(routing_weights.shape)}")
+    first = matmul_4bit_experts_batched if _batched_served(x, gate_up_state, gated) else matmul_4bit_experts
+    h = first(x, gate_up, gate_up_state, expert_ids, bias=gate_up_bias, gated=gated)
+    second = matmul_4bit_experts_batched if _batched_served(h, down_state, "none") else matmul_4bit_experts
+    y = second(h, down, down_state, expert_ids, bias=down_bias, row_scale=routing_weights)
+    return y[:, 0] if y.shape[1] == 1 else y.sum(dim=1)
+
+
 def _gated_fused(x: torch.Tensor, quant_state: F.QuantState) -> bool:
     """Whether the gated launch serves this call - decided from shapes, dtypes and alignment only (nothing is read on the host)."""
     if x.device.type != "cuda" or quant_state.nested or _is_compiling():

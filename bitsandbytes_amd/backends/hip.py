@@ -548,6 +548,53 @@ def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str,
     return out
 
 
+# ------------------------------------------------------------------------------------------ gemm_4bit_experts_mfma
+def gemm_4bit_experts_mfma_supported(dtype: torch.dtype, E: int, N: int, K: int, blocksize: int, gated: str = "none") -> bool:
+    """Whether the expert-indexed MFMA kernel serves this geometry with this epilogue (N: weight rows per expert; pure host logic)."""
+    if dtype not in _DT_CODE or gated not in GATED_CODES or max(E, N, K) >= 2**31:
+        return False
+    return bool(lib.bnb_mi355x_gemm_4bit_experts_mfma_supported(_DT_CODE[dtype], E, N, K, blocksize, GATED_CODES[gated]))
+
+
+@register_kernel("bitsandbytes_amd::gemm_4bit_experts_mfma", "cuda")
+def _(A, B, shapeB: Sequence[int], absmax, ids, blocksize: int, quant_type: str, bias=None, absmax_8bit=None, absmax_code=None,
+      absmax_offset=None, row_scale=None, gated: str = "none"):
+    """One launch of gemm4_experts_mfma_kernel with the plain, gated or row-scale epilogue; ids and scales stay on the device."""
+    E, N, K, per_slot, width = _check_gemm_4bit_experts_ffn(A, B, shapeB, absmax, ids, blocksize, quant_type, bias, absmax_8bit,
+                                                            absmax_code, absmax_offset, row_scale, gated)
+    P = ids.numel()
+    S = ids.shape[1] if ids.dim() == 2 else 1
+    with _device_of(A):
+        # (inside the guard, with the launch: the tile height of the plan follows the current device's CU count)
+        if not gemm_4bit_experts_mfma_supported(A.dtype, E, N, K, blocksize, gated):
+            raise ValueError(f"gemm_4bit_experts_mfma: no kernel for E={E}, N={N}, K={K}, blocksize={blocksize}, dtype={A.dtype}, gated={gated}")
+        out = torch.empty((*ids.shape, width), dtype=A.dtype, device=A.device)
+        if P == 0:
+            return out
+        A = A.contiguous()
+        B = B.contiguous()
+        ids = ids.contiguous()
+        if A.data_ptr() % 16 or B.data_ptr() % 16:
+            raise ValueError("gemm_4bit_experts_mfma: A and B must be 16-byte aligned")
+        for t in (absmax, bias, absmax_8bit, absmax_code, absmax_offset):
+            if t is not None and t.device != A.device:
+                raise ValueError("gemm_4bit_experts_mfma: statistics and bias must live on A's device")
+        code32 = absmax_code.to(dtype=torch.float32).contiguous() if absmax_code is not None else None
+        offset32 = absmax_offset.to(dtype=torch.float32) if absmax_offset is not None else None
+        scale = None if row_scale is None else row_scale.contiguous()  # (read in its own dtype: no conversion launch)
+        from ..cextension import ExpertsMfmaArgs
+
+        absmax, a8 = absmax.contiguous(), absmax_8bit if absmax_8bit is None else absmax_8bit.contiguous()
+        bias = bias if bias is None else bias.contiguous()
+        args = ExpertsMfmaArgs(ct.sizeof(ExpertsMfmaArgs), _DT_CODE[A.dtype], _QT_CODE[quant_type], blocksize, ids.element_size(),
+                               GATED_CODES[gated], 0 if scale is None else _DT_CODE[scale.dtype], S, E, N, K, P,
+                               K if (per_slot or ids.dim() == 1) else 0, A.data_ptr(), B.data_ptr(), absmax.data_ptr(), _ptr(a8), _ptr(code32),
+                               _ptr(offset32), _ptr(bias), ids.data_ptr(), _ptr(scale), out.data_ptr(), _stream(A))
+        if lib.bnb_mi355x_gemm_4bit_experts_mfma(ct.byref(args)) != 0:
+            raise ValueError("gemm_4bit_experts_mfma: the library refused the call (its message is on stderr)")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ gemm_4bit_experts_combine
 def gemm_4bit_experts_combine_supported(dtype: torch.dtype, E: int, N: int, K: int, blocksize: int, S: int) -> bool:
     """Whether the token-major kernel serves this down projection with S slots per token (pure host logic of the library)."""

@@ -85,6 +85,16 @@ class ExpertsGateUpArgs(ct.Structure):
                 ("out", ct.c_void_p), ("stream", ct.c_void_p)]
 
 
+class ExpertsMfmaArgs(ct.Structure):
+    """``bnb_mi355x_gemm_4bit_experts_mfma_args`` of include/bnb_mi355x.h; ``struct_bytes`` is ``ctypes.sizeof(ExpertsMfmaArgs)``."""
+
+    _fields_ = [("struct_bytes", ct.c_size_t), ("dtype", ct.c_int), ("quant_type", ct.c_int), ("blocksize", ct.c_int),
+                ("index_bytes", ct.c_int), ("gated", ct.c_int), ("row_scale_dtype", ct.c_int), ("S", ct.c_int), ("E", ct.c_int),
+                ("N", ct.c_int), ("K", ct.c_int), ("P", ct.c_long), ("a_slot_stride", ct.c_long), ("A", ct.c_void_p), ("B", ct.c_void_p),
+                ("absmax", ct.c_void_p), ("absmax_8bit", ct.c_void_p), ("absmax_code", ct.c_void_p), ("absmax_offset", ct.c_void_p),
+                ("bias", ct.c_void_p), ("ids", ct.c_void_p), ("row_scale", ct.c_void_p), ("out", ct.c_void_p), ("stream", ct.c_void_p)]
+
+
 def _declare(dll: ct.CDLL) -> None:
     def sig(names, argtypes, restype=None):
         for n in names:
@@ -136,6 +146,9 @@ def _declare(dll: ct.CDLL) -> None:
     sig(["bnb_mi355x_gemm_4bit_experts_gate_up"], [_VOID_P], _I32)
     sig(["bnb_mi355x_gemm_4bit_experts_gate_up_supported"], [_I32] * 7, _I32)  # (dtype, E, N = 2 I, K, blocksize, S, gated)
     sig(["bnb_mi355x_gemm_4bit_experts_gate_up_plan"], [ct.c_long, _I32, _I32, _I32, _VOID_P], _I32)  # (T, S, N, K, out4: int32[4] on the host)
+    # (one argument block, passed with ctypes.byref(ExpertsMfmaArgs(...)); non-zero: refused, nothing launched)
+    sig(["bnb_mi355x_gemm_4bit_experts_mfma"], [_VOID_P], _I32)
+    sig(["bnb_mi355x_gemm_4bit_experts_mfma_supported"], [_I32] * 6, _I32)  # (dtype, E, N, K, blocksize, gated)
     # (dtype, A, B, absmax, out, bias, M, N = 2 F, K, blocksize, quant_type, stream)
     sig(["bnb_mi355x_gemm_4bit_gated"], [_I32] + [_VOID_P] * 5 + [_I32] * 5 + [_VOID_P])
     sig(["bnb_mi355x_gemm_4bit_gated_supported"], [_I32] * 5, _I32)
@@ -229,6 +242,7 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_gemm_4bit_experts_combine_plan",
        "bnb_mi355x_gemm_4bit_experts_gate_up", "bnb_mi355x_gemm_4bit_experts_gate_up_supported",
        "bnb_mi355x_gemm_4bit_experts_gate_up_plan",
+       "bnb_mi355x_gemm_4bit_experts_mfma", "bnb_mi355x_gemm_4bit_experts_mfma_supported",
        "bnb_mi355x_gemm_4bit_gated", "bnb_mi355x_gemm_4bit_gated_supported",
        "bnb_mi355x_gemm_4bit_lora", "bnb_mi355x_gemm_4bit_lora_supported",
        "bnb_mi355x_gemm_4bit_lora_ids", "bnb_mi355x_gemm_4bit_lora_ids_supported",

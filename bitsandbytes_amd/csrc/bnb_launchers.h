@@ -171,6 +171,15 @@ bool gemm_4bit_experts_gate_up(int dtype, const void* x, const uint8_t* B, const
                                const float* absmax_offset, const void* bias, const void* ids, int index_bytes, int gated, void* out, long T, int S,
                                int E, int N, int K, int blocksize, int quant_type, hipStream_t stream);
 
+// gemm4_experts_mfma.hip (the expert-indexed matmul on the matrix pipe, 16 pairs per weight pass; the operands and epilogues of
+// gemm_4bit_experts_ffn; false = refused, nothing launched)
+bool gemm_4bit_experts_mfma_supported(int dtype, long E, long N, long K, int blocksize, int gated);
+int gemm_4bit_experts_mfma_tiles(int N);
+bool gemm_4bit_experts_mfma(int dtype, const void* A, long a_slot_stride, const uint8_t* B, const float* absmax, const uint8_t* absmax8,
+                            const float* absmax_code, const float* absmax_offset, const void* bias, const void* ids, int index_bytes,
+                            const void* row_scale, int row_scale_dtype, int gated, void* out, long P, int S, int E, int N, int K,
+                            int blocksize, int quant_type, hipStream_t stream);
+
 // lora_shrink.hip
 bool lora_shrink_supported(int dtype, int M, int R, int K);
 bool lora_shrink(int dtype, const void* x, const void* lora_a, void* t, int M, int R, int K, const int* splits, int n_splits, hipStream_t stream);

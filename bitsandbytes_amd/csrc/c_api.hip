@@ -307,6 +307,26 @@ int bnb_mi355x_gemm_4bit_experts_gate_up_plan(long T, int slots, int N, int K, i
 int bnb_mi355x_gemm_4bit_experts_gate_up_supported(int dtype, int E, int N, int K, int blocksize, int slots, int gated) {
     return gemm_4bit_experts_gate_up_supported(dtype, E, N, K, blocksize, slots, gated) ? 1 : 0;
 }
+// (the same convention: one argument block, non-zero = refused, nothing launched)
+int bnb_mi355x_gemm_4bit_experts_mfma(const bnb_mi355x_gemm_4bit_experts_mfma_args* args) {
+    if (args == nullptr || args->struct_bytes != sizeof(bnb_mi355x_gemm_4bit_experts_mfma_args)) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_experts_mfma: struct_bytes is %zu, this library's bnb_mi355x_gemm_4bit_experts_mfma_args has %zu\n",
+                args == nullptr ? static_cast<size_t>(0) : args->struct_bytes, sizeof(bnb_mi355x_gemm_4bit_experts_mfma_args));
+        return 1;
+    }
+    if (!gemm_4bit_experts_mfma(args->dtype, args->A, args->a_slot_stride, args->B, args->absmax, args->absmax_8bit, args->absmax_code, args->absmax_offset,
+                                args->bias, args->ids, args->index_bytes, args->row_scale, args->row_scale_dtype, args->gated, args->out, args->P, args->S,
+                                args->E, args->N, args->K, args->blocksize, args->quant_type, S(args->stream))) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_4bit_experts_mfma: no kernel for dtype %d, P=%ld, S=%d, E=%d, N=%d, K=%d, blocksize=%d, quant_type %d, index_bytes %d, gated %d, row_scale %s of dtype %d, a_slot_stride %ld (fp16 / bf16, K %% 64 == 0, blocksize a power of two >= 64 dividing K, N even when gated, FP4 / NF4, gated and row_scale exclude each other; A, B, absmax, ids, out not NULL; A and B 16-byte aligned)\n",
+                args->dtype, args->P, args->S, args->E, args->N, args->K, args->blocksize, args->quant_type, args->index_bytes, args->gated,
+                args->row_scale ? "given" : "null", args->row_scale_dtype, args->a_slot_stride);
+        return 1;
+    }
+    return 0;
+}
+int bnb_mi355x_gemm_4bit_experts_mfma_supported(int dtype, int E, int N, int K, int blocksize, int gated) {
+    return gemm_4bit_experts_mfma_supported(dtype, E, N, K, blocksize, gated) ? 1 : 0;
+}
 
 // ------------------------------------------------------------------ gated gemm_4bit (dense FFN: silu(gate) * up as the epilogue)
 void bnb_mi355x_gemm_4bit_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N,

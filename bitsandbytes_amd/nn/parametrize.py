@@ -17,6 +17,7 @@ import torch.nn.utils.parametrize as P
 from .. import functional as F
 from ..autograd._functions import matmul_4bit_experts as _matmul_4bit_experts
 from ..autograd._functions import moe_ffn_4bit as _moe_ffn_4bit
+from ..autograd._functions import moe_ffn_4bit_batched as _moe_ffn_4bit_batched
 from ..autograd._functions import moe_ffn_4bit_fused as _moe_ffn_4bit_fused
 from ..autograd._functions import moe_ffn_4bit_tokens as _moe_ffn_4bit_tokens
 
@@ -147,11 +148,12 @@ def moe_ffn_4bit(module: nn.Module, gate_up_name: str, down_name: str, x: torch.
     block is composed of :func:`matmul_4bit_experts` of this module and torch's ``silu``, ``*`` and ``sum`` - also without looking at
     the ids or the weights on the host. ``combine="fused"``: the down projection and the slot sum as one launch where the library
     serves it (:func:`bitsandbytes_amd.moe_ffn_4bit_fused`); ``combine="tokens"``: both stages token-major
-    (:func:`bitsandbytes_amd.moe_ffn_4bit_tokens`). Inference only."""
+    (:func:`bitsandbytes_amd.moe_ffn_4bit_tokens`); ``combine="batched"``: the block of :func:`bitsandbytes_amd.moe_ffn_4bit` with both
+    launches on the expert-indexed MFMA kernel, for batched decode steps (:func:`bitsandbytes_amd.moe_ffn_4bit_batched`). Inference only."""
     if gated not in ("chunked", "interleaved"):
         raise ValueError(f"moe_ffn_4bit: gated must be 'chunked' or 'interleaved', got {gated!r}")
-    if combine not in ("sum", "fused", "tokens"):
-        raise ValueError(f"moe_ffn_4bit: combine must be 'sum', 'fused' or 'tokens', got {combine!r}")
+    if combine not in ("sum", "fused", "tokens", "batched"):
+        raise ValueError(f"moe_ffn_4bit: combine must be 'sum', 'fused', 'tokens' or 'batched', got {combine!r}")
     gu_packed, gu_state = _expert_state(module, gate_up_name, "moe_ffn_4bit")
     dn_packed, dn_state = _expert_state(module, down_name, "moe_ffn_4bit")
     if expert_ids.dim() != 2 or tuple(routing_weights.shape) != tuple(expert_ids.shape):
@@ -168,7 +170,7 @@ def moe_ffn_4bit(module: nn.Module, gate_up_name: str, down_name: str, x: torch.
 
     if (x.is_cuda and routing_weights.dtype in (torch.float32, x.dtype) and served(gu_packed, gu_state, gated)
             and served(dn_packed, dn_state, "none")):
-        block = {"sum": _moe_ffn_4bit, "fused": _moe_ffn_4bit_fused, "tokens": _moe_ffn_4bit_tokens}[combine]
+        block = {"sum": _moe_ffn_4bit, "fused": _moe_ffn_4bit_fused, "tokens": _moe_ffn_4bit_tokens, "batched": _moe_ffn_4bit_batched}[combine]
         return block(x, gu_packed.data, gu_state, dn_packed.data, dn_state, expert_ids, routing_weights,
                      gate_up_bias=gate_up_bias, down_bias=down_bias, gated=gated)
     with torch.no_grad():

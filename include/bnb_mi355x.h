@@ -156,7 +156,8 @@ int bnb_mi355x_gemm_4bit_fused_max_m(int dtype, int N, int K, int blocksize, int
  * 4 producer/consumer MFMA kernel (gemm4_mfma_pc_kernel), 6 K-quarter MFMA kernel (gemm4_mfma_kq_kernel),
  * 7 streaming MFMA kernel (gemm4_mfma_sm_kernel: 2 ... 16 rows, one persistent workgroup per CU), 9 expert-indexed kernel
  * (gemm4_experts_kernel: bnb_mi355x_gemm_4bit_experts), 10 token-major expert kernel (bnb_mi355x_gemm_4bit_experts_combine),
- * 11 token-major gate / up kernel (bnb_mi355x_gemm_4bit_experts_gate_up). Debug / test query:
+ * 11 token-major gate / up kernel (bnb_mi355x_gemm_4bit_experts_gate_up), 12 expert-indexed MFMA kernel
+ * (bnb_mi355x_gemm_4bit_experts_mfma). Debug / test query:
  * a test that forces a kernel with bnb_mi355x_set_tuning asserts here that it ran (a geometry the forced kernel does not
  * serve falls back to another family by design). */
 int bnb_mi355x_last_gemm_kernel(void);
@@ -266,6 +267,41 @@ int bnb_mi355x_gemm_4bit_experts_gate_up_supported(int dtype, int E, int N, int 
  * those of bnb_mi355x_gemm_4bit_experts_combine_plan for the same K. Returns 1, or 0 outside T >= 1, 1 <= S <= 16, N >= 2 and even,
  * K a multiple of 32 up to 65536. */
 int bnb_mi355x_gemm_4bit_experts_gate_up_plan(long T, int S, int N, int K, int* out4);
+/* The expert-indexed matmul on the matrix pipe, for batched MoE decode (family 12, gemm4_experts_mfma_kernel): the operands, the id
+ * handling and the three epilogues (plain; gated 1 chunked / 2 interleaved; row_scale) of bnb_mi355x_gemm_4bit_experts_ffn, in that
+ * call's arithmetic behind the fp32 sum - but one pass over an expert's weights serves SIXTEEN (token, slot) pairs, the rows of one
+ * v_mfma_f32_16x16x32 batch, instead of four. fp16 / bf16 only, K a multiple of 64, blocksize a power of two >= 64 dividing K, N even
+ * when gated, and the size limits of bnb_mi355x_gemm_4bit_experts_supported; A and B 16-byte aligned; a_slot_stride K or 0. The fp32
+ * sum of an output element runs in an order that is a function of K alone (not of the other pairs, the tile or the CU count): no
+ * atomics, no workspace, no memset; ids, row_scale on the DEVICE, read by the kernel only. The convention of
+ * bnb_mi355x_gemm_4bit_experts_gate_up: struct_bytes = sizeof of the block; returns 0 after the launch (P == 0: 0, nothing launched);
+ * a call outside the preconditions - where bnb_mi355x_gemm_4bit_experts_mfma_supported (pure host logic) answers 0, gated together
+ * with row_scale, a NULL or misaligned pointer - prints one line on stderr, launches nothing, returns non-zero and does NOT end the
+ * process. */
+typedef struct bnb_mi355x_gemm_4bit_experts_mfma_args {
+    size_t struct_bytes;            /* sizeof of this struct as the caller was compiled */
+    int dtype;                      /* 1 fp16, 2 bf16: A, bias, out */
+    int quant_type, blocksize;
+    int index_bytes;                /* 4 / 8: ids int32 / int64 */
+    int gated;                      /* 0 none, 1 chunked, 2 interleaved */
+    int row_scale_dtype;            /* 0 fp32, or dtype */
+    int S, E, N, K;                 /* N weight rows per expert */
+    long P;                         /* (token, slot) pairs */
+    long a_slot_stride;             /* K: A is [P, K]; 0: A is [P / S, K] */
+    const void* A;
+    const uint8_t* B;               /* [E, N, K] packed */
+    const float* absmax;
+    const uint8_t* absmax_8bit;     /* nested statistics, or NULL */
+    const float* absmax_code;
+    const float* absmax_offset;
+    const void* bias;               /* [E, N] or NULL */
+    const void* ids;                /* [P] */
+    const void* row_scale;          /* [P] or NULL */
+    void* out;                      /* [P, N], gated: [P, N / 2] */
+    bnb_stream_t stream;
+} bnb_mi355x_gemm_4bit_experts_mfma_args;
+int bnb_mi355x_gemm_4bit_experts_mfma(const bnb_mi355x_gemm_4bit_experts_mfma_args* args);
+int bnb_mi355x_gemm_4bit_experts_mfma_supported(int dtype, int E, int N, int K, int blocksize, int gated);
 /* Dense gated-SiLU FFN: the fused matmul over ONE interleaved matrix B [N = 2 F, K] - gate row i at row 2 i, up row i at row 2 i + 1;
  * bias, if given, [N] in the same layout - with silu(gate) * up as its epilogue. A is [M, K], out is [M, F]:
  *     g = T(acc_g + bias_g), u = T(acc_u + bias_u), out[m, i] = T(float(T(silu(g))) * float(u)),  silu(g) = g / (1 + expf(-g)) in fp32

@@ -15,6 +15,8 @@ that the weights selected by one pass over the rotation exceed the 256 MiB Infin
   combine  the down stage of `fused2` alone: matmul_4bit_experts_combine                                           1 launch
   tokens   moe_ffn_4bit_tokens(...): both stages token-major                                                       2 launches
   gate_up  the first launch of `tokens` alone, on the stacks of `gated`: matmul_4bit_experts_gate_up               1 launch
+  batched  moe_ffn_4bit_batched(...): the block of `fused` with both launches on the expert-indexed MFMA kernel   3 launches (2 at S = 1)
+  gated16  the first launch of `batched` alone: matmul_4bit_experts_batched(..., gated="chunked")                  1 launch
 A shape whose rotation does not fit in memory is skipped with a line that says so.
 The table is written to profiles/moe_ffn_bench.txt (--out), replacing the file.
     python tools/bench_moe_ffn.py [--rounds 5] [--quick] [--out profiles/moe_ffn_bench.txt]"""
@@ -35,8 +37,8 @@ from tools.bench_experts import BS, CACHE_BYTES, capture, timed  # noqa: E402
 
 # (label, E, I, H, S, T values): gate_up [E, 2I, H], down [E, H, I]
 SHAPES = [
-    ("Mixtral 8 x 28672 x 4096 + 8 x 4096 x 14336", 8, 14336, 4096, 2, (1, 4, 16)),
-    ("128 x 1536 x 2048 + 128 x 2048 x 768", 128, 768, 2048, 8, (1, 4, 8)),
+    ("Mixtral 8 x 28672 x 4096 + 8 x 4096 x 14336", 8, 14336, 4096, 2, (1, 4, 16, 64, 128)),
+    ("128 x 1536 x 2048 + 128 x 2048 x 768", 128, 768, 2048, 8, (1, 4, 8, 16, 64, 128)),
     ("256 x 4096 x 7168 + 256 x 7168 x 2048", 256, 2048, 7168, 8, (1, 4, 8)),
 ]
 
@@ -68,7 +70,8 @@ def main():
         "x is [T, H], routing weights fp32")
     say(f"{'shape':>44s} {'T':>2s} {'S':>2s} {'fused block':>24s} {'parent block':>24s} {'saved':>7s} {'ratio':>6s} "
         f"{'gated launch':>24s} {'plain launch':>24s} {'gated-plain':>11s} {'fused2 block':>24s} {'down+sum':>24s} {'combine':>24s} "
-        f"{'down saved':>10s} {'tokens block':>24s} {'gate_up launch':>24s} {'gated/gate_up':>13s} {'fused2/tokens':>13s}")
+        f"{'down saved':>10s} {'tokens block':>24s} {'gate_up launch':>24s} {'gated/gate_up':>13s} {'fused2/tokens':>13s} "
+        f"{'batched block':>24s} {'gated16 launch':>24s} {'fused/batched':>13s} {'gated/gated16':>13s}")
     gen = torch.Generator(device="cuda").manual_seed(0)
     for label, E, I, H, S, Ts in SHAPES:
         per_block = (2 * I * H + H * I) // 2 + (2 * I * H + H * I) // BS * 4     # one expert's bytes of both stacks
@@ -134,7 +137,17 @@ def main():
                     gu, gs, _, _ = stacks[c % L]
                     bnb.matmul_4bit_experts_gate_up(x, gu, gs, ids)
 
-            legs = [fused, parent, gated, plain, fused2, down_sum, combine, tokens, gate_up]
+            def batched():
+                for c in range(calls):
+                    gu, gs, dn, ds = stacks[c % L]
+                    bnb.moe_ffn_4bit_batched(x, gu, gs, dn, ds, ids, w)
+
+            def gated16():
+                for c in range(calls):
+                    gu, gs, _, _ = stacks[c % L]
+                    bnb.matmul_4bit_experts_batched(x, gu, gs, ids, gated="chunked")
+
+            legs = [fused, parent, gated, plain, fused2, down_sum, combine, tokens, gate_up, batched, gated16]
             graphs = [capture(fn) for fn in legs]
             samples = [[] for _ in legs]
             reps = [max(2, int(10000.0 / (timed(g, calls, 1) * calls)) + 1) for g in graphs]
@@ -146,7 +159,8 @@ def main():
             med = [statistics.median(s) for s in samples]
             say(f"{label:>44s} {T:>2d} {S:>2d} {cols[0]:>24s} {cols[1]:>24s} {med[1] - med[0]:7.2f} {med[1] / med[0]:5.2f}x "
                 f"{cols[2]:>24s} {cols[3]:>24s} {med[2] - med[3]:+11.2f} {cols[4]:>24s} {cols[5]:>24s} {cols[6]:>24s} {med[5] - med[6]:10.2f} "
-                f"{cols[7]:>24s} {cols[8]:>24s} {med[2] / med[8]:12.2f}x {med[4] / med[7]:12.2f}x")
+                f"{cols[7]:>24s} {cols[8]:>24s} {med[2] / med[8]:12.2f}x {med[4] / med[7]:12.2f}x "
+                f"{cols[9]:>24s} {cols[10]:>24s} {med[0] / med[9]:12.2f}x {med[2] / med[10]:12.2f}x")
             del graphs
         del stacks
         torch.cuda.empty_cache()
