@@ -262,6 +262,85 @@ if _define(
         torch._check(out.dtype == dtype, lambda: f"Expected out.dtype == {dtype}, got {out.dtype}")
 
 
+# ---------------------------------------------------------------------------------------------- LLM.int8() (inference)
+# The reference's schemas (bitsandbytes/_ops.py:9-139), string for string. A [*, K] and B [N, K] are int8 and row-major; row_stats [M]
+# and col_stats [N] are the fp32 row maxima the operands were quantized with.
+def _int8_out_shape(A, B):
+    return (*A.shape[:-1], B.shape[0])
+
+
+def _check_int8_operands(A, B):
+    torch._check(A.dtype == torch.int8, lambda: f"A must be int8, got {A.dtype}")
+    torch._check(B.dtype == torch.int8, lambda: f"B must be int8, got {B.dtype}")
+    torch._check(B.dim() == 2 and A.dim() >= 1 and A.shape[-1] == B.shape[1],
+                 lambda: f"A [*, K] and B [N, K] must share K, got {tuple(A.shape)} and {tuple(B.shape)}")
+
+
+if _define("bitsandbytes::int8_vectorwise_quant", "(Tensor A, float threshold=0.0) -> (Tensor, Tensor, Tensor?)"):
+
+    @register_fake("bitsandbytes::int8_vectorwise_quant")
+    def _(A: torch.Tensor, threshold=0.0):
+        q = torch.empty(A.shape, device=A.device, dtype=torch.int8)
+        stats = torch.empty(A.numel() // A.shape[-1], device=A.device, dtype=torch.float32)
+        if threshold == 0.0:
+            return q, stats, None
+        # (the number of outlier columns is known on the device only)
+        return q, stats, A.new_empty(torch.library.get_ctx().new_dynamic_size(), dtype=torch.int64)
+
+
+if _define("bitsandbytes::int8_linear_matmul", "(Tensor A, Tensor B) -> Tensor"):
+
+    @register_fake("bitsandbytes::int8_linear_matmul")
+    def _(A: torch.Tensor, B: torch.Tensor):
+        _check_int8_operands(A, B)
+        return torch.empty(_int8_out_shape(A, B), device=A.device, dtype=torch.int32)
+
+
+if _define("bitsandbytes::int8_linear_matmul.out", "(Tensor A, Tensor B, Tensor! out) -> ()"):
+
+    @register_fake("bitsandbytes::int8_linear_matmul.out")
+    def _(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor):
+        _check_int8_operands(A, B)
+        shape = _int8_out_shape(A, B)
+        torch._check(out.shape == shape, lambda: f"Expected out.shape == {shape}, got {out.shape}")
+        torch._check(out.device == A.device, lambda: f"Expected out.device == {A.device}, got {out.device}")
+        torch._check(out.dtype == torch.int32, lambda: f"Expected out.dtype == int32, got {out.dtype}")
+
+
+if _define("bitsandbytes::int8_mm_dequant",
+           "(Tensor A, Tensor row_stats, Tensor col_stats, ScalarType? dtype=None, Tensor? bias=None) -> Tensor"):
+
+    @register_fake("bitsandbytes::int8_mm_dequant")
+    def _(A, row_stats, col_stats, dtype: Optional[torch.dtype] = None, bias: Optional[torch.Tensor] = None):
+        torch._check(A.dtype == torch.int32, lambda: f"A must be int32, got {A.dtype}")
+        return torch.empty_like(A, dtype=dtype or torch.float16)
+
+
+if _define("bitsandbytes::int8_scaled_mm",
+           "(Tensor A, Tensor B, Tensor row_stats, Tensor col_stats, Tensor? bias=None, ScalarType? dtype=None) -> Tensor"):
+
+    @register_fake("bitsandbytes::int8_scaled_mm")
+    def _(A, B, row_stats, col_stats, bias: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None):
+        return torch.empty(_int8_out_shape(A, B), device=A.device, dtype=dtype or torch.float16)
+
+
+if _define("bitsandbytes::int8_mixed_scaled_mm",
+           "(Tensor A, Tensor CA, Tensor CB, Tensor SCA, Tensor SCB, Tensor? outlier_cols=None, Tensor? bias=None) -> (Tensor, Tensor?)"):
+
+    @register_fake("bitsandbytes::int8_mixed_scaled_mm")
+    def _(A, CA, CB, SCA, SCB, outlier_cols: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
+        out = torch.empty(_int8_out_shape(CA, CB), device=A.device, dtype=A.dtype)
+        return out, A.new_empty(torch.library.get_ctx().new_dynamic_size(), dtype=torch.int64)
+
+
+if _define("bitsandbytes::int8_vectorwise_dequant", "(Tensor A, Tensor stats) -> Tensor"):
+
+    @register_fake("bitsandbytes::int8_vectorwise_dequant")
+    def _(A: torch.Tensor, stats: torch.Tensor):
+        torch._check(A.dtype == torch.int8, lambda: f"A must be int8, got {A.dtype}")
+        return torch.empty_like(A, dtype=torch.float32)
+
+
 __all__ = ["register_kernel", "register_fake", "prod"]
 
 

@@ -931,6 +931,154 @@ def _(logits, top_k: int, n_group: int, topk_group: int, group_score: str, scori
     return ids, weights
 
 
+# ------------------------------------------------------------------------------------------ LLM.int8() (inference)
+# csrc/int8_quant.hip and csrc/gemm_int8.hip behind the reference's int8 ops. "cuda" kernels only: on CPU tensors the ops raise.
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+@register_kernel("bitsandbytes::int8_vectorwise_quant", "cuda")
+def _(A: torch.Tensor, threshold=0.0):
+    """One launch (one workgroup per row). threshold > 0 also returns the sorted outlier columns, found with torch as the reference does:
+    their number sizes a tensor, which SYNCHRONISES the host with the device - the threshold path cannot be captured in a graph."""
+    if A.dtype not in _DT_CODE:
+        raise ValueError(f"int8_vectorwise_quant: A must be float16, bfloat16 or float32, got {A.dtype}")
+    if A.dim() < 1 or A.shape[-1] == 0:
+        raise ValueError(f"int8_vectorwise_quant: A must be [*, cols] with cols >= 1, got {tuple(A.shape)}")
+    A = A.contiguous()
+    cols = A.shape[-1]
+    rows = A.numel() // cols
+    q = torch.empty(A.shape, device=A.device, dtype=torch.int8)
+    stats = torch.empty(rows, device=A.device, dtype=torch.float32)
+    threshold = float(threshold)
+    with _device_of(A):
+        from ..cextension import Int8QuantArgs
+
+        args = Int8QuantArgs(ct.sizeof(Int8QuantArgs), _DT_CODE[A.dtype], max(threshold, 0.0), rows, cols, A.data_ptr(), q.data_ptr(),
+                             stats.data_ptr(), _stream(A))
+        if lib.bnb_mi355x_int8_vectorwise_quant(ct.byref(args)) != 0:
+            raise ValueError("int8_vectorwise_quant: the library refused the call (its message is on stderr)")
+    if threshold <= 0.0:
+        return q, stats, None
+    outlier_cols = torch.argwhere((A.reshape(rows, cols).abs() >= threshold).any(dim=0)).view(-1)
+    if rows > 1 and outlier_cols.numel():
+        q.view(rows, cols)[:, outlier_cols] = 0
+    return q, stats, outlier_cols
+
+
+def _gemm_int8(A, B, out, row_stats=None, col_stats=None, bias=None) -> bool:
+    """One launch of gemm_int8_kernel into `out` (int32: the plain product; a float dtype: the dequant epilogue). False, with nothing
+    launched: K is not a multiple of 16 or is above 131056 - the caller takes the reference's fallback."""
+    from ..cextension import INT8_OK, INT8_REFUSED_K, GemmInt8Args
+
+    K, N = A.shape[-1], B.shape[0]
+    M = A.numel() // K if K else 0
+    dequant = out.dtype != torch.int32
+    args = GemmInt8Args(ct.sizeof(GemmInt8Args), 1 if dequant else 0, _DT_CODE[out.dtype] if dequant else 0,
+                        _DT_CODE[bias.dtype] if bias is not None else 0, M, N, K, A.data_ptr(), B.data_ptr(), _ptr(row_stats), _ptr(col_stats),
+                        _ptr(bias), out.data_ptr(), _stream(A))
+    rc = lib.bnb_mi355x_gemm_int8(ct.byref(args))
+    if rc not in (INT8_OK, INT8_REFUSED_K):
+        raise ValueError("gemm_int8: the library refused the call (its message is on stderr)")
+    return rc == INT8_OK
+
+
+def _check_int8_matmul(A, B):
+    if A.dtype != torch.int8 or B.dtype != torch.int8:
+        raise ValueError(f"A and B must be int8, got {A.dtype} and {B.dtype}")
+    if B.dim() != 2 or A.dim() < 1 or A.shape[-1] != B.shape[1] or B.device != A.device:
+        raise ValueError(f"A [*, K] and B [N, K] must share K and the device, got {tuple(A.shape)} and {tuple(B.shape)}")
+    return _aligned16(A), _aligned16(B)
+
+
+def _int8_linear_matmul_impl(A, B, out):
+    A, B = _check_int8_matmul(A, B)
+    with _device_of(A):
+        if not _gemm_int8(A, B, out):
+            # the reference's own fallback (backends/default/ops.py:134-139): an fp32 matmul, INEXACT once a sum passes 2^24
+            out.copy_(torch.matmul(A.float(), B.float().t()).to(torch.int32))
+    return out
+
+
+@register_kernel("bitsandbytes::int8_linear_matmul", "cuda")
+def _(A: torch.Tensor, B: torch.Tensor):
+    return _int8_linear_matmul_impl(A, B, torch.empty((*A.shape[:-1], B.shape[0]), device=A.device, dtype=torch.int32))
+
+
+@register_kernel("bitsandbytes::int8_linear_matmul.out", "cuda")
+def _(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor):
+    if out.dtype != torch.int32 or tuple(out.shape) != (*A.shape[:-1], B.shape[0]) or out.device != A.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous int32 tensor {(*A.shape[:-1], B.shape[0])} on A's device")
+    _int8_linear_matmul_impl(A, B, out)
+
+
+def _check_int8_stats(M, N, row_stats, col_stats, bias, dtype, device):
+    dtype = dtype or torch.float16
+    if dtype not in _DT_CODE:
+        raise ValueError(f"dtype must be float16, bfloat16 or float32, got {dtype}")
+    for name, t, n in (("row_stats", row_stats, M), ("col_stats", col_stats, N)):
+        if t.dtype != torch.float32 or t.numel() != n or t.device != device:
+            raise ValueError(f"{name} must hold {n} float32 values on the operands' device, got {t.dtype} {tuple(t.shape)}")
+    if bias is not None and (bias.dtype not in _DT_CODE or bias.numel() != N or bias.device != device):
+        raise ValueError(f"bias must hold N = {N} 16/32-bit float values on the operands' device, got {bias.dtype} {tuple(bias.shape)}")
+    return dtype, row_stats.contiguous(), col_stats.contiguous(), bias if bias is None else bias.contiguous()
+
+
+@register_kernel("bitsandbytes::int8_mm_dequant", "cuda")
+def _(A: torch.Tensor, row_stats: torch.Tensor, col_stats: torch.Tensor, dtype: Optional[torch.dtype] = None, bias: Optional[torch.Tensor] = None):
+    if A.dtype != torch.int32 or A.dim() < 1:
+        raise ValueError(f"A must be an int32 tensor [*, N], got {A.dtype} {tuple(A.shape)}")
+    A = A.contiguous()
+    N = A.shape[-1]
+    M = A.numel() // N if N else 0
+    dtype, row_stats, col_stats, bias = _check_int8_stats(M, N, row_stats, col_stats, bias, dtype, A.device)
+    out = torch.empty(A.shape, device=A.device, dtype=dtype)
+    with _device_of(A):
+        from ..cextension import Int8MmDequantArgs
+
+        args = Int8MmDequantArgs(ct.sizeof(Int8MmDequantArgs), _DT_CODE[dtype], _DT_CODE[bias.dtype] if bias is not None else 0, M, N, A.data_ptr(),
+                                 row_stats.data_ptr(), col_stats.data_ptr(), _ptr(bias), out.data_ptr(), _stream(A))
+        if lib.bnb_mi355x_int8_mm_dequant(ct.byref(args)) != 0:
+            raise ValueError("int8_mm_dequant: the library refused the call (its message is on stderr)")
+    return out
+
+
+@register_kernel("bitsandbytes::int8_scaled_mm", "cuda")
+def _(A: torch.Tensor, B: torch.Tensor, row_stats: torch.Tensor, col_stats: torch.Tensor, bias: Optional[torch.Tensor] = None,
+      dtype: Optional[torch.dtype] = None):
+    """ONE launch: the int8 matmul with the dequantization as its epilogue (a K the kernel refuses: the fallback matmul, then the
+    standalone dequantization kernel - the same bits wherever the fallback's fp32 sums are exact)."""
+    A, B = _check_int8_matmul(A, B)
+    N, K = B.shape
+    dtype, row_stats, col_stats, bias = _check_int8_stats(A.numel() // K if K else 0, N, row_stats, col_stats, bias, dtype, A.device)
+    out = torch.empty((*A.shape[:-1], N), device=A.device, dtype=dtype)
+    with _device_of(A):
+        if _gemm_int8(A, B, out, row_stats, col_stats, bias):
+            return out
+    return torch.ops.bitsandbytes.int8_mm_dequant.default(torch.ops.bitsandbytes.int8_linear_matmul.default(A, B), row_stats, col_stats,
+                                                          dtype=dtype, bias=bias)
+
+
+@register_kernel("bitsandbytes::int8_vectorwise_dequant", "cuda")
+def _(A: torch.Tensor, stats: torch.Tensor):
+    # (not a hot path: the outlier columns of a weight, once per mixed call) 7.874015718698502e-3 = 1 / 127
+    return A * stats.view(-1, 1) * 7.874015718698502e-3
+
+
+@register_kernel("bitsandbytes::int8_mixed_scaled_mm", "cuda")
+def _(A: torch.Tensor, CA: torch.Tensor, CB: torch.Tensor, SCA: torch.Tensor, SCB: torch.Tensor, outlier_cols: Optional[torch.Tensor] = None,
+      bias: Optional[torch.Tensor] = None):
+    """The LLM.int8() decomposition: the scaled int8 matmul (one launch) plus, over the outlier columns of A, a 16-bit addmm against
+    those columns of the weight dequantized (CB[:, cols] * SCB[:, None] / 127)."""
+    out = torch.ops.bitsandbytes.int8_scaled_mm.default(CA, CB, SCA, SCB, bias=bias, dtype=A.dtype)
+    if outlier_cols is None or outlier_cols.numel() == 0:
+        return out, torch.empty(0, device=A.device, dtype=A.dtype)
+    sub_a = A.reshape(-1, A.shape[-1])[:, outlier_cols].contiguous()
+    sub_b = torch.ops.bitsandbytes.int8_vectorwise_dequant.default(CB[:, outlier_cols].contiguous(), SCB).to(A.dtype).t()
+    return out.view(-1, out.shape[-1]).addmm(sub_a, sub_b).view(out.shape), sub_a
+
+
 def gemm_4bit_grouped(A: torch.Tensor, mats, blocksize: int, quant_type: str, outs=None):
     """``[A @ dequant(B_i).T (+ bias_i) for i]`` for several packed weights that share the activations, in ONE launch
     (``bnb_mi355x_gemm_4bit_grouped``): of the streaming MFMA kernel at 2 ... 16 rows, of the streaming kernel at M <= 4 where

@@ -95,6 +95,32 @@ class ExpertsMfmaArgs(ct.Structure):
                 ("bias", ct.c_void_p), ("ids", ct.c_void_p), ("row_scale", ct.c_void_p), ("out", ct.c_void_p), ("stream", ct.c_void_p)]
 
 
+class GemmInt8Args(ct.Structure):
+    """``bnb_mi355x_gemm_int8_args`` of include/bnb_mi355x.h; ``struct_bytes`` is ``ctypes.sizeof(GemmInt8Args)``."""
+
+    _fields_ = [("struct_bytes", ct.c_size_t), ("epilogue", ct.c_int), ("out_dtype", ct.c_int), ("bias_dtype", ct.c_int),
+                ("M", ct.c_long), ("N", ct.c_long), ("K", ct.c_long), ("A", ct.c_void_p), ("B", ct.c_void_p), ("row_stats", ct.c_void_p),
+                ("col_stats", ct.c_void_p), ("bias", ct.c_void_p), ("out", ct.c_void_p), ("stream", ct.c_void_p)]
+
+
+class Int8QuantArgs(ct.Structure):
+    """``bnb_mi355x_int8_vectorwise_quant_args`` of include/bnb_mi355x.h."""
+
+    _fields_ = [("struct_bytes", ct.c_size_t), ("dtype", ct.c_int), ("threshold", ct.c_float), ("rows", ct.c_long), ("cols", ct.c_long),
+                ("A", ct.c_void_p), ("q", ct.c_void_p), ("row_stats", ct.c_void_p), ("stream", ct.c_void_p)]
+
+
+class Int8MmDequantArgs(ct.Structure):
+    """``bnb_mi355x_int8_mm_dequant_args`` of include/bnb_mi355x.h."""
+
+    _fields_ = [("struct_bytes", ct.c_size_t), ("out_dtype", ct.c_int), ("bias_dtype", ct.c_int), ("M", ct.c_long), ("N", ct.c_long),
+                ("C", ct.c_void_p), ("row_stats", ct.c_void_p), ("col_stats", ct.c_void_p), ("bias", ct.c_void_p), ("out", ct.c_void_p),
+                ("stream", ct.c_void_p)]
+
+
+INT8_OK, INT8_MALFORMED, INT8_REFUSED_K = 0, 1, 2  # BNB_MI355X_INT8_* of include/bnb_mi355x.h
+
+
 def _declare(dll: ct.CDLL) -> None:
     def sig(names, argtypes, restype=None):
         for n in names:
@@ -149,6 +175,9 @@ def _declare(dll: ct.CDLL) -> None:
     # (one argument block, passed with ctypes.byref(ExpertsMfmaArgs(...)); non-zero: refused, nothing launched)
     sig(["bnb_mi355x_gemm_4bit_experts_mfma"], [_VOID_P], _I32)
     sig(["bnb_mi355x_gemm_4bit_experts_mfma_supported"], [_I32] * 6, _I32)  # (dtype, E, N, K, blocksize, gated)
+    # LLM.int8(): one argument block each (ctypes.byref(Int8QuantArgs / GemmInt8Args / Int8MmDequantArgs)); non-zero: nothing launched
+    # (bnb_mi355x_gemm_int8: INT8_REFUSED_K = take the fallback)
+    sig(["bnb_mi355x_int8_vectorwise_quant", "bnb_mi355x_gemm_int8", "bnb_mi355x_int8_mm_dequant"], [_VOID_P], _I32)
     # (dtype, A, B, absmax, out, bias, M, N = 2 F, K, blocksize, quant_type, stream)
     sig(["bnb_mi355x_gemm_4bit_gated"], [_I32] + [_VOID_P] * 5 + [_I32] * 5 + [_VOID_P])
     sig(["bnb_mi355x_gemm_4bit_gated_supported"], [_I32] * 5, _I32)
@@ -243,6 +272,7 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_gemm_4bit_experts_gate_up", "bnb_mi355x_gemm_4bit_experts_gate_up_supported",
        "bnb_mi355x_gemm_4bit_experts_gate_up_plan",
        "bnb_mi355x_gemm_4bit_experts_mfma", "bnb_mi355x_gemm_4bit_experts_mfma_supported",
+       "bnb_mi355x_int8_vectorwise_quant", "bnb_mi355x_gemm_int8", "bnb_mi355x_int8_mm_dequant",
        "bnb_mi355x_gemm_4bit_gated", "bnb_mi355x_gemm_4bit_gated_supported",
        "bnb_mi355x_gemm_4bit_lora", "bnb_mi355x_gemm_4bit_lora_supported",
        "bnb_mi355x_gemm_4bit_lora_ids", "bnb_mi355x_gemm_4bit_lora_ids_supported",

@@ -166,6 +166,23 @@ __device__ __forceinline__ float nested_scale(float c, float a, float offset) {
     return prod + offset;
 }
 
+// LLM.int8() dequantization of one int32 accumulator, in the order of the reference's default backend
+// (bitsandbytes/backends/default/ops.py:57-61: `A * (row_stats * col_stats) * 6.200124e-05`, `+= bias`, `.to(dtype)`): four fp32
+// operations, each rounded on its own, then ONE conversion to T by the caller. rounded_f32 keeps hipcc from contracting a product
+// into the add behind it or into the conversion. ONE definition: the matmul's epilogue and the standalone int8_mm_dequant kernel
+// (gemm_int8.hip) give the same bits. bias: [N] of bias_dtype (0 fp32, 1 fp16, 2 bf16) or nullptr (no add).
+__device__ __forceinline__ float int8_dequant_f32(int acc, float row_stat, float col_stat, const void* bias, int bias_dtype, long n) {
+    const float stats = rounded_f32(row_stat * col_stat);
+    float v = rounded_f32(rounded_f32(static_cast<float>(acc) * stats) * 6.200124e-05f);
+    if (bias != nullptr) {
+        const float b = bias_dtype == 0   ? static_cast<const float*>(bias)[n]
+                        : bias_dtype == 1 ? static_cast<float>(static_cast<const _Float16*>(bias)[n])
+                                          : static_cast<float>(static_cast<const __bf16*>(bias)[n]);
+        v = rounded_f32(v + b);
+    }
+    return v;
+}
+
 // A zero the compiler cannot see through, materialised at the point of the call. Adding it to the
 // shift amounts of the nibble/byte extraction ties the whole decode to program order *after* this
 // point: without it LLVM hoists the first v_bfe_u32 of the decode above the workgroup barrier and

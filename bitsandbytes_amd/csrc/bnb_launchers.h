@@ -207,6 +207,17 @@ struct MoeTopkGroupedCall {
 bool moe_topk_grouped_supported(int dtype, int rows, int experts, int top_k, int n_group, int topk_group, int group_score);
 bool moe_topk_grouped(const MoeTopkGroupedCall& call, hipStream_t stream);
 
+// int8_quant.hip / gemm_int8.hip (LLM.int8() inference: row-wise quantize, the int8 MFMA matmul with its int32 / dequant epilogues, the
+// standalone dequantization). Every launcher returns one of these; nothing is launched unless it returns kInt8Ok.
+enum Int8Status : int { kInt8Ok = 0, kInt8Malformed = 1, kInt8RefusedK = 2 };
+int int8_vectorwise_quant(int dtype, const void* A, int8_t* q, float* row_stats, long rows, long cols, float threshold, hipStream_t stream);
+int gemm_int8_tiles(int N);
+bool gemm_int8_k_supported(long K);
+int gemm_int8(int epilogue, int out_dtype, const int8_t* A, const int8_t* B, const float* row_stats, const float* col_stats, const void* bias,
+              int bias_dtype, void* out, long M, long N, long K, hipStream_t stream);
+int int8_mm_dequant(int out_dtype, const int* C, const float* row_stats, const float* col_stats, const void* bias, int bias_dtype, void* out,
+                    long M, long N, hipStream_t stream);
+
 // c_api.hip (g_last_gemm_kernel, defined there as well, is declared in bnb_common.h)
 #ifdef BNB_PROFILING
 extern unsigned long long* g_dbg_buf; // profiling builds only: device buffer for the kernels' s_memtime stamps

@@ -328,6 +328,41 @@ int bnb_mi355x_gemm_4bit_experts_mfma_supported(int dtype, int E, int N, int K, 
     return gemm_4bit_experts_mfma_supported(dtype, E, N, K, blocksize, gated) ? 1 : 0;
 }
 
+// ------------------------------------------------------------------ LLM.int8() inference (int8_quant.hip, gemm_int8.hip)
+int bnb_mi355x_int8_vectorwise_quant(const bnb_mi355x_int8_vectorwise_quant_args* args) {
+    const bool block_ok = args != nullptr && args->struct_bytes == sizeof(bnb_mi355x_int8_vectorwise_quant_args);
+    const int rc = block_ok ? int8_vectorwise_quant(args->dtype, args->A, args->q, args->row_stats, args->rows, args->cols, args->threshold, S(args->stream))
+                            : static_cast<int>(kInt8Malformed);
+    if (rc != kInt8Ok)
+        fprintf(stderr, "bitsandbytes_amd: int8_vectorwise_quant: refused (struct_bytes %zu of %zu; dtype 0 / 1 / 2, rows and cols below 2^31, A, q, row_stats not NULL, threshold not NaN)\n",
+                args == nullptr ? static_cast<size_t>(0) : args->struct_bytes, sizeof(bnb_mi355x_int8_vectorwise_quant_args));
+    return rc;
+}
+// (one argument block; BNB_MI355X_INT8_REFUSED_K is an answer, not an error: it prints nothing)
+int bnb_mi355x_gemm_int8(const bnb_mi355x_gemm_int8_args* args) {
+    if (args == nullptr || args->struct_bytes != sizeof(bnb_mi355x_gemm_int8_args)) {
+        fprintf(stderr, "bitsandbytes_amd: gemm_int8: struct_bytes is %zu, this library's bnb_mi355x_gemm_int8_args has %zu\n",
+                args == nullptr ? static_cast<size_t>(0) : args->struct_bytes, sizeof(bnb_mi355x_gemm_int8_args));
+        return kInt8Malformed;
+    }
+    const int rc = gemm_int8(args->epilogue, args->out_dtype, args->A, args->B, args->row_stats, args->col_stats, args->bias, args->bias_dtype,
+                             args->out, args->M, args->N, args->K, S(args->stream));
+    if (rc == kInt8Malformed)
+        fprintf(stderr, "bitsandbytes_amd: gemm_int8: refused epilogue %d, out_dtype %d, bias_dtype %d, M=%ld, N=%ld, K=%ld (epilogue 0 / 1; dtypes 0 / 1 / 2; M, N below 2^31; A, B, out not NULL, A and B 16-byte aligned; row_stats and col_stats with epilogue 1)\n",
+                args->epilogue, args->out_dtype, args->bias_dtype, args->M, args->N, args->K);
+    return rc;
+}
+int bnb_mi355x_int8_mm_dequant(const bnb_mi355x_int8_mm_dequant_args* args) {
+    const bool block_ok = args != nullptr && args->struct_bytes == sizeof(bnb_mi355x_int8_mm_dequant_args);
+    const int rc = block_ok ? int8_mm_dequant(args->out_dtype, args->C, args->row_stats, args->col_stats, args->bias, args->bias_dtype, args->out, args->M,
+                                              args->N, S(args->stream))
+                            : static_cast<int>(kInt8Malformed);
+    if (rc != kInt8Ok)
+        fprintf(stderr, "bitsandbytes_amd: int8_mm_dequant: refused (struct_bytes %zu of %zu; dtypes 0 / 1 / 2; C, row_stats, col_stats, out not NULL)\n",
+                args == nullptr ? static_cast<size_t>(0) : args->struct_bytes, sizeof(bnb_mi355x_int8_mm_dequant_args));
+    return rc;
+}
+
 // ------------------------------------------------------------------ gated gemm_4bit (dense FFN: silu(gate) * up as the epilogue)
 void bnb_mi355x_gemm_4bit_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N,
                                 int K, int blocksize, int quant_type, bnb_stream_t s) {

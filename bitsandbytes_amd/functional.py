@@ -612,6 +612,33 @@ def gemv_4bit(A: Tensor, B: Tensor, out: Optional[Tensor] = None, transposed_A=F
     return torch.ops.bitsandbytes.gemv_4bit.default(*args)
 
 
+# ---------------------------------------------------------------------------------------------- LLM.int8() (inference)
+def int8_vectorwise_quant(A: Tensor, threshold=0.0):
+    """Row-wise int8 quantization (reference functional.py:1655-1673): ``(q int8, row_stats fp32, outlier_cols or None)``. With
+    ``threshold > 0`` the elements at or above it are left out and the sorted outlier columns come back - at the price of a host
+    synchronisation."""
+    return torch.ops.bitsandbytes.int8_vectorwise_quant.default(A, threshold)
+
+
+def int8_linear_matmul(A: Tensor, B: Tensor, out: Optional[Tensor] = None, dtype=torch.int32) -> Tensor:
+    """``A @ B.T`` for int8 ``A [*, K]`` and ``B [N, K]``, exact in int32 (reference functional.py:1536-1559)."""
+    if out is not None:
+        torch.ops.bitsandbytes.int8_linear_matmul.out(A, B, out)
+        return out
+    return torch.ops.bitsandbytes.int8_linear_matmul.default(A, B)
+
+
+def int8_mm_dequant(A: Tensor, row_stats: Tensor, col_stats: Tensor, out: Optional[Tensor] = None, bias: Optional[Tensor] = None) -> Tensor:
+    """Dequantizes the int32 result of :func:`int8_linear_matmul` to float16 (reference functional.py:1562-1593)."""
+    result = torch.ops.bitsandbytes.int8_mm_dequant.default(A, row_stats, col_stats, dtype=torch.float16, bias=bias)
+    return result if out is None else out.copy_(result)
+
+
+def int8_vectorwise_dequant(A: Tensor, stats: Tensor) -> Tensor:
+    """int8 ``A`` back to float32 with its row statistics (reference functional.py:1641-1652)."""
+    return torch.ops.bitsandbytes.int8_vectorwise_dequant.default(A, stats)
+
+
 def has_avx512bf16() -> bool:
     """Reference ``functional.has_avx512bf16`` asks its CPU library whether the AVX512-BF16 gemv path exists
     (functional.py:1670-1674). This package ships no CPU kernels, so the answer is always False."""

@@ -4,9 +4,11 @@ from .modules import (
     EmbeddingFP4,
     EmbeddingNF4,
     FFN4bit,
+    Int8Params,
     Linear4bitLoRA,
     Linear4bitMultiLoRA,
     Linear4bit,
+    Linear8bitLt,
     LinearFP4,
     LinearNF4,
     MoERouter,
@@ -15,4 +17,5 @@ from .modules import (
 )
 
 __all__ = ["Linear4bit", "LinearFP4", "LinearNF4", "Params4bit", "Embedding4bit", "EmbeddingFP4", "EmbeddingNF4",
-           "parametrize", "linear4bit_group_forward", "FFN4bit", "Linear4bitLoRA", "Linear4bitMultiLoRA", "MoERouter"]
+           "parametrize", "linear4bit_group_forward", "FFN4bit", "Linear4bitLoRA", "Linear4bitMultiLoRA", "MoERouter",
+           "Linear8bitLt", "Int8Params"]

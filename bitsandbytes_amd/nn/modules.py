@@ -667,6 +667,122 @@ class LinearNF4(Linear4bit):
                          quant_storage, device)
 
 
+class Int8Params(torch.nn.Parameter):
+    """The weight of :class:`Linear8bitLt`: 16/32-bit floats until it reaches a HIP device, then int8 rows (``CB``, the parameter's
+    own data) with their fp32 row maxima beside it (``SCB``)."""
+
+    def __new__(cls, data: Optional[torch.Tensor] = None, requires_grad: bool = False, has_fp16_weights: bool = False,
+                CB: Optional[torch.Tensor] = None, SCB: Optional[torch.Tensor] = None, **kwargs) -> "Int8Params":
+        if has_fp16_weights:
+            raise NotImplementedError("Int8Params(has_fp16_weights=True): this package serves LLM.int8() inference only")
+        if data is None:
+            data = torch.empty(0) if CB is None else CB
+        self = torch.Tensor._make_subclass(cls, data, requires_grad)
+        self.SCB = SCB
+        self.has_fp16_weights = False
+        return self
+
+    @property
+    def CB(self) -> Optional[torch.Tensor]:
+        return self.data if self.data.dtype == torch.int8 else None
+
+    def _moved(self, fn) -> "Int8Params":
+        """The parameter after `fn` (what nn.Module._apply passes: a device move and / or a float cast) - quantized row-wise once
+        its floats land on a HIP device (as float16, like the reference: modules.py:737-748)."""
+        data = fn(self.data)
+        if self.data.dtype == torch.int8:
+            scb = None if self.SCB is None else self.SCB.to(data.device)
+            return Int8Params(data, SCB=scb)
+        if data.device.type != "cuda":
+            return Int8Params(data)
+        q, stats, _ = F.int8_vectorwise_quant(data.contiguous().to(torch.float16))
+        return Int8Params(q, SCB=stats)
+
+    def to(self, *args, **kwargs):
+        device, dtype, non_blocking, _ = torch._C._nn._parse_to(*args, **kwargs)
+        return self._moved(lambda t: t.to(device=device, dtype=dtype if t.is_floating_point() else None, non_blocking=non_blocking))
+
+    def cpu(self):
+        return self.to(device="cpu")
+
+    def cuda(self, device=None, non_blocking: bool = False):
+        return self.to(device="cuda" if device is None else device, non_blocking=non_blocking)
+
+    def __deepcopy__(self, memo):
+        return Int8Params(copy.deepcopy(self.data, memo), SCB=copy.deepcopy(self.SCB, memo))
+
+
+class Linear8bitLt(nn.Linear):
+    """LLM.int8() linear layer, inference only (reference modules.py:1018-1194). Load float weights (or a ``load_in_8bit`` checkpoint:
+    keys ``weight`` int8, ``SCB``, optional ``weight_format`` = row) and move it to the HIP device. ``threshold == 0``: the forward is
+    two launches - quantize x row-wise, int8 matmul with the dequantization and the bias as its epilogue - without a host
+    synchronisation (it can be captured in a graph). ``threshold > 0``: the mixed decomposition - activation columns holding a
+    value at or above the threshold go through a 16-bit matmul instead; finding them synchronises."""
+
+    def __init__(self, input_features, output_features, bias=True, has_fp16_weights=False, threshold=0.0, index=None, device=None):
+        if has_fp16_weights:
+            raise NotImplementedError("Linear8bitLt(has_fp16_weights=True): this package serves LLM.int8() inference only")
+        super().__init__(input_features, output_features, bias, device)
+        self.threshold = float(threshold)
+        self.index = index
+        self.weight = Int8Params(self.weight.data)
+        if self.bias is not None:
+            self.bias.requires_grad_(False)
+
+    def _apply(self, fn, recurse=True):
+        # the weight moves (and quantizes) as a whole: nn.Module._apply would keep the parameter object and drop its statistics
+        weight = self._parameters["weight"]
+        self._parameters["weight"] = None
+        try:
+            super()._apply(fn, recurse)
+        finally:
+            self._parameters["weight"] = weight
+        self._parameters["weight"] = weight._moved(fn)
+        return self
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        if self.weight.SCB is not None:
+            destination[prefix + "SCB"] = self.weight.SCB if keep_vars else self.weight.SCB.detach()
+            destination[prefix + "weight_format"] = torch.tensor(0, dtype=torch.uint8)  # "row", the only layout there is
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        fmt = state_dict.get(prefix + "weight_format", "row")
+        fmt = fmt.item() if isinstance(fmt, torch.Tensor) else fmt
+        if fmt not in ("row", 0):
+            raise ValueError(f"Linear8bitLt: only the 'row' weight format is supported, got {fmt!r}")
+        weight, scb = state_dict.get(prefix + "weight"), state_dict.get(prefix + "SCB")
+        own = (prefix + "weight", prefix + "SCB", prefix + "weight_format")
+        quantized = weight is not None and weight.dtype == torch.int8
+        if quantized or self.weight.data.dtype == torch.int8:
+            if not quantized or scb is None or tuple(weight.shape) != (self.out_features, self.in_features) or scb.numel() != self.out_features:
+                error_msgs.append(f"{prefix}weight: a quantized Linear8bitLt loads an int8 weight [{self.out_features}, {self.in_features}] "
+                                  f"with its SCB [{self.out_features}]")
+            else:
+                device = self.weight.device
+                self.weight = Int8Params(weight.detach().to(device).contiguous(), SCB=scb.detach().to(device=device, dtype=torch.float32).reshape(-1))
+            state_dict = {k: v for k, v in state_dict.items() if k not in own}
+            super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+            if prefix + "weight" in missing_keys:  # (loaded above)
+                missing_keys.remove(prefix + "weight")
+            return
+        state_dict = {k: v for k, v in state_dict.items() if k not in own[1:]}
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+    def forward(self, x: torch.Tensor):
+        weight = self.weight
+        if weight.CB is None or weight.SCB is None:
+            raise RuntimeError("Linear8bitLt: the weight is not quantized yet - move the layer to the HIP device first")
+        x2 = x.reshape(-1, x.shape[-1])
+        ops = torch.ops.bitsandbytes
+        q, stats, outlier_cols = ops.int8_vectorwise_quant.default(x2, self.threshold)
+        if self.threshold > 0.0:
+            out = ops.int8_mixed_scaled_mm.default(x2, q, weight.CB, stats, weight.SCB, outlier_cols, self.bias)[0]
+        else:
+            out = ops.int8_scaled_mm.default(q, weight.CB, stats, weight.SCB, self.bias, x.dtype)
+        return out.view(*x.shape[:-1], self.out_features)
+
+
 class MoERouter(nn.Module):
     """The router (gate) of a mixture-of-experts block: ``forward(x)`` returns ``(ids, weights)``, ``[*, top_k]`` int32 and fp32 on
     ``x``'s device - what :func:`bitsandbytes_amd.moe_ffn_4bit` takes as ``expert_ids`` and ``routing_weights`` - in two launches where

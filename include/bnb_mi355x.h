@@ -302,6 +302,64 @@ typedef struct bnb_mi355x_gemm_4bit_experts_mfma_args {
 } bnb_mi355x_gemm_4bit_experts_mfma_args;
 int bnb_mi355x_gemm_4bit_experts_mfma(const bnb_mi355x_gemm_4bit_experts_mfma_args* args);
 int bnb_mi355x_gemm_4bit_experts_mfma_supported(int dtype, int E, int N, int K, int blocksize, int gated);
+/* ------------------------------------------------------------------------------------------------
+ * LLM.int8() inference (csrc/int8_quant.hip, csrc/gemm_int8.hip). dtype codes: 0 fp32, 1 fp16, 2 bf16. All three calls take one argument
+ * block (struct_bytes = sizeof of the block, as bnb_mi355x_gemm_4bit_experts_mfma does), only enqueue
+ * work on `stream`, allocate nothing, and return 0 after the launch (an empty problem: 0, nothing launched) or a non-zero code with
+ * NOTHING launched; they never end the process. The arithmetic is that of the reference's default (torch) backend
+ * (bitsandbytes/backends/default/ops.py:38-61, 142-177), bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+#define BNB_MI355X_INT8_OK 0
+#define BNB_MI355X_INT8_MALFORMED 1 /* outside the preconditions: one line on stderr */
+#define BNB_MI355X_INT8_REFUSED_K 2 /* bnb_mi355x_gemm_int8 only: a K the kernel does not serve (silent: the caller has a fallback) */
+/* Row-wise quantize: A [rows, cols] contiguous -> q int8 [rows, cols], row_stats fp32 [rows] = max |A[r, :]| in fp32;
+ * q = int8(rint(float(A) * (127.0f / row_stats[r]))), IEEE division, ties to even. A row with row_stats 0 gives zeros. threshold > 0:
+ * an element with |a| >= threshold (fp32 compare) is left out of the maximum and written as 0. One workgroup per row. */
+typedef struct bnb_mi355x_int8_vectorwise_quant_args {
+    size_t struct_bytes;       /* sizeof of this struct as the caller was compiled */
+    int dtype;                 /* of A */
+    float threshold;           /* <= 0: none */
+    long rows, cols;
+    const void* A;
+    int8_t* q;
+    float* row_stats;
+    bnb_stream_t stream;
+} bnb_mi355x_int8_vectorwise_quant_args;
+int bnb_mi355x_int8_vectorwise_quant(const bnb_mi355x_int8_vectorwise_quant_args* args);
+/* C[m, n] = sum_k A[m, k] * B[n, k], A [M, K] and B [N, K] int8 row-major and 16-byte aligned, exact in int32, on
+ * v_mfma_i32_16x16x64_i8; any M and N, K a multiple of 16 up to 131056 (128 * 128 * K fits int32) - any other K returns
+ * BNB_MI355X_INT8_REFUSED_K. epilogue 0: out is int32 [M, N]. epilogue 1: out is [M, N] of out_dtype,
+ *     T(((float(C) * (row_stats[m] * col_stats[n])) * 6.200124e-05f) + float(bias[n]))
+ * - four fp32 operations rounded one by one, the add only with a bias (of bias_dtype, any of the three), one conversion to T. The
+ * result is a function of the operands alone: not of the tile height or the CU count. No workspace, no atomics, no memset. */
+typedef struct bnb_mi355x_gemm_int8_args {
+    size_t struct_bytes;       /* sizeof of this struct as the caller was compiled */
+    int epilogue;              /* 0 int32, 1 dequant */
+    int out_dtype, bias_dtype; /* epilogue 1 */
+    long M, N, K;
+    const int8_t* A;
+    const int8_t* B;
+    const float* row_stats;    /* [M], epilogue 1 */
+    const float* col_stats;    /* [N], epilogue 1 */
+    const void* bias;          /* [N] or NULL, epilogue 1 */
+    void* out;
+    bnb_stream_t stream;
+} bnb_mi355x_gemm_int8_args;
+int bnb_mi355x_gemm_int8(const bnb_mi355x_gemm_int8_args* args);
+/* The second step of the two-step API: C int32 [M, N] -> out [M, N] of out_dtype, the arithmetic of epilogue 1 above (the same
+ * device function: the same bits). */
+typedef struct bnb_mi355x_int8_mm_dequant_args {
+    size_t struct_bytes;       /* sizeof of this struct as the caller was compiled */
+    int out_dtype, bias_dtype;
+    long M, N;
+    const int32_t* C;
+    const float* row_stats;    /* [M] */
+    const float* col_stats;    /* [N] */
+    const void* bias;          /* [N] or NULL */
+    void* out;
+    bnb_stream_t stream;
+} bnb_mi355x_int8_mm_dequant_args;
+int bnb_mi355x_int8_mm_dequant(const bnb_mi355x_int8_mm_dequant_args* args);
 /* Dense gated-SiLU FFN: the fused matmul over ONE interleaved matrix B [N = 2 F, K] - gate row i at row 2 i, up row i at row 2 i + 1;
  * bias, if given, [N] in the same layout - with silu(gate) * up as its epilogue. A is [M, K], out is [M, F]:
  *     g = T(acc_g + bias_g), u = T(acc_u + bias_u), out[m, i] = T(float(T(silu(g))) * float(u)),  silu(g) = g / (1 + expf(-g)) in fp32

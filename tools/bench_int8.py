@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""LLM.int8() inference (csrc/int8_quant.hip, csrc/gemm_int8.hip, nn.Linear8bitLt), us per call, against yardsticks in the same process.
+
+Method (tools/bench_moe_ffn.py): every leg is a hipGraph of >= 64 calls that rotate over enough distinct weights that one pass over the
+rotation exceeds the 256 MiB Infinity Cache; HIP events around `reps` replays (regions >= 10 ms); the legs alternate inside one process,
+order reversed every round; median and min ... max of the rounds - read the spread first. Legs, x bf16 [M, K]:
+  quant      int8_vectorwise_quant(x)                                                         1 launch
+  scaled_mm  int8_scaled_mm(q, CB, stats, SCB, dtype=bf16): the matmul with the dequant epilogue 1 launch
+  layer      Linear8bitLt(x), threshold 0                                                     2 launches
+  bf16       F.linear(x, W) on the dequantized weight (hipBLASLt)
+  4bit       this package's Linear4bit (NF4, bf16) at the same shape
+  _int_mm    torch._int_mm(q, CB.t()) and the torch dequantization expression, where this torch build runs it ('raises' otherwise)
+For M <= 16 the scaled_mm column also gives the achieved bytes/s over bench.HBM_PEAK_GBS; the bound there is the N * K weight bytes.
+    python tools/bench_int8.py [--rounds 5] [--quick] [--out profiles/int8_bench.txt]"""
+import argparse
+import math
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as TF
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bitsandbytes_amd as bnb  # noqa: E402
+from bench import HBM_PEAK_GBS  # noqa: E402
+from tools.bench_experts import CACHE_BYTES, capture, timed  # noqa: E402
+
+SHAPES = [(4096, 4096), (11008, 4096), (4096, 11008)]  # (N, K)
+MS = (1, 4, 16, 64, 512, 2048)
+OPS = torch.ops.bitsandbytes
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--quick", action="store_true", help="first M of every shape only")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "int8_bench.txt"), help="the table is also written here ('' for none)")
+    args = ap.parse_args()
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    say(f"# {torch.cuda.get_device_name(0)}, {bnb.lib.bnb_mi355x_version().decode()}, torch {torch.__version__}")
+    say(f"# us per call: median (min ... max) of {args.rounds} rounds; x bf16; %HBM = N * K bytes / time / {HBM_PEAK_GBS:.0f} GB/s (M <= 16)")
+    names = ["quant", "scaled_mm", "layer", "bf16 F.linear", "Linear4bit", "_int_mm+dequant"]
+    say(f"{'N x K':>13s} {'M':>5s} " + " ".join(f"{n:>26s}" for n in names) + f" {'%HBM':>6s} {'bf16/layer':>10s} {'4bit/layer':>10s} {'_int_mm/scaled_mm':>17s}")
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    for N, K in SHAPES:
+        L = max(2, math.ceil(1.25 * CACHE_BYTES / (N * K)))
+        calls = L * math.ceil(64 / L)
+        layers, dense, four = [], [], []
+        for _ in range(L):
+            W = torch.randn(N, K, device="cuda", generator=gen) / K ** 0.5
+            l8 = bnb.nn.Linear8bitLt(K, N, bias=False)
+            l8.weight = bnb.nn.Int8Params(W.cpu())
+            layers.append(l8.to("cuda"))
+            dense.append(OPS.int8_vectorwise_dequant.default(layers[-1].weight.CB, layers[-1].weight.SCB).bfloat16())
+            l4 = bnb.nn.Linear4bit(K, N, bias=False, quant_type="nf4", compute_dtype=torch.bfloat16)
+            l4.weight = bnb.nn.Params4bit(W.bfloat16().cpu(), requires_grad=False, quant_type="nf4", module=l4)
+            four.append(l4.to("cuda"))
+        for M in (MS[:1] if args.quick else MS):
+            x = torch.randn(M, K, device="cuda", generator=gen).bfloat16()
+            q, stats, _ = OPS.int8_vectorwise_quant.default(x, 0.0)
+
+            def quant():
+                for c in range(calls):
+                    OPS.int8_vectorwise_quant.default(x, 0.0)
+
+            def scaled_mm():
+                for c in range(calls):
+                    w = layers[c % L].weight
+                    OPS.int8_scaled_mm.default(q, w.CB, stats, w.SCB, None, torch.bfloat16)
+
+            def layer():
+                for c in range(calls):
+                    layers[c % L](x)
+
+            def bf16():
+                for c in range(calls):
+                    TF.linear(x, dense[c % L])
+
+            def fourbit():
+                for c in range(calls):
+                    four[c % L](x)
+
+            def int_mm():
+                for c in range(calls):
+                    w = layers[c % L].weight
+                    (torch._int_mm(q, w.CB.t()) * (stats[:, None] * w.SCB[None, :]) * 6.200124e-05).bfloat16()
+
+            legs = [quant, scaled_mm, layer, bf16, fourbit, int_mm]
+            graphs = []
+            for fn in legs:
+                try:
+                    graphs.append(capture(fn))
+                except Exception as exc:  # (torch._int_mm refuses small M on this build)
+                    graphs.append(None)
+                    say(f"#   {N} x {K}, M = {M}: {fn.__name__} raises {type(exc).__name__}: {str(exc).splitlines()[0][:120]}")
+                    torch.cuda.synchronize()
+            live = [i for i, g in enumerate(graphs) if g is not None]
+            samples = {i: [] for i in live}
+            reps = {i: max(2, int(10000.0 / (timed(graphs[i], calls, 1) * calls)) + 1) for i in live}
+            for r in range(args.rounds):
+                for i in (live if r % 2 == 0 else live[::-1]):
+                    samples[i].append(timed(graphs[i], calls, reps[i]))
+            med = {i: statistics.median(s) for i, s in samples.items()}
+            cols = [f"{med[i]:9.2f} ({min(samples[i]):.2f}...{max(samples[i]):.2f})" if i in med else "raises" for i in range(len(legs))]
+            hbm = f"{100.0 * N * K / med[1] / 1e3 / HBM_PEAK_GBS:5.1f}%" if M <= 16 else ""
+            vs = f"{med[5] / med[1]:16.2f}x" if 5 in med else f"{'n/a':>17s}"
+            say(f"{f'{N} x {K}':>13s} {M:>5d} " + " ".join(f"{c:>26s}" for c in cols) + f" {hbm:>6s} {med[3] / med[2]:9.2f}x {med[4] / med[2]:9.2f}x {vs}")
+            del graphs
+        del layers, dense, four
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
