@@ -14,10 +14,11 @@ from .autograd import (MatMul4Bit, ffn_4bit, lora_shrink, lora_shrink_ids, matmu
 from .cextension import lib
 from .backends import hip as _hip_backend  # noqa: F401  registers the "cuda"-key (HIP) kernels
 from . import nn  # noqa: F401
+from . import optim  # noqa: F401
 from . import utils  # noqa: F401
 from .parallel import (GraphedBlock, ShardedFFN4bit, ShardedLinear4bit, ShardedLinear4bitChain, ShardedLinear4bitGroup,  # noqa: F401
                        shard_ffn4bit, shard_linear4bit)
 
 __version__ = "0.1.0"
 
-__all__ = ["functional", "nn", "utils", "matmul_4bit", "matmul_4bit_grouped", "matmul_4bit_experts", "matmul_4bit_experts_batched", "matmul_4bit_experts_combine", "matmul_4bit_experts_gate_up", "moe_ffn_4bit", "moe_ffn_4bit_batched", "moe_ffn_4bit_fused", "moe_ffn_4bit_tokens", "matmul_4bit_gated", "ffn_4bit", "matmul_4bit_lora", "lora_shrink", "lora_shrink_ids", "matmul_4bit_lora_ids", "moe_topk", "moe_route", "moe_topk_grouped", "moe_route_grouped", "MatMul4Bit", "lib", "ShardedLinear4bit", "ShardedLinear4bitGroup", "ShardedLinear4bitChain", "ShardedFFN4bit", "GraphedBlock", "shard_linear4bit", "shard_ffn4bit"]
+__all__ = ["functional", "nn", "optim", "utils", "matmul_4bit", "matmul_4bit_grouped", "matmul_4bit_experts", "matmul_4bit_experts_batched", "matmul_4bit_experts_combine", "matmul_4bit_experts_gate_up", "moe_ffn_4bit", "moe_ffn_4bit_batched", "moe_ffn_4bit_fused", "moe_ffn_4bit_tokens", "matmul_4bit_gated", "ffn_4bit", "matmul_4bit_lora", "lora_shrink", "lora_shrink_ids", "matmul_4bit_lora_ids", "moe_topk", "moe_route", "moe_topk_grouped", "moe_route_grouped", "MatMul4Bit", "lib", "ShardedLinear4bit", "ShardedLinear4bitGroup", "ShardedLinear4bitChain", "ShardedFFN4bit", "GraphedBlock", "shard_linear4bit", "shard_ffn4bit"]

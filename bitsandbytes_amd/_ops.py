@@ -341,6 +341,43 @@ if _define("bitsandbytes::int8_vectorwise_dequant", "(Tensor A, Tensor stats) ->
         return torch.empty_like(A, dtype=torch.float32)
 
 
+# ---------------------------------------------------------------------------------------------- optimizer updates
+# The reference's schemas (bitsandbytes/_ops.py:409-455), string for string, and its fake kernels: every tensor is updated in place.
+def _check_optimizer_g_p(g, p):
+    torch._check(g.numel() == p.numel(), lambda: f"g and p must have the same number of elements, got {g.numel()} and {p.numel()}")
+    torch._check(g.dtype in _FLOAT_DTYPES, lambda: f"g must be bfloat16, float16, or float32, got {g.dtype}")
+    torch._check(g.dtype == p.dtype, lambda: f"Expected all tensors to have the same dtype, got g.dtype={g.dtype}, p.dtype={p.dtype}")
+
+
+if _define(
+    "bitsandbytes::optimizer_update_32bit",
+    "(str optimizer_name, Tensor(a0!) g, Tensor(a1!) p, Tensor(a2!) state1, Tensor(a3!)? state2, Tensor(a4!)? unorm_vec, float max_unorm, float param_norm, float beta1, float beta2, float beta3, float alpha, float eps, float weight_decay, int step, float lr, float gnorm_scale, bool skip_zeros=False) -> ()",
+):
+
+    @register_fake("bitsandbytes::optimizer_update_32bit")
+    def _(optimizer_name: str, g, p, state1, state2, unorm_vec, max_unorm: float, param_norm: float, beta1: float, beta2: float, beta3: float,
+          alpha: float, eps: float, weight_decay: float, step: int, lr: float, gnorm_scale: float, skip_zeros=False) -> None:
+        _check_optimizer_g_p(g, p)
+
+
+if _define(
+    "bitsandbytes::optimizer_update_8bit_blockwise",
+    "(str optimizer_name, Tensor(a0!) g, Tensor(a1!) p, Tensor(a2!) state1, Tensor(a3!)? state2, float beta1, float beta2, float beta3, float alpha, float eps, int step, float lr, Tensor(a4!) qmap1, Tensor(a5!)? qmap2, Tensor(a6!) absmax1, Tensor(a7!)? absmax2, float weight_decay, float gnorm_scale, bool skip_zeros=False) -> ()",
+):
+
+    @register_fake("bitsandbytes::optimizer_update_8bit_blockwise")
+    def _(optimizer_name: str, g, p, state1, state2, beta1: float, beta2: float, beta3: float, alpha: float, eps: float, step: int, lr: float,
+          qmap1, qmap2, absmax1, absmax2, weight_decay: float, gnorm_scale: float, skip_zeros=False) -> None:
+        _check_optimizer_g_p(g, p)
+        torch._check(state1.dtype == torch.uint8, lambda: f"state1 must be uint8, got {state1.dtype}")
+        torch._check(qmap1.dtype == absmax1.dtype == torch.float32,
+                     lambda: f"Expected qmap1 and absmax1 to be float32, got qmap1.dtype={qmap1.dtype}, absmax1.dtype={absmax1.dtype}")
+        if state2 is not None:
+            torch._check(state2.dtype == torch.uint8, lambda: f"state2 must be uint8, got {state2.dtype}")
+            torch._check(qmap2.dtype == absmax2.dtype == torch.float32,
+                         lambda: f"Expected qmap2 and absmax2 to be float32, got qmap2.dtype={qmap2.dtype}, absmax2.dtype={absmax2.dtype}")
+
+
 __all__ = ["register_kernel", "register_fake", "prod"]
 
 

@@ -1079,6 +1079,73 @@ def _(A: torch.Tensor, CA: torch.Tensor, CB: torch.Tensor, SCA: torch.Tensor, SC
     return out.view(-1, out.shape[-1]).addmm(sub_a, sub_b).view(out.shape), sub_a
 
 
+# ------------------------------------------------------------------------------------------ optimizer updates
+# csrc/optim8.hip behind the reference's two optimizer ops: ONE launch per parameter tensor, everything updated in place, no host
+# synchronisation. The scalars that depend on step, lr or the betas are computed here in Python double and rounded to fp32 once
+# (ctypes.c_float), as the ledger of DESIGN.md §3.19 states them.
+_OPTIM_NOT_SERVED = {"ademamix": "AdEMAMix (two first moments and beta3 / alpha)", "lamb": "LAMB (needs a global update-norm pass)",
+                     "lars": "LARS (needs a global update-norm pass)"}
+
+
+def _optimizer_update(entry: str, optimizer_name, g, p, state1, state2, qmap1, qmap2, absmax1, absmax2, beta1, beta2, eps, weight_decay, step,
+                      lr, gnorm_scale):
+    from ..cextension import OPTIMIZER_CODES, OptimizerUpdateArgs
+
+    if optimizer_name in _OPTIM_NOT_SERVED:
+        raise NotImplementedError(f"{entry}: optimizer {optimizer_name!r} is not served: {_OPTIM_NOT_SERVED[optimizer_name]}; "
+                                  f"served: {sorted(OPTIMIZER_CODES)}")
+    if optimizer_name not in OPTIMIZER_CODES:
+        raise ValueError(f"{entry}: unknown optimizer {optimizer_name!r}; served: {sorted(OPTIMIZER_CODES)}")
+    if step < 1:
+        raise ValueError(f"{entry}: step counts from 1, got {step}")
+    eight_bit = qmap1 is not None
+    two = optimizer_name == "adam"
+    n = p.numel()
+    if g.dtype not in _DT_CODE or g.dtype != p.dtype or g.numel() != n or g.device != p.device:
+        raise ValueError(f"{entry}: g and p must be float16, bfloat16 or float32 tensors of one dtype, size and device, got {g.dtype} "
+                         f"{tuple(g.shape)} and {p.dtype} {tuple(p.shape)}")
+    if not (g.is_contiguous() and p.is_contiguous()):
+        raise ValueError(f"{entry}: g and p must be contiguous (p is updated in place)")
+    state_dtype = torch.uint8 if eight_bit else torch.float32
+    states = [("state1", state1, qmap1, absmax1)] + ([("state2", state2, qmap2, absmax2)] if two else [])
+    for name, s, qmap, absmax in states:
+        if s is None or s.dtype != state_dtype or s.numel() != n or s.device != p.device or not s.is_contiguous():
+            raise ValueError(f"{entry}: {name} must be a contiguous {state_dtype} tensor of {n} elements on p's device")
+        if not eight_bit:
+            continue
+        if qmap is None or qmap.dtype != torch.float32 or qmap.numel() != 256 or qmap.device != p.device or not qmap.is_contiguous():
+            raise ValueError(f"{entry}: the qmap of {name} must hold 256 float32 values on p's device")
+        if absmax is None or absmax.dtype != torch.float32 or absmax.numel() < -(n // -256) or absmax.device != p.device or not absmax.is_contiguous():
+            raise ValueError(f"{entry}: the absmax of {name} must hold ceil(n / 256) = {-(n // -256)} float32 values on p's device")
+    correction1 = 1.0 - beta1 ** step
+    args = OptimizerUpdateArgs(ct.sizeof(OptimizerUpdateArgs), OPTIMIZER_CODES[optimizer_name], _DT_CODE[p.dtype], n, g.data_ptr(), p.data_ptr(),
+                               state1.data_ptr(), _ptr(state2) if two else None, _ptr(qmap1), _ptr(qmap2) if two else None, _ptr(absmax1),
+                               _ptr(absmax2) if two else None, int(step), gnorm_scale, beta1, 1.0 - beta1, beta2, 1.0 - beta2,
+                               (1.0 - beta2 ** step) ** 0.5, eps, weight_decay, 1.0 - lr * weight_decay,
+                               -lr / correction1 if correction1 != 0.0 else 0.0, -lr, _stream(p))
+    with _device_of(p):
+        if getattr(lib, f"bnb_mi355x_{entry}")(ct.byref(args)) != 0:
+            raise ValueError(f"{entry}: the library refused the call (its message is on stderr)")
+
+
+@register_kernel("bitsandbytes::optimizer_update_8bit_blockwise", "cuda")
+def _(optimizer_name: str, g, p, state1, state2, beta1: float, beta2: float, beta3: float, alpha: float, eps: float, step: int, lr: float,
+      qmap1, qmap2, absmax1, absmax2, weight_decay: float, gnorm_scale: float, skip_zeros=False) -> None:
+    """skip_zeros is accepted and ignored, as both reference backends do."""
+    _optimizer_update("optimizer_update_8bit_blockwise", optimizer_name, g, p, state1, state2, qmap1, qmap2, absmax1, absmax2, beta1, beta2, eps,
+                      weight_decay, step, lr, gnorm_scale)
+
+
+@register_kernel("bitsandbytes::optimizer_update_32bit", "cuda")
+def _(optimizer_name: str, g, p, state1, state2, unorm_vec, max_unorm: float, param_norm: float, beta1: float, beta2: float, beta3: float,
+      alpha: float, eps: float, weight_decay: float, step: int, lr: float, gnorm_scale: float, skip_zeros=False) -> None:
+    """fp32 states, the ledger of the 8-bit update without the codec (the same kernel template)."""
+    if max_unorm > 0.0:
+        raise NotImplementedError("optimizer_update_32bit: max_unorm > 0 (update-norm clipping) is not served: it needs a global norm pass")
+    _optimizer_update("optimizer_update_32bit", optimizer_name, g, p, state1, state2, None, None, None, None, beta1, beta2, eps, weight_decay,
+                      step, lr, gnorm_scale)
+
+
 def gemm_4bit_grouped(A: torch.Tensor, mats, blocksize: int, quant_type: str, outs=None):
     """``[A @ dequant(B_i).T (+ bias_i) for i]`` for several packed weights that share the activations, in ONE launch
     (``bnb_mi355x_gemm_4bit_grouped``): of the streaming MFMA kernel at 2 ... 16 rows, of the streaming kernel at M <= 4 where

@@ -121,6 +121,20 @@ class Int8MmDequantArgs(ct.Structure):
 INT8_OK, INT8_MALFORMED, INT8_REFUSED_K = 0, 1, 2  # BNB_MI355X_INT8_* of include/bnb_mi355x.h
 
 
+class OptimizerUpdateArgs(ct.Structure):
+    """``bnb_mi355x_optimizer_update_args`` of include/bnb_mi355x.h (both optimizer entry points take it)."""
+
+    _fields_ = [("struct_bytes", ct.c_size_t), ("optimizer", ct.c_int), ("dtype", ct.c_int), ("n", ct.c_long), ("g", ct.c_void_p),
+                ("p", ct.c_void_p), ("state1", ct.c_void_p), ("state2", ct.c_void_p), ("qmap1", ct.c_void_p), ("qmap2", ct.c_void_p),
+                ("absmax1", ct.c_void_p), ("absmax2", ct.c_void_p), ("step", ct.c_int), ("gnorm_scale", ct.c_float), ("beta1", ct.c_float),
+                ("one_minus_beta1", ct.c_float), ("beta2", ct.c_float), ("one_minus_beta2", ct.c_float), ("sqrt_correction2", ct.c_float),
+                ("eps", ct.c_float), ("weight_decay", ct.c_float), ("decay", ct.c_float), ("step_scale", ct.c_float), ("neg_lr", ct.c_float),
+                ("stream", ct.c_void_p)]
+
+
+OPTIMIZER_CODES = {"adam": 0, "momentum": 1, "rmsprop": 2, "adagrad": 3, "lion": 4}  # BNB_MI355X_OPT_* of include/bnb_mi355x.h
+
+
 def _declare(dll: ct.CDLL) -> None:
     def sig(names, argtypes, restype=None):
         for n in names:
@@ -178,6 +192,9 @@ def _declare(dll: ct.CDLL) -> None:
     # LLM.int8(): one argument block each (ctypes.byref(Int8QuantArgs / GemmInt8Args / Int8MmDequantArgs)); non-zero: nothing launched
     # (bnb_mi355x_gemm_int8: INT8_REFUSED_K = take the fallback)
     sig(["bnb_mi355x_int8_vectorwise_quant", "bnb_mi355x_gemm_int8", "bnb_mi355x_int8_mm_dequant"], [_VOID_P], _I32)
+    # the fused optimizer updates: one argument block (ctypes.byref(OptimizerUpdateArgs)); non-zero: nothing launched
+    sig(["bnb_mi355x_optimizer_update_8bit_blockwise", "bnb_mi355x_optimizer_update_32bit"], [_VOID_P], _I32)
+    sig(["bnb_mi355x_optimizer_update_grid"], [ct.c_long], _I32)  # workgroups of that launch for n elements (host logic)
     # (dtype, A, B, absmax, out, bias, M, N = 2 F, K, blocksize, quant_type, stream)
     sig(["bnb_mi355x_gemm_4bit_gated"], [_I32] + [_VOID_P] * 5 + [_I32] * 5 + [_VOID_P])
     sig(["bnb_mi355x_gemm_4bit_gated_supported"], [_I32] * 5, _I32)
@@ -273,6 +290,7 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_gemm_4bit_experts_gate_up_plan",
        "bnb_mi355x_gemm_4bit_experts_mfma", "bnb_mi355x_gemm_4bit_experts_mfma_supported",
        "bnb_mi355x_int8_vectorwise_quant", "bnb_mi355x_gemm_int8", "bnb_mi355x_int8_mm_dequant",
+       "bnb_mi355x_optimizer_update_8bit_blockwise", "bnb_mi355x_optimizer_update_32bit", "bnb_mi355x_optimizer_update_grid",
        "bnb_mi355x_gemm_4bit_gated", "bnb_mi355x_gemm_4bit_gated_supported",
        "bnb_mi355x_gemm_4bit_lora", "bnb_mi355x_gemm_4bit_lora_supported",
        "bnb_mi355x_gemm_4bit_lora_ids", "bnb_mi355x_gemm_4bit_lora_ids_supported",

@@ -218,6 +218,31 @@ int gemm_int8(int epilogue, int out_dtype, const int8_t* A, const int8_t* B, con
 int int8_mm_dequant(int out_dtype, const int* C, const float* row_stats, const float* col_stats, const void* bias, int bias_dtype, void* out,
                     long M, long N, hipStream_t stream);
 
+// optim8.hip (the fused optimizer update: one launch per parameter tensor; the fields of bnb_mi355x_optimizer_update_args).
+// state_bits 8: uint8 codes + fp32 absmax per 256 elements, re-encoded in the launch; 32: fp32 states, no tables, no absmax.
+enum OptimStatus : int { kOptimOk = 0, kOptimMalformed = 1, kOptimRefusedOptimizer = 2, kOptimRefusedDtype = 3 };
+enum OptimId : int { kOptAdam = 0, kOptMomentum = 1, kOptRmsprop = 2, kOptAdagrad = 3, kOptLion = 4 };
+constexpr int kOptim8WorkgroupsPerCu = 4; // the persistent grid: at most this many 4-wavefront workgroups per compute unit
+struct OptimScalars { // computed by the caller in double, rounded to fp32 once
+    float gnorm_scale, beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_correction2, eps, weight_decay, decay, step_scale, neg_lr;
+    int step;
+};
+struct OptimUpdateCall {
+    int optimizer, dtype; // OptimId; g and p: 0 fp32, 1 fp16, 2 bf16
+    long n;
+    const void* g;
+    void* p;
+    void* state1; // uint8 [n] or float [n]
+    void* state2; // two-state optimizers (adam), else unused
+    const float* qmap1;
+    const float* qmap2; // 8-bit only: the 256-entry codes
+    float* absmax1;
+    float* absmax2; // 8-bit only: [ceil(n / 256)]
+    OptimScalars k;
+};
+int optimizer_update(int state_bits, const OptimUpdateCall& call, hipStream_t stream);
+long optimizer_update_grid(long n); // workgroups of that launch (host logic and the CU count or its override)
+
 // c_api.hip (g_last_gemm_kernel, defined there as well, is declared in bnb_common.h)
 #ifdef BNB_PROFILING
 extern unsigned long long* g_dbg_buf; // profiling builds only: device buffer for the kernels' s_memtime stamps

@@ -363,6 +363,32 @@ int bnb_mi355x_int8_mm_dequant(const bnb_mi355x_int8_mm_dequant_args* args) {
     return rc;
 }
 
+// ------------------------------------------------------------------ optimizer updates (optim8.hip)
+static int optimizer_update_entry(const char* entry, int state_bits, const bnb_mi355x_optimizer_update_args* args) {
+    if (args == nullptr || args->struct_bytes != sizeof(bnb_mi355x_optimizer_update_args)) {
+        fprintf(stderr, "bitsandbytes_amd: %s: struct_bytes is %zu, this library's bnb_mi355x_optimizer_update_args has %zu\n", entry,
+                args == nullptr ? static_cast<size_t>(0) : args->struct_bytes, sizeof(bnb_mi355x_optimizer_update_args));
+        return kOptimMalformed;
+    }
+    const OptimUpdateCall call{args->optimizer, args->dtype, args->n, args->g, args->p, args->state1, args->state2, args->qmap1, args->qmap2,
+                               args->absmax1, args->absmax2,
+                               OptimScalars{args->gnorm_scale, args->beta1, args->one_minus_beta1, args->beta2, args->one_minus_beta2,
+                                            args->sqrt_correction2, args->eps, args->weight_decay, args->decay, args->step_scale, args->neg_lr,
+                                            args->step}};
+    const int rc = optimizer_update(state_bits, call, S(args->stream));
+    if (rc != kOptimOk)
+        fprintf(stderr, "bitsandbytes_amd: %s: refused optimizer %d, dtype %d, n=%ld (optimizer 0 ... 4; dtype 0 / 1 / 2; n >= 0; g, p, state1 and, for adam, state2 not NULL; 8-bit: the qmap and absmax of every state not NULL)\n",
+                entry, args->optimizer, args->dtype, args->n);
+    return rc;
+}
+int bnb_mi355x_optimizer_update_8bit_blockwise(const bnb_mi355x_optimizer_update_args* args) {
+    return optimizer_update_entry("optimizer_update_8bit_blockwise", 8, args);
+}
+int bnb_mi355x_optimizer_update_32bit(const bnb_mi355x_optimizer_update_args* args) {
+    return optimizer_update_entry("optimizer_update_32bit", 32, args);
+}
+int bnb_mi355x_optimizer_update_grid(long n) { return static_cast<int>(optimizer_update_grid(n < 0 ? 0 : n)); }
+
 // ------------------------------------------------------------------ gated gemm_4bit (dense FFN: silu(gate) * up as the epilogue)
 void bnb_mi355x_gemm_4bit_gated(int dtype, const void* A, const uint8_t* B, const float* absmax, void* out, const void* bias, int M, int N,
                                 int K, int blocksize, int quant_type, bnb_stream_t s) {

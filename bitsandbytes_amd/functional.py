@@ -639,6 +639,27 @@ def int8_vectorwise_dequant(A: Tensor, stats: Tensor) -> Tensor:
     return torch.ops.bitsandbytes.int8_vectorwise_dequant.default(A, stats)
 
 
+# ---------------------------------------------------------------------------------------------- optimizer updates
+def optimizer_update_32bit(optimizer_name: str, g: Tensor, p: Tensor, state1: Tensor, beta1: float, eps: float, step: int, lr: float,
+                           state2: Optional[Tensor] = None, beta2: float = 0.0, beta3: float = 0.0, alpha: float = 0.0,
+                           weight_decay: float = 0.0, gnorm_scale: float = 1.0, unorm_vec: Optional[Tensor] = None, max_unorm: float = 0.0,
+                           skip_zeros=False) -> None:
+    """In-place update of ``p`` and its fp32 state(s) in one launch (reference functional.py:1080-1166). ``max_unorm > 0`` raises
+    NotImplementedError: update-norm clipping is not served."""
+    torch.ops.bitsandbytes.optimizer_update_32bit(optimizer_name, g, p, state1, state2, unorm_vec, max_unorm, 0.0, beta1, beta2, beta3, alpha,
+                                                  eps, weight_decay, step, lr, gnorm_scale, skip_zeros)
+
+
+def optimizer_update_8bit_blockwise(optimizer_name: str, g: Tensor, p: Tensor, state1: Tensor, state2: Optional[Tensor], beta1: float,
+                                    beta2: float, beta3: float, alpha: float, eps: float, step: int, lr: float, qmap1: Tensor,
+                                    qmap2: Optional[Tensor], absmax1: Tensor, absmax2: Optional[Tensor], weight_decay: float = 0.0,
+                                    gnorm_scale: float = 1.0, skip_zeros=False) -> None:
+    """In-place update of ``p`` and its 8-bit blockwise state(s) - uint8 codes of ``qmap``, one fp32 ``absmax`` per 256 elements - in
+    one launch (reference functional.py:1169-1212). The stored states equal ``quantize_blockwise(new fp32 state, qmap, 256)``."""
+    torch.ops.bitsandbytes.optimizer_update_8bit_blockwise(optimizer_name, g, p, state1, state2, beta1, beta2, beta3, alpha, eps, step, lr,
+                                                           qmap1, qmap2, absmax1, absmax2, weight_decay, gnorm_scale, skip_zeros)
+
+
 def has_avx512bf16() -> bool:
     """Reference ``functional.has_avx512bf16`` asks its CPU library whether the AVX512-BF16 gemv path exists
     (functional.py:1670-1674). This package ships no CPU kernels, so the answer is always False."""

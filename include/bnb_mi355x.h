@@ -360,6 +360,59 @@ typedef struct bnb_mi355x_int8_mm_dequant_args {
     bnb_stream_t stream;
 } bnb_mi355x_int8_mm_dequant_args;
 int bnb_mi355x_int8_mm_dequant(const bnb_mi355x_int8_mm_dequant_args* args);
+/* ------------------------------------------------------------------------------------------------
+ * Optimizer updates (csrc/optim8.hip): ONE launch updates one parameter tensor in place. Both calls take one argument block
+ * (struct_bytes = sizeof of the block), only enqueue work on `stream`, use no workspace, and return 0 after the launch (n == 0: 0,
+ * nothing launched) or a non-zero code with NOTHING launched; they never end the process.
+ *   bnb_mi355x_optimizer_update_8bit_blockwise: state1 / state2 are uint8 codes [n] of qmap1 / qmap2 (256 floats each) with one fp32
+ *     absmax per 256 elements ([ceil(n / 256)]); the new fp32 states are re-encoded in the launch with quantize_blockwise's function,
+ *     so the stored codes and absmax equal quantize_blockwise(new state, blocksize 256) bit for bit.
+ *   bnb_mi355x_optimizer_update_32bit: state1 / state2 are fp32 [n]; qmap and absmax are ignored. No update-norm clipping (max_unorm).
+ * The arithmetic is fp32 with every operation rounded on its own, in the order of the reference CPU backend
+ * (bitsandbytes/backends/cpu/ops.py _optimizer_update_8bit_blockwise_cpu); the ledger of every optimizer is DESIGN.md 3.19. The
+ * caller computes the scalars in double and rounds each to fp32 once. state2 / qmap2 / absmax2: Adam only.
+ * ---------------------------------------------------------------------------------------------- */
+#define BNB_MI355X_OPTIM_OK 0
+#define BNB_MI355X_OPTIM_MALFORMED 1         /* struct_bytes, n < 0 or a NULL pointer the optimizer needs: one line on stderr */
+#define BNB_MI355X_OPTIM_REFUSED_OPTIMIZER 2 /* not one of BNB_MI355X_OPT_* */
+#define BNB_MI355X_OPTIM_REFUSED_DTYPE 3     /* not 0 fp32, 1 fp16, 2 bf16 */
+#define BNB_MI355X_OPT_ADAM 0
+#define BNB_MI355X_OPT_MOMENTUM 1
+#define BNB_MI355X_OPT_RMSPROP 2
+#define BNB_MI355X_OPT_ADAGRAD 3
+#define BNB_MI355X_OPT_LION 4
+typedef struct bnb_mi355x_optimizer_update_args {
+    size_t struct_bytes;    /* sizeof of this struct as the caller was compiled */
+    int optimizer;          /* BNB_MI355X_OPT_* */
+    int dtype;              /* of g and p */
+    long n;
+    const void* g;
+    void* p;
+    void* state1;
+    void* state2;
+    const float* qmap1;
+    const float* qmap2;
+    float* absmax1;
+    float* absmax2;
+    int step;               /* 1-based */
+    float gnorm_scale;
+    float beta1;
+    float one_minus_beta1;  /* 1 - beta1 */
+    float beta2;
+    float one_minus_beta2;  /* 1 - beta2 */
+    float sqrt_correction2; /* sqrt(1 - beta2^step) */
+    float eps;
+    float weight_decay;
+    float decay;            /* 1 - lr * weight_decay */
+    float step_scale;       /* -lr / (1 - beta1^step) */
+    float neg_lr;           /* -lr */
+    bnb_stream_t stream;
+} bnb_mi355x_optimizer_update_args;
+int bnb_mi355x_optimizer_update_8bit_blockwise(const bnb_mi355x_optimizer_update_args* args);
+int bnb_mi355x_optimizer_update_32bit(const bnb_mi355x_optimizer_update_args* args);
+/* Debug / test query (host logic and the CU count of the current device or bnb_mi355x_set_cu_count's override): the number of
+ * 256-thread workgroups either call launches for n elements. A workgroup takes 1024 elements per pass over the persistent grid. */
+int bnb_mi355x_optimizer_update_grid(long n);
 /* Dense gated-SiLU FFN: the fused matmul over ONE interleaved matrix B [N = 2 F, K] - gate row i at row 2 i, up row i at row 2 i + 1;
  * bias, if given, [N] in the same layout - with silu(gate) * up as its epilogue. A is [M, K], out is [M, F]:
  *     g = T(acc_g + bias_g), u = T(acc_u + bias_u), out[m, i] = T(float(T(silu(g))) * float(u)),  silu(g) = g / (1 + expf(-g)) in fp32
