@@ -192,6 +192,7 @@ def _declare(dll: ct.CDLL) -> None:
     # LLM.int8(): one argument block each (ctypes.byref(Int8QuantArgs / GemmInt8Args / Int8MmDequantArgs)); non-zero: nothing launched
     # (bnb_mi355x_gemm_int8: INT8_REFUSED_K = take the fallback)
     sig(["bnb_mi355x_int8_vectorwise_quant", "bnb_mi355x_gemm_int8", "bnb_mi355x_int8_mm_dequant"], [_VOID_P], _I32)
+    sig(["bnb_mi355x_gemm_int8_route"], [ct.c_long] * 3, _I32)  # (M, N, K): 13 / 14, 0 for a refused K (host logic)
     # the fused optimizer updates: one argument block (ctypes.byref(OptimizerUpdateArgs)); non-zero: nothing launched
     sig(["bnb_mi355x_optimizer_update_8bit_blockwise", "bnb_mi355x_optimizer_update_32bit"], [_VOID_P], _I32)
     sig(["bnb_mi355x_optimizer_update_grid"], [ct.c_long], _I32)  # workgroups of that launch for n elements (host logic)
@@ -289,7 +290,7 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_gemm_4bit_experts_gate_up", "bnb_mi355x_gemm_4bit_experts_gate_up_supported",
        "bnb_mi355x_gemm_4bit_experts_gate_up_plan",
        "bnb_mi355x_gemm_4bit_experts_mfma", "bnb_mi355x_gemm_4bit_experts_mfma_supported",
-       "bnb_mi355x_int8_vectorwise_quant", "bnb_mi355x_gemm_int8", "bnb_mi355x_int8_mm_dequant",
+       "bnb_mi355x_int8_vectorwise_quant", "bnb_mi355x_gemm_int8", "bnb_mi355x_int8_mm_dequant", "bnb_mi355x_gemm_int8_route",
        "bnb_mi355x_optimizer_update_8bit_blockwise", "bnb_mi355x_optimizer_update_32bit", "bnb_mi355x_optimizer_update_grid",
        "bnb_mi355x_gemm_4bit_gated", "bnb_mi355x_gemm_4bit_gated_supported",
        "bnb_mi355x_gemm_4bit_lora", "bnb_mi355x_gemm_4bit_lora_supported",

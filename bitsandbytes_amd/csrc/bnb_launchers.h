@@ -215,6 +215,14 @@ int gemm_int8_tiles(int N);
 bool gemm_int8_k_supported(long K);
 int gemm_int8(int epilogue, int out_dtype, const int8_t* A, const int8_t* B, const float* row_stats, const float* col_stats, const void* bias,
               int bias_dtype, void* out, long M, long N, long K, hipStream_t stream);
+// Which kernel a gemm_int8 call of this shape launches under the calling thread's tuning and CU count: kKernelInt8, kKernelInt8Tall (then
+// *instance = 1: 128 x 128 tiles, 2: 64 x 128) or kKernelNone for a K that is refused. The launch and the query ask here.
+int gemm_int8_route(long M, long N, long K, int* instance);
+// gemm_int8_tall.hip (the LDS-tiled kernel for prefill-sized batches; launched by gemm_int8 only)
+int gemm_int8_tall_instance(long M, long N);
+bool gemm_int8_tall_serves(int instance, long M, long N);
+void gemm_int8_tall(int instance, int epilogue, int out_dtype, const int8_t* A, const int8_t* B, const float* row_stats, const float* col_stats,
+                    const void* bias, int bias_dtype, void* out, int M, int N, int K, hipStream_t stream);
 int int8_mm_dequant(int out_dtype, const int* C, const float* row_stats, const float* col_stats, const void* bias, int bias_dtype, void* out,
                     long M, long N, hipStream_t stream);
 

@@ -352,6 +352,10 @@ int bnb_mi355x_gemm_int8(const bnb_mi355x_gemm_int8_args* args) {
                 args->epilogue, args->out_dtype, args->bias_dtype, args->M, args->N, args->K);
     return rc;
 }
+int bnb_mi355x_gemm_int8_route(long M, long N, long K) {
+    int instance;
+    return (M < 0 || N < 0 || M >= (1L << 31) || N >= (1L << 31)) ? 0 : gemm_int8_route(M, N, K, &instance);
+}
 int bnb_mi355x_int8_mm_dequant(const bnb_mi355x_int8_mm_dequant_args* args) {
     const bool block_ok = args != nullptr && args->struct_bytes == sizeof(bnb_mi355x_int8_mm_dequant_args);
     const int rc = block_ok ? int8_mm_dequant(args->out_dtype, args->C, args->row_stats, args->col_stats, args->bias, args->bias_dtype, args->out, args->M,

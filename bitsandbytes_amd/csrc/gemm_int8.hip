@@ -173,6 +173,7 @@ template <int EPI, typename T> void launch(const Int8Args& a, int slot, hipStrea
     const size_t lds = static_cast<size_t>(kWaves) * a.TT * kPassTiles * 1024;
     ensure_dynamic_lds(g_lds[slot], reinterpret_cast<const void*>(&gemm_int8_kernel<EPI, T>), lds);
     const dim3 grid((a.N + 16 * a.TT - 1) / (16 * a.TT));
+    g_last_gemm_kernel = kKernelInt8;
     hipLaunchKernelGGL((gemm_int8_kernel<EPI, T>), grid, dim3(kThreads), lds, stream, a);
 }
 
@@ -191,6 +192,39 @@ int gemm_int8_tiles(int N) {
 
 bool gemm_int8_k_supported(long K) { return K > 0 && K % 16 == 0 && K <= kMaxK; }
 
+// THE answer to "which kernel does this gemm_int8 call launch": this file's (weight rows over workgroups, K over wavefronts, M in 64-row
+// passes: decode) or the LDS-tiled one of gemm_int8_tall.hip (prefill). Tuning knob1 = 100 * cfg: cfg 60 forces this file's kernel, 61 the
+// tall one with its built-in tile choice, 62 / 63 its 128 x 128 / 64 x 128 instance; anything else keeps the rule below.
+// The rule, measured on MI355X (profiles/int8_bench.txt, us per int8_scaled_mm call, tall vs this file's kernel, spreads <= 0.5 us):
+//   M = 64 (tall forced): 4096^2 31.2 vs 14.7, 11008 x 4096 32.9 vs 20.8, 4096 x 11008 80.5 vs 30.8 - behind everywhere;
+//   M = 128: 4096^2 31.1 vs 26.2, 4096 x 11008 80.7 vs 56.9 - behind (64 tiles of 64 x 128 on 256 CUs) - but 11008 x 4096 32.8 vs 37.3
+//     (172 tiles) ahead;
+//   M = 256: 31.1 vs 48.9, 57.5 vs 70.7, 80.7 vs 108.3; M = 512: 32.1 vs 94.4, 75.6 vs 137.3, 87.7 vs 211.6; M = 2048: 79 vs 365, 225 vs
+//     539, 191 vs 832 - ahead everywhere.
+// M_tall = kTallMinRows = 256 is the smallest benchmarked M at which the tall kernel wins on all three shapes; the one shape that wins at
+// 128 differs from the two that lose by its tile count, so 128 ... 255 rows go to the tall kernel where its 64 x 128 tiles give at least
+// half of the CUs a workgroup (between 64 and 172 tiles on 256 CUs nothing was measured: the line is drawn at 128).
+constexpr long kTallMinRows = 256, kTallMinRowsFilled = 128;
+static bool tall_selected(long M, long N) {
+    if (M >= kTallMinRows)
+        return true;
+    return M >= kTallMinRowsFilled && 2 * ((M + 63) / 64) * ((N + 127) / 128) >= device_cu_count_or_default();
+}
+int gemm_int8_route(long M, long N, long K, int* instance) {
+    *instance = 0;
+    if (!gemm_int8_k_supported(K))
+        return kKernelNone;
+    const int cfg = g_mfma_knob1.load(std::memory_order_relaxed) / 100;
+    const bool forced_tall = cfg >= 61 && cfg <= 63;
+    if (cfg == 60 || (!forced_tall && !tall_selected(M, N)))
+        return kKernelInt8;
+    const int inst = cfg == 62 ? 1 : cfg == 63 ? 2 : gemm_int8_tall_instance(M, N);
+    if (!gemm_int8_tall_serves(inst, M, N)) // (an empty problem, or more tiles than one grid axis carries)
+        return kKernelInt8;
+    *instance = inst;
+    return kKernelInt8Tall;
+}
+
 // epilogue 0: out int32 [M, N]; 1: out of out_dtype (0 fp32, 1 fp16, 2 bf16) = dequant(C, row_stats [M], col_stats [N], bias [N] of
 // bias_dtype or nullptr). Returns kInt8Ok after the launch (M == 0 or N == 0: nothing to launch), kInt8RefusedK for a K this kernel
 // does not serve, kInt8Malformed for anything else outside the preconditions; nothing is launched when it refuses.
@@ -207,6 +241,12 @@ int gemm_int8(int epilogue, int out_dtype, const int8_t* A, const int8_t* B, con
     if (epilogue == kEpiDequant && (row_stats == nullptr || col_stats == nullptr || out_dtype < 0 || out_dtype > 2 ||
                                     (bias != nullptr && (bias_dtype < 0 || bias_dtype > 2))))
         return kInt8Malformed;
+    int instance = 0;
+    if (gemm_int8_route(M, N, K, &instance) == kKernelInt8Tall) {
+        gemm_int8_tall(instance, epilogue, out_dtype, A, B, row_stats, col_stats, bias, bias_dtype, out, static_cast<int>(M), static_cast<int>(N),
+                       static_cast<int>(K), stream);
+        return hipPeekAtLastError() == hipSuccess ? kInt8Ok : kInt8Malformed;
+    }
     Int8Args a{};
     a.A = A;
     a.B = B;

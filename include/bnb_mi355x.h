@@ -157,7 +157,8 @@ int bnb_mi355x_gemm_4bit_fused_max_m(int dtype, int N, int K, int blocksize, int
  * 7 streaming MFMA kernel (gemm4_mfma_sm_kernel: 2 ... 16 rows, one persistent workgroup per CU), 9 expert-indexed kernel
  * (gemm4_experts_kernel: bnb_mi355x_gemm_4bit_experts), 10 token-major expert kernel (bnb_mi355x_gemm_4bit_experts_combine),
  * 11 token-major gate / up kernel (bnb_mi355x_gemm_4bit_experts_gate_up), 12 expert-indexed MFMA kernel
- * (bnb_mi355x_gemm_4bit_experts_mfma). Debug / test query:
+ * (bnb_mi355x_gemm_4bit_experts_mfma), 13 int8 kernel (gemm_int8_kernel: bnb_mi355x_gemm_int8), 14 LDS-tiled int8 kernel
+ * (gemm_int8_tall_kernel: bnb_mi355x_gemm_int8 on prefill-sized batches). Debug / test query:
  * a test that forces a kernel with bnb_mi355x_set_tuning asserts here that it ran (a geometry the forced kernel does not
  * serve falls back to another family by design). */
 int bnb_mi355x_last_gemm_kernel(void);
@@ -331,7 +332,13 @@ int bnb_mi355x_int8_vectorwise_quant(const bnb_mi355x_int8_vectorwise_quant_args
  * BNB_MI355X_INT8_REFUSED_K. epilogue 0: out is int32 [M, N]. epilogue 1: out is [M, N] of out_dtype,
  *     T(((float(C) * (row_stats[m] * col_stats[n])) * 6.200124e-05f) + float(bias[n]))
  * - four fp32 operations rounded one by one, the add only with a bias (of bias_dtype, any of the three), one conversion to T. The
- * result is a function of the operands alone: not of the tile height or the CU count. No workspace, no atomics, no memset. */
+ * result is a function of the operands alone: not of the kernel, the tile or the CU count. No workspace, no atomics, no memset.
+ * Two kernels stand behind the one entry: gemm_int8_kernel (family 13: weight rows over workgroups, K over wavefronts, every operand a
+ * global load of its lane, M in 64-row passes - decode-sized batches) and gemm_int8_tall_kernel (family 14, csrc/gemm_int8_tall.hip: a
+ * 128 x 128 or 64 x 128 output tile per workgroup, both operands through LDS by LDS-DMA - prefill-sized batches, M >= 128).
+ * bnb_mi355x_set_tuning knob1 = 100 * cfg forces one FOR THIS ENTRY: cfg 60 family 13, 61 family 14 with its built-in tile choice,
+ * 62 / 63 its 128 x 128 / 64 x 128 instance (bnb_mi355x_gemm_4bit reads cfg 60 as its own tall-tile kernel and knows no 61-63).
+ * bnb_mi355x_last_gemm_kernel reports 13 or 14 after the call. */
 typedef struct bnb_mi355x_gemm_int8_args {
     size_t struct_bytes;       /* sizeof of this struct as the caller was compiled */
     int epilogue;              /* 0 int32, 1 dequant */
@@ -346,6 +353,9 @@ typedef struct bnb_mi355x_gemm_int8_args {
     bnb_stream_t stream;
 } bnb_mi355x_gemm_int8_args;
 int bnb_mi355x_gemm_int8(const bnb_mi355x_gemm_int8_args* args);
+/* Which of the two kernels bnb_mi355x_gemm_int8 launches for this shape under the calling thread's tuning and CU count: 13 or 14 (the
+ * families of bnb_mi355x_last_gemm_kernel), 0 for a K that is refused (or M, N outside [0, 2^31)). Host logic only: nothing is launched. */
+int bnb_mi355x_gemm_int8_route(long M, long N, long K);
 /* The second step of the two-step API: C int32 [M, N] -> out [M, N] of out_dtype, the arithmetic of epilogue 1 above (the same
  * device function: the same bits). */
 typedef struct bnb_mi355x_int8_mm_dequant_args {
@@ -645,7 +655,9 @@ void bnb_mi355x_peer_chain_read(void* const* bufs, void* epoch_word, int world, 
  * workspace-size query follows it). MFMA kernels: knob0 bit 0 = round 2's form of the register-transposed kernel (measurement build only; ignored by the product library),
  * knob0 bit 1 = the built-in route without the streaming MFMA kernel (round 5's routing: A/B runs), bit 2 = its weights-first experiment,
  * knob1 = 100 * cfg + K-slice count (cfg 11-14 producer/consumer geometries, 20/21/22
- * register-transposed kernel with built-in / 8 / 16 wavefronts, 40 K-quarter kernel, 50 streaming MFMA kernel). Every setting
+ * register-transposed kernel with built-in / 8 / 16 wavefronts, 40 K-quarter kernel, 50 streaming MFMA kernel, 60 tall-tile kernel; bnb_mi355x_gemm_int8 reads its own values: 60 gemm_int8_kernel, 61 / 62 /
+ * 63 gemm_int8_tall_kernel with its built-in / 128 x 128 / 64 x 128 tile; it keeps its route under every other value, and a 4-bit call under a cfg
+ * it does not know forces none of its kernels). Every setting
  * computes correct results - the knobs only choose a launch geometry. THREAD-LOCAL: a setting applies to the calls the
  * SAME host thread makes afterwards and to nothing else in the process. */
 void bnb_mi355x_set_tuning(int reserved0, int reserved1, int mfma_knob0, int mfma_knob1);

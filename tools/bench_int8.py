@@ -5,14 +5,19 @@ Method (tools/bench_moe_ffn.py): every leg is a hipGraph of >= 64 calls that rot
 rotation exceeds the 256 MiB Infinity Cache; HIP events around `reps` replays (regions >= 10 ms); the legs alternate inside one process,
 order reversed every round; median and min ... max of the rounds - read the spread first. Legs, x bf16 [M, K]:
   quant      int8_vectorwise_quant(x)                                                         1 launch
-  scaled_mm  int8_scaled_mm(q, CB, stats, SCB, dtype=bf16): the matmul with the dequant epilogue 1 launch
+  scaled_mm  int8_scaled_mm(q, CB, stats, SCB, dtype=bf16): the matmul with the dequant epilogue 1 launch, by the route as shipped
+  mm 6000    the same call under bnb_mi355x_set_tuning(0, 0, 0, 6000): gemm_int8_kernel forced (the parent's only kernel)
+  mm 6100    the same call under 6100: gemm_int8_tall_kernel forced, its built-in tile choice
   layer      Linear8bitLt(x), threshold 0                                                     2 launches
   bf16       F.linear(x, W) on the dequantized weight (hipBLASLt)
   4bit       this package's Linear4bit (NF4, bf16) at the same shape
   _int_mm    torch._int_mm(q, CB.t()) and the torch dequantization expression, where this torch build runs it ('raises' otherwise)
 For M <= 16 the scaled_mm column also gives the achieved bytes/s over bench.HBM_PEAK_GBS; the bound there is the N * K weight bytes.
+For M >= 128 the 'mm 6100' column also gives 2 M N K operations / time over the int8 MFMA peak at the clock the device reports: CUs x 4 SIMDs x
+1024 operations a cycle (v_mfma_i32_16x16x64_i8: 32768 operations in 8 passes of 4 cycles) x torch's clock_rate.
     python tools/bench_int8.py [--rounds 5] [--quick] [--out profiles/int8_bench.txt]"""
 import argparse
+import ctypes as ct
 import math
 import os
 import statistics
@@ -28,7 +33,7 @@ from bench import HBM_PEAK_GBS  # noqa: E402
 from tools.bench_experts import CACHE_BYTES, capture, timed  # noqa: E402
 
 SHAPES = [(4096, 4096), (11008, 4096), (4096, 11008)]  # (N, K)
-MS = (1, 4, 16, 64, 512, 2048)
+MS = (1, 4, 16, 64, 128, 256, 512, 2048)
 OPS = torch.ops.bitsandbytes
 
 
@@ -46,8 +51,15 @@ def main():
 
     say(f"# {torch.cuda.get_device_name(0)}, {bnb.lib.bnb_mi355x_version().decode()}, torch {torch.__version__}")
     say(f"# us per call: median (min ... max) of {args.rounds} rounds; x bf16; %HBM = N * K bytes / time / {HBM_PEAK_GBS:.0f} GB/s (M <= 16)")
-    names = ["quant", "scaled_mm", "layer", "bf16 F.linear", "Linear4bit", "_int_mm+dequant"]
-    say(f"{'N x K':>13s} {'M':>5s} " + " ".join(f"{n:>26s}" for n in names) + f" {'%HBM':>6s} {'bf16/layer':>10s} {'4bit/layer':>10s} {'_int_mm/scaled_mm':>17s}")
+    props = torch.cuda.get_device_properties(0)
+    khz = ct.c_int(0)  # hipDeviceAttributeClockRate (5): the peak engine clock the runtime reports, kHz
+    if ct.CDLL("libamdhip64.so").hipDeviceGetAttribute(ct.byref(khz), 5, torch.cuda.current_device()) != 0:
+        raise RuntimeError("hipDeviceGetAttribute(hipDeviceAttributeClockRate) failed")
+    khz = khz.value
+    peak_ops = props.multi_processor_count * 4 * 1024 * khz * 1e3  # int8 operations / s
+    say(f"# %MFMA = 2 M N K / time of 'mm 6100' / ({props.multi_processor_count} CUs x 4 SIMDs x 1024 ops/cycle x {khz / 1e3:.0f} MHz reported = {peak_ops / 1e15:.3f} Pop/s)")
+    names = ["quant", "scaled_mm", "mm 6000", "mm 6100", "layer", "bf16 F.linear", "Linear4bit", "_int_mm+dequant"]
+    say(f"{'N x K':>13s} {'M':>5s} " + " ".join(f"{n:>26s}" for n in names) + f" {'%HBM':>6s} {'%MFMA':>6s} {'kernel':>6s} {'bf16/layer':>10s} {'4bit/layer':>10s} {'_int_mm/scaled_mm':>17s}")
     gen = torch.Generator(device="cuda").manual_seed(0)
     for N, K in SHAPES:
         L = max(2, math.ceil(1.25 * CACHE_BYTES / (N * K)))
@@ -70,10 +82,20 @@ def main():
                 for c in range(calls):
                     OPS.int8_vectorwise_quant.default(x, 0.0)
 
-            def scaled_mm():
-                for c in range(calls):
-                    w = layers[c % L].weight
-                    OPS.int8_scaled_mm.default(q, w.CB, stats, w.SCB, None, torch.bfloat16)
+            def scaled_mm(value=0):
+                bnb.lib.bnb_mi355x_set_tuning(0, 0, 0, value)  # (the route is host logic: what is captured is what it chose)
+                try:
+                    for c in range(calls):
+                        w = layers[c % L].weight
+                        OPS.int8_scaled_mm.default(q, w.CB, stats, w.SCB, None, torch.bfloat16)
+                finally:
+                    bnb.lib.bnb_mi355x_set_tuning(0, 0, 0, 0)
+
+            def mm_6000():
+                scaled_mm(6000)
+
+            def mm_6100():
+                scaled_mm(6100)
 
             def layer():
                 for c in range(calls):
@@ -92,7 +114,7 @@ def main():
                     w = layers[c % L].weight
                     (torch._int_mm(q, w.CB.t()) * (stats[:, None] * w.SCB[None, :]) * 6.200124e-05).bfloat16()
 
-            legs = [quant, scaled_mm, layer, bf16, fourbit, int_mm]
+            legs = [quant, scaled_mm, mm_6000, mm_6100, layer, bf16, fourbit, int_mm]
             graphs = []
             for fn in legs:
                 try:
@@ -110,8 +132,10 @@ def main():
             med = {i: statistics.median(s) for i, s in samples.items()}
             cols = [f"{med[i]:9.2f} ({min(samples[i]):.2f}...{max(samples[i]):.2f})" if i in med else "raises" for i in range(len(legs))]
             hbm = f"{100.0 * N * K / med[1] / 1e3 / HBM_PEAK_GBS:5.1f}%" if M <= 16 else ""
-            vs = f"{med[5] / med[1]:16.2f}x" if 5 in med else f"{'n/a':>17s}"
-            say(f"{f'{N} x {K}':>13s} {M:>5d} " + " ".join(f"{c:>26s}" for c in cols) + f" {hbm:>6s} {med[3] / med[2]:9.2f}x {med[4] / med[2]:9.2f}x {vs}")
+            mfma = f"{100.0 * 2.0 * M * N * K / (med[3] * 1e-6) / peak_ops:5.1f}%" if M >= 128 and peak_ops > 0 else ""
+            vs = f"{med[7] / med[1]:16.2f}x" if 7 in med else f"{'n/a':>17s}"
+            say(f"{f'{N} x {K}':>13s} {M:>5d} " + " ".join(f"{c:>26s}" for c in cols) + f" {hbm:>6s} {mfma:>6s} {bnb.lib.bnb_mi355x_gemm_int8_route(M, N, K):>6d} "
+                f"{med[5] / med[4]:9.2f}x {med[6] / med[4]:9.2f}x {vs}")
             del graphs
         del layers, dense, four
         torch.cuda.empty_cache()
