@@ -341,6 +341,60 @@ if _define("bitsandbytes::int8_vectorwise_dequant", "(Tensor A, Tensor stats) ->
         return torch.empty_like(A, dtype=torch.float32)
 
 
+# Not reference ops: the mixed decomposition without a host synchronisation. bitsandbytes::int8_vectorwise_quant returns the outlier
+# columns as a tensor whose SIZE depends on the data; these two keep the set on the device as a bitmask of fixed size instead:
+#   int8_vectorwise_quant_mask(A [*, K], threshold > 0) -> (q int8 like A, row_stats fp32 [rows], mask int32 [ceil(K / 32)])
+#     bit c % 32 of word c / 32 is set iff some row has |A[r, c]| >= threshold (fp32 compare); the other bits are 0. row_stats leaves
+#     out the outlier elements of its own row; q is 0 in every flagged column of every row - the values of the reference op.
+#   int8_outlier_addmm_(out [*, N], A [*, K] fp16 / bf16, CB int8 [N, K], SCB fp32 [N], mask): in place,
+#     out = T(float(out) + sum over flagged c of A[:, c] * T((float(CB[:, c]) * SCB) * (1 / 127))), fp32 accumulation, one rounding.
+# A fixed number of launches each, nothing read on the host: both can be captured in a graph. "cuda" kernels only.
+INT8_MAX_K = 131056  # csrc/gemm_int8.hip, csrc/int8_outlier.hip
+
+
+def int8_k_served(K: int) -> bool:
+    """Whether the int8 matmul kernels and the outlier kernel serve rows of K elements."""
+    return 0 < K <= INT8_MAX_K and K % 16 == 0
+
+
+torch.library.define("bitsandbytes_amd::int8_vectorwise_quant_mask", "(Tensor A, float threshold) -> (Tensor, Tensor, Tensor)")
+torch.library.define("bitsandbytes_amd::int8_outlier_addmm_", "(Tensor(a!) out, Tensor A, Tensor CB, Tensor SCB, Tensor mask) -> ()")
+
+
+def _check_int8_quant_mask(A, threshold):
+    torch._check(A.dtype in _FLOAT_DTYPES, lambda: f"A must be float16, bfloat16 or float32, got {A.dtype}")
+    torch._check(A.dim() >= 1 and A.shape[-1] >= 1, lambda: f"A must be [*, cols] with cols >= 1, got {tuple(A.shape)}")
+    torch._check(threshold > 0.0, lambda: f"threshold must be positive (bitsandbytes::int8_vectorwise_quant serves threshold 0), got {threshold}")
+
+
+@register_fake("bitsandbytes_amd::int8_vectorwise_quant_mask")
+def _(A: torch.Tensor, threshold: float):
+    _check_int8_quant_mask(A, threshold)
+    cols = A.shape[-1]
+    return (torch.empty(A.shape, device=A.device, dtype=torch.int8), torch.empty(A.numel() // cols, device=A.device, dtype=torch.float32),
+            torch.empty(-(cols // -32), device=A.device, dtype=torch.int32))
+
+
+def _check_int8_outlier_addmm(out, A, CB, SCB, mask):
+    torch._check(A.dtype in (torch.float16, torch.bfloat16) and out.dtype == A.dtype,
+                 lambda: f"A and out must share float16 or bfloat16, got {A.dtype} and {out.dtype}")
+    torch._check(CB.dtype == torch.int8 and CB.dim() == 2 and A.dim() >= 1 and A.shape[-1] == CB.shape[1],
+                 lambda: f"A [*, K] and CB int8 [N, K] must share K, got {tuple(A.shape)} and {CB.dtype} {tuple(CB.shape)}")
+    N, K = CB.shape
+    torch._check(int8_k_served(K), lambda: f"K must be a multiple of 16 in [16, {INT8_MAX_K}], got {K}")
+    torch._check(tuple(out.shape) == (*A.shape[:-1], N), lambda: f"out must be {(*A.shape[:-1], N)}, got {tuple(out.shape)}")
+    torch._check(SCB.dtype == torch.float32 and SCB.numel() == N, lambda: f"SCB must hold N = {N} float32 values, got {SCB.dtype} {tuple(SCB.shape)}")
+    torch._check(mask.dtype == torch.int32 and mask.numel() == -(K // -32),
+                 lambda: f"mask must hold ceil(K / 32) = {-(K // -32)} int32 words, got {mask.dtype} {tuple(mask.shape)}")
+    torch._check(all(t.device == A.device for t in (out, CB, SCB, mask)), lambda: "out, A, CB, SCB and mask must be on one device")
+    torch._check(all(t.is_contiguous() for t in (out, A, CB, SCB, mask)), lambda: "out, A, CB, SCB and mask must be contiguous")
+
+
+@register_fake("bitsandbytes_amd::int8_outlier_addmm_")
+def _(out, A, CB, SCB, mask) -> None:
+    _check_int8_outlier_addmm(out, A, CB, SCB, mask)
+
+
 # ---------------------------------------------------------------------------------------------- optimizer updates
 # The reference's schemas (bitsandbytes/_ops.py:409-455), string for string, and its fake kernels: every tensor is updated in place.
 def _check_optimizer_g_p(g, p):

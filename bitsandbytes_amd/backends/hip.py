@@ -23,6 +23,7 @@ import torch
 
 from .._ops import (GATED_CODES, MOE_GROUP_SCORE_CODES, MOE_SCORING_CODES, _check_moe_topk_grouped, _check_gemm_4bit_experts, _check_gemm_4bit_experts_combine, _check_gemm_4bit_experts_gate_up, _check_gemm_4bit_experts_ffn, _check_gemm_4bit_gated,
                      _check_gemm_4bit_lora, _check_gemm_4bit_lora_ids,
+                     _check_int8_outlier_addmm, _check_int8_quant_mask,
                      _check_lora_shrink, _check_lora_shrink_ids, _check_moe_topk, register_kernel)
 from ..cextension import lib
 
@@ -941,7 +942,9 @@ def _aligned16(t: torch.Tensor) -> torch.Tensor:
 @register_kernel("bitsandbytes::int8_vectorwise_quant", "cuda")
 def _(A: torch.Tensor, threshold=0.0):
     """One launch (one workgroup per row). threshold > 0 also returns the sorted outlier columns, found with torch as the reference does:
-    their number sizes a tensor, which SYNCHRONISES the host with the device - the threshold path cannot be captured in a graph."""
+    their number sizes a tensor, which SYNCHRONISES the host with the device - THIS op's threshold path cannot be captured in a graph.
+    bitsandbytes_amd::int8_vectorwise_quant_mask (below) returns the same q and row_stats with the columns as a device bitmask instead,
+    without the synchronisation; Linear8bitLt uses that one."""
     if A.dtype not in _DT_CODE:
         raise ValueError(f"int8_vectorwise_quant: A must be float16, bfloat16 or float32, got {A.dtype}")
     if A.dim() < 1 or A.shape[-1] == 0:
@@ -1077,6 +1080,41 @@ def _(A: torch.Tensor, CA: torch.Tensor, CB: torch.Tensor, SCA: torch.Tensor, SC
     sub_a = A.reshape(-1, A.shape[-1])[:, outlier_cols].contiguous()
     sub_b = torch.ops.bitsandbytes.int8_vectorwise_dequant.default(CB[:, outlier_cols].contiguous(), SCB).to(A.dtype).t()
     return out.view(-1, out.shape[-1]).addmm(sub_a, sub_b).view(out.shape), sub_a
+
+
+@register_kernel("bitsandbytes_amd::int8_vectorwise_quant_mask", "cuda")
+def _(A: torch.Tensor, threshold: float):
+    """csrc/int8_quant.hip: clear the mask, quantize (its row's outlier bits ORed into the mask), zero the flagged columns of q - three
+    launches, two with one row; nothing is read on the host."""
+    from ..cextension import Int8QuantMaskArgs
+
+    _check_int8_quant_mask(A, threshold)
+    A = A.contiguous()
+    cols = A.shape[-1]
+    rows = A.numel() // cols
+    q = torch.empty(A.shape, device=A.device, dtype=torch.int8)
+    stats = torch.empty(rows, device=A.device, dtype=torch.float32)
+    mask = torch.empty(-(cols // -32), device=A.device, dtype=torch.int32)
+    with _device_of(A):
+        args = Int8QuantMaskArgs(ct.sizeof(Int8QuantMaskArgs), _DT_CODE[A.dtype], float(threshold), rows, cols, A.data_ptr(), q.data_ptr(),
+                                 stats.data_ptr(), mask.data_ptr(), _stream(A))
+        if lib.bnb_mi355x_int8_vectorwise_quant_mask(ct.byref(args)) != 0:
+            raise ValueError("int8_vectorwise_quant_mask: the library refused the call (its message is on stderr)")
+    return q, stats, mask
+
+
+@register_kernel("bitsandbytes_amd::int8_outlier_addmm_", "cuda")
+def _(out: torch.Tensor, A: torch.Tensor, CB: torch.Tensor, SCB: torch.Tensor, mask: torch.Tensor) -> None:
+    """One launch of csrc/int8_outlier.hip, in place on `out`; nothing is read on the host."""
+    from ..cextension import Int8OutlierAddmmArgs
+
+    _check_int8_outlier_addmm(out, A, CB, SCB, mask)
+    N, K = CB.shape
+    with _device_of(A):
+        args = Int8OutlierAddmmArgs(ct.sizeof(Int8OutlierAddmmArgs), _DT_CODE[A.dtype], A.numel() // K, N, K, A.data_ptr(), CB.data_ptr(),
+                                    SCB.data_ptr(), mask.data_ptr(), out.data_ptr(), _stream(A))
+        if lib.bnb_mi355x_int8_outlier_addmm(ct.byref(args)) != 0:
+            raise ValueError("int8_outlier_addmm_: the library refused the call (its message is on stderr)")
 
 
 # ------------------------------------------------------------------------------------------ optimizer updates

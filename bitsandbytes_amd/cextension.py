@@ -110,6 +110,20 @@ class Int8QuantArgs(ct.Structure):
                 ("A", ct.c_void_p), ("q", ct.c_void_p), ("row_stats", ct.c_void_p), ("stream", ct.c_void_p)]
 
 
+class Int8QuantMaskArgs(ct.Structure):
+    """``bnb_mi355x_int8_vectorwise_quant_mask_args`` of include/bnb_mi355x.h."""
+
+    _fields_ = [("struct_bytes", ct.c_size_t), ("dtype", ct.c_int), ("threshold", ct.c_float), ("rows", ct.c_long), ("cols", ct.c_long),
+                ("A", ct.c_void_p), ("q", ct.c_void_p), ("row_stats", ct.c_void_p), ("mask", ct.c_void_p), ("stream", ct.c_void_p)]
+
+
+class Int8OutlierAddmmArgs(ct.Structure):
+    """``bnb_mi355x_int8_outlier_addmm_args`` of include/bnb_mi355x.h."""
+
+    _fields_ = [("struct_bytes", ct.c_size_t), ("dtype", ct.c_int), ("M", ct.c_long), ("N", ct.c_long), ("K", ct.c_long), ("A", ct.c_void_p),
+                ("CB", ct.c_void_p), ("SCB", ct.c_void_p), ("mask", ct.c_void_p), ("out", ct.c_void_p), ("stream", ct.c_void_p)]
+
+
 class Int8MmDequantArgs(ct.Structure):
     """``bnb_mi355x_int8_mm_dequant_args`` of include/bnb_mi355x.h."""
 
@@ -192,6 +206,8 @@ def _declare(dll: ct.CDLL) -> None:
     # LLM.int8(): one argument block each (ctypes.byref(Int8QuantArgs / GemmInt8Args / Int8MmDequantArgs)); non-zero: nothing launched
     # (bnb_mi355x_gemm_int8: INT8_REFUSED_K = take the fallback)
     sig(["bnb_mi355x_int8_vectorwise_quant", "bnb_mi355x_gemm_int8", "bnb_mi355x_int8_mm_dequant"], [_VOID_P], _I32)
+    # the sync-free mixed decomposition: Int8QuantMaskArgs / Int8OutlierAddmmArgs (the second answers INT8_REFUSED_K like the matmul)
+    sig(["bnb_mi355x_int8_vectorwise_quant_mask", "bnb_mi355x_int8_outlier_addmm"], [_VOID_P], _I32)
     sig(["bnb_mi355x_gemm_int8_route"], [ct.c_long] * 3, _I32)  # (M, N, K): 13 / 14, 0 for a refused K (host logic)
     # the fused optimizer updates: one argument block (ctypes.byref(OptimizerUpdateArgs)); non-zero: nothing launched
     sig(["bnb_mi355x_optimizer_update_8bit_blockwise", "bnb_mi355x_optimizer_update_32bit"], [_VOID_P], _I32)
@@ -291,6 +307,7 @@ EXPORTED_SYMBOLS = tuple(
        "bnb_mi355x_gemm_4bit_experts_gate_up_plan",
        "bnb_mi355x_gemm_4bit_experts_mfma", "bnb_mi355x_gemm_4bit_experts_mfma_supported",
        "bnb_mi355x_int8_vectorwise_quant", "bnb_mi355x_gemm_int8", "bnb_mi355x_int8_mm_dequant", "bnb_mi355x_gemm_int8_route",
+       "bnb_mi355x_int8_vectorwise_quant_mask", "bnb_mi355x_int8_outlier_addmm",
        "bnb_mi355x_optimizer_update_8bit_blockwise", "bnb_mi355x_optimizer_update_32bit", "bnb_mi355x_optimizer_update_grid",
        "bnb_mi355x_gemm_4bit_gated", "bnb_mi355x_gemm_4bit_gated_supported",
        "bnb_mi355x_gemm_4bit_lora", "bnb_mi355x_gemm_4bit_lora_supported",

@@ -211,6 +211,12 @@ bool moe_topk_grouped(const MoeTopkGroupedCall& call, hipStream_t stream);
 // standalone dequantization). Every launcher returns one of these; nothing is launched unless it returns kInt8Ok.
 enum Int8Status : int { kInt8Ok = 0, kInt8Malformed = 1, kInt8RefusedK = 2 };
 int int8_vectorwise_quant(int dtype, const void* A, int8_t* q, float* row_stats, long rows, long cols, float threshold, hipStream_t stream);
+// The sync-free mixed decomposition: the quantize with the outlier columns as a device bitmask (uint32 [ceil(cols / 32)]), and the
+// 16-bit outlier term added in place to the scaled matmul's result (int8_outlier.hip; kInt8RefusedK for a K outside the matmul's range).
+int int8_vectorwise_quant_mask(int dtype, const void* A, int8_t* q, float* row_stats, uint32_t* mask, long rows, long cols, float threshold,
+                               hipStream_t stream);
+int int8_outlier_addmm(int dtype, const void* A, const int8_t* CB, const float* SCB, const uint32_t* mask, void* out, long M, long N, long K,
+                       hipStream_t stream);
 int gemm_int8_tiles(int N);
 bool gemm_int8_k_supported(long K);
 int gemm_int8(int epilogue, int out_dtype, const int8_t* A, const int8_t* B, const float* row_stats, const float* col_stats, const void* bias,

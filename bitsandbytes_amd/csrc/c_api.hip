@@ -338,6 +338,27 @@ int bnb_mi355x_int8_vectorwise_quant(const bnb_mi355x_int8_vectorwise_quant_args
                 args == nullptr ? static_cast<size_t>(0) : args->struct_bytes, sizeof(bnb_mi355x_int8_vectorwise_quant_args));
     return rc;
 }
+int bnb_mi355x_int8_vectorwise_quant_mask(const bnb_mi355x_int8_vectorwise_quant_mask_args* args) {
+    const bool block_ok = args != nullptr && args->struct_bytes == sizeof(bnb_mi355x_int8_vectorwise_quant_mask_args);
+    const int rc = block_ok ? int8_vectorwise_quant_mask(args->dtype, args->A, args->q, args->row_stats, reinterpret_cast<uint32_t*>(args->mask),
+                                                         args->rows, args->cols, args->threshold, S(args->stream))
+                            : static_cast<int>(kInt8Malformed);
+    if (rc != kInt8Ok)
+        fprintf(stderr, "bitsandbytes_amd: int8_vectorwise_quant_mask: refused (struct_bytes %zu of %zu; dtype 0 / 1 / 2, rows and cols below 2^31, A, q, row_stats, mask not NULL, threshold > 0)\n",
+                args == nullptr ? static_cast<size_t>(0) : args->struct_bytes, sizeof(bnb_mi355x_int8_vectorwise_quant_mask_args));
+    return rc;
+}
+// (BNB_MI355X_INT8_REFUSED_K is an answer here as well: the caller keeps the composed path for such a K)
+int bnb_mi355x_int8_outlier_addmm(const bnb_mi355x_int8_outlier_addmm_args* args) {
+    const bool block_ok = args != nullptr && args->struct_bytes == sizeof(bnb_mi355x_int8_outlier_addmm_args);
+    const int rc = block_ok ? int8_outlier_addmm(args->dtype, args->A, args->CB, args->SCB, reinterpret_cast<const uint32_t*>(args->mask), args->out,
+                                                 args->M, args->N, args->K, S(args->stream))
+                            : static_cast<int>(kInt8Malformed);
+    if (rc == kInt8Malformed)
+        fprintf(stderr, "bitsandbytes_amd: int8_outlier_addmm: refused (struct_bytes %zu of %zu; dtype 1 / 2; M, N below 2^31; A, CB, SCB, mask, out not NULL)\n",
+                args == nullptr ? static_cast<size_t>(0) : args->struct_bytes, sizeof(bnb_mi355x_int8_outlier_addmm_args));
+    return rc;
+}
 // (one argument block; BNB_MI355X_INT8_REFUSED_K is an answer, not an error: it prints nothing)
 int bnb_mi355x_gemm_int8(const bnb_mi355x_gemm_int8_args* args) {
     if (args == nullptr || args->struct_bytes != sizeof(bnb_mi355x_gemm_int8_args)) {

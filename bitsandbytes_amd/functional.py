@@ -616,8 +616,23 @@ def gemv_4bit(A: Tensor, B: Tensor, out: Optional[Tensor] = None, transposed_A=F
 def int8_vectorwise_quant(A: Tensor, threshold=0.0):
     """Row-wise int8 quantization (reference functional.py:1655-1673): ``(q int8, row_stats fp32, outlier_cols or None)``. With
     ``threshold > 0`` the elements at or above it are left out and the sorted outlier columns come back - at the price of a host
-    synchronisation."""
+    synchronisation (:func:`int8_vectorwise_quant_mask` has none)."""
     return torch.ops.bitsandbytes.int8_vectorwise_quant.default(A, threshold)
+
+
+def int8_vectorwise_quant_mask(A: Tensor, threshold: float):
+    """:func:`int8_vectorwise_quant` with ``threshold > 0`` and the outlier columns as a device bitmask: ``(q int8, row_stats fp32,
+    mask int32 [ceil(cols / 32)])``, bit ``c % 32`` of word ``c // 32`` set iff column ``c`` holds a value at or above the threshold.
+    The same ``q`` and ``row_stats``; no host synchronisation, a fixed number of launches."""
+    return torch.ops.bitsandbytes_amd.int8_vectorwise_quant_mask.default(A, float(threshold))
+
+
+def int8_outlier_addmm_(out: Tensor, A: Tensor, CB: Tensor, SCB: Tensor, mask: Tensor) -> Tensor:
+    """Adds, in place, the 16-bit half of the LLM.int8() decomposition to ``out`` (the result of ``int8_scaled_mm`` on the masked
+    quantization of ``A``): ``A[:, c] @ dequantized CB[:, c].T`` over the columns ``c`` flagged in ``mask``. One launch, no host
+    synchronisation. ``A`` and ``out`` float16 or bfloat16; ``K`` a multiple of 16 up to 131056. Returns ``out``."""
+    torch.ops.bitsandbytes_amd.int8_outlier_addmm_.default(out, A, CB, SCB, mask)
+    return out
 
 
 def int8_linear_matmul(A: Tensor, B: Tensor, out: Optional[Tensor] = None, dtype=torch.int32) -> Tensor:

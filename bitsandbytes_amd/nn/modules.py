@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from .. import functional as F
-from .._ops import MOE_GROUP_SCORE_CODES, MOE_SCORING_CODES
+from .._ops import MOE_GROUP_SCORE_CODES, MOE_SCORING_CODES, int8_k_served
 from ..autograd import matmul_4bit
 from ..functional import QuantState
 
@@ -717,7 +717,11 @@ class Linear8bitLt(nn.Linear):
     keys ``weight`` int8, ``SCB``, optional ``weight_format`` = row) and move it to the HIP device. ``threshold == 0``: the forward is
     two launches - quantize x row-wise, int8 matmul with the dequantization and the bias as its epilogue - without a host
     synchronisation (it can be captured in a graph). ``threshold > 0``: the mixed decomposition - activation columns holding a
-    value at or above the threshold go through a 16-bit matmul instead; finding them synchronises."""
+    value at or above the threshold go through a 16-bit matmul instead. With float16 / bfloat16 input and ``in_features`` a multiple
+    of 16 up to 131056 the outlier columns stay on the device as a bitmask: quantize with the mask (three launches, two for one row),
+    the same int8 matmul, and one launch that adds the outlier term in place - no host synchronisation either, so this forward can be
+    captured in a graph as well. float32 input or any other ``in_features`` takes the composed path
+    (``int8_vectorwise_quant`` + ``int8_mixed_scaled_mm``), where finding the columns synchronises."""
 
     def __init__(self, input_features, output_features, bias=True, has_fp16_weights=False, threshold=0.0, index=None, device=None):
         if has_fp16_weights:
@@ -775,6 +779,13 @@ class Linear8bitLt(nn.Linear):
             raise RuntimeError("Linear8bitLt: the weight is not quantized yet - move the layer to the HIP device first")
         x2 = x.reshape(-1, x.shape[-1])
         ops = torch.ops.bitsandbytes
+        if self.threshold > 0.0 and x.dtype in (torch.float16, torch.bfloat16) and int8_k_served(x2.shape[-1]):
+            # the outlier set stays on the device as a bitmask: a fixed number of launches, nothing read on the host
+            x2 = x2.contiguous()
+            q, stats, mask = torch.ops.bitsandbytes_amd.int8_vectorwise_quant_mask.default(x2, self.threshold)
+            out = ops.int8_scaled_mm.default(q, weight.CB, stats, weight.SCB, self.bias, x.dtype)
+            torch.ops.bitsandbytes_amd.int8_outlier_addmm_.default(out, x2, weight.CB, weight.SCB, mask)
+            return out.view(*x.shape[:-1], self.out_features)
         q, stats, outlier_cols = ops.int8_vectorwise_quant.default(x2, self.threshold)
         if self.threshold > 0.0:
             out = ops.int8_mixed_scaled_mm.default(x2, q, weight.CB, stats, weight.SCB, outlier_cols, self.bias)[0]

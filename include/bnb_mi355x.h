@@ -304,7 +304,7 @@ typedef struct bnb_mi355x_gemm_4bit_experts_mfma_args {
 int bnb_mi355x_gemm_4bit_experts_mfma(const bnb_mi355x_gemm_4bit_experts_mfma_args* args);
 int bnb_mi355x_gemm_4bit_experts_mfma_supported(int dtype, int E, int N, int K, int blocksize, int gated);
 /* ------------------------------------------------------------------------------------------------
- * LLM.int8() inference (csrc/int8_quant.hip, csrc/gemm_int8.hip). dtype codes: 0 fp32, 1 fp16, 2 bf16. All three calls take one argument
+ * LLM.int8() inference (csrc/int8_quant.hip, csrc/gemm_int8.hip, csrc/int8_outlier.hip). dtype codes: 0 fp32, 1 fp16, 2 bf16. All calls take one argument
  * block (struct_bytes = sizeof of the block, as bnb_mi355x_gemm_4bit_experts_mfma does), only enqueue
  * work on `stream`, allocate nothing, and return 0 after the launch (an empty problem: 0, nothing launched) or a non-zero code with
  * NOTHING launched; they never end the process. The arithmetic is that of the reference's default (torch) backend
@@ -327,6 +327,45 @@ typedef struct bnb_mi355x_int8_vectorwise_quant_args {
     bnb_stream_t stream;
 } bnb_mi355x_int8_vectorwise_quant_args;
 int bnb_mi355x_int8_vectorwise_quant(const bnb_mi355x_int8_vectorwise_quant_args* args);
+/* The sync-free LLM.int8() mixed decomposition (csrc/int8_quant.hip, csrc/int8_outlier.hip): the outlier columns stay on the device as a
+ * bitmask, nothing is read on the host, and the launch count does not depend on the data (both calls can be captured in a graph).
+ * bnb_mi355x_int8_vectorwise_quant_mask: the row-wise quantize above with threshold > 0 (anything else is MALFORMED), and
+ *   mask int32 [ceil(cols / 32)]: bit c % 32 of word c / 32 is set iff some row has |A[r, c]| >= threshold; bits at and behind cols are 0;
+ *   row_stats[r] leaves out the outlier elements of row r only; q is 0 in every flagged column of EVERY row.
+ * Three launches in stream order (two with one row): a kernel clears the mask, the quantize kernel ORs its row's outlier bits into it
+ * with vector atomics (non-zero patterns only; an OR does not depend on its order: the result is deterministic), a kernel writes the
+ * zero bytes of the flagged columns. rows == 0 clears the mask. */
+typedef struct bnb_mi355x_int8_vectorwise_quant_mask_args {
+    size_t struct_bytes;       /* sizeof of this struct as the caller was compiled */
+    int dtype;                 /* of A */
+    float threshold;           /* > 0 */
+    long rows, cols;
+    const void* A;
+    int8_t* q;
+    float* row_stats;
+    int32_t* mask;             /* [ceil(cols / 32)] */
+    bnb_stream_t stream;
+} bnb_mi355x_int8_vectorwise_quant_mask_args;
+int bnb_mi355x_int8_vectorwise_quant_mask(const bnb_mi355x_int8_vectorwise_quant_mask_args* args);
+/* out[m, n] = T(float(out[m, n]) + sum over the flagged columns c of A[m, c] * Wd[n, c]), in place on the [M, N] result of the scaled
+ * int8 matmul; Wd[n, c] = T((float(CB[n, c]) * SCB[n]) * 7.874015718698502e-3f) (two fp32 products, each rounded, then T); products on
+ * v_mfma_f32_16x16x32_{f16,bf16} with fp32 accumulation; ONE rounding of the sum to T. T = dtype 1 (fp16) or 2 (bf16), of A and out.
+ * A [M, K] contiguous, CB int8 [N, K], SCB fp32 [N], mask as above with cols = K (bits at and behind K are ignored). Any M and N; K a
+ * multiple of 16 up to 131056, any other K returns BNB_MI355X_INT8_REFUSED_K (silent). One launch whose grid depends on M and N alone:
+ * a workgroup owns 64 columns x 64 rows of out and compacts the mask into a column list in LDS itself; with an empty mask no byte of
+ * out is written. No workspace, no atomics. */
+typedef struct bnb_mi355x_int8_outlier_addmm_args {
+    size_t struct_bytes;       /* sizeof of this struct as the caller was compiled */
+    int dtype;                 /* of A and out: 1 / 2 */
+    long M, N, K;
+    const void* A;
+    const int8_t* CB;
+    const float* SCB;          /* [N] */
+    const int32_t* mask;       /* [ceil(K / 32)] */
+    void* out;
+    bnb_stream_t stream;
+} bnb_mi355x_int8_outlier_addmm_args;
+int bnb_mi355x_int8_outlier_addmm(const bnb_mi355x_int8_outlier_addmm_args* args);
 /* C[m, n] = sum_k A[m, k] * B[n, k], A [M, K] and B [N, K] int8 row-major and 16-byte aligned, exact in int32, on
  * v_mfma_i32_16x16x64_i8; any M and N, K a multiple of 16 up to 131056 (128 * 128 * K fits int32) - any other K returns
  * BNB_MI355X_INT8_REFUSED_K. epilogue 0: out is int32 [M, N]. epilogue 1: out is [M, N] of out_dtype,

@@ -15,8 +15,11 @@ order reversed every round; median and min ... max of the rounds - read the spre
 For M <= 16 the scaled_mm column also gives the achieved bytes/s over bench.HBM_PEAK_GBS; the bound there is the N * K weight bytes.
 For M >= 128 the 'mm 6100' column also gives 2 M N K operations / time over the int8 MFMA peak at the clock the device reports: CUs x 4 SIMDs x
 1024 operations a cycle (v_mfma_i32_16x16x64_i8: 32768 operations in 8 passes of 4 cycles) x torch's clock_rate.
-    python tools/bench_int8.py [--rounds 5] [--quick] [--out profiles/int8_bench.txt]"""
+--mixed prints the threshold-6 table instead (mixed_table below: the sync-free mixed decomposition against the composed ops).
+    python tools/bench_int8.py [--rounds 5] [--quick] [--out profiles/int8_bench.txt]
+    python tools/bench_int8.py --mixed [--rounds 5] [--quick] [--out profiles/int8_mixed_bench.txt]"""
 import argparse
+import copy
 import ctypes as ct
 import math
 import os
@@ -35,14 +38,85 @@ from tools.bench_experts import CACHE_BYTES, capture, timed  # noqa: E402
 SHAPES = [(4096, 4096), (11008, 4096), (4096, 11008)]  # (N, K)
 MS = (1, 4, 16, 64, 128, 256, 512, 2048)
 OPS = torch.ops.bitsandbytes
+MIXED_OUTLIER_COLS = 8  # --mixed: columns of x that hold a value above the threshold
+
+
+class Eager:
+    """What `timed` replays for a leg that cannot be captured: the calls themselves, host time included."""
+
+    def __init__(self, fn):
+        self.replay = fn
+
+
+def mixed_table(args, say):
+    """--mixed: Linear8bitLt at threshold 6 (the mixed decomposition), x bf16 [M, K] with MIXED_OUTLIER_COLS columns that hold one value
+    of 8.0 each (the other values are randn: none reaches 6 in practice) - the handful of outlier feature dimensions of a real model.
+      layer t0   Linear8bitLt(x), threshold 0: 2 launches, in the tool's graphs (the yardstick: the same matmul without the outlier term)
+      layer t6   Linear8bitLt(x), threshold 6: quantize with the mask (3 launches, 2 at M = 1), int8_scaled_mm, int8_outlier_addmm_ -
+                 in the tool's graphs, nothing read on the host
+      composed   int8_vectorwise_quant(x, 6.0) then int8_mixed_scaled_mm: the path of the parent commit. It synchronises (the number of
+                 outlier columns sizes a tensor) and cannot be captured: timed EAGERLY with events around the same rotation of calls, so
+                 its figure INCLUDES the host time of about a dozen launches and one device-to-host round trip per call."""
+    say(f"# us per call: median (min ... max) of {args.rounds} rounds; x bf16 with {MIXED_OUTLIER_COLS} outlier columns; 'layer' legs in graphs, "
+        "'composed' eager (host time included)")
+    names = ["layer t0", "layer t6", "composed t6 (eager)"]
+    say(f"{'N x K':>13s} {'M':>5s} " + " ".join(f"{n:>28s}" for n in names) + f" {'t6/t0':>7s} {'composed/t6':>11s}")
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    for N, K in SHAPES:
+        L = max(2, math.ceil(1.25 * CACHE_BYTES / (N * K)))
+        calls = L * math.ceil(64 / L)
+        layers, layers6 = [], []
+        for _ in range(L):
+            l8 = bnb.nn.Linear8bitLt(K, N, bias=False)
+            l8.weight = bnb.nn.Int8Params((torch.randn(N, K, device="cuda", generator=gen) / K ** 0.5).cpu())
+            layers.append(l8.to("cuda"))
+            l6 = copy.copy(layers[-1])  # (the same parameters)
+            l6.threshold = 6.0
+            layers6.append(l6)
+        for M in (MS[:1] if args.quick else MS):
+            x = torch.randn(M, K, device="cuda", generator=gen).clamp(-5.5, 5.5)
+            x[torch.arange(MIXED_OUTLIER_COLS) % M, torch.arange(MIXED_OUTLIER_COLS) * (K // MIXED_OUTLIER_COLS) + 3] = 8.0
+            x = x.bfloat16()
+
+            def layer_t0():
+                for c in range(calls):
+                    layers[c % L](x)
+
+            def layer_t6():
+                for c in range(calls):
+                    layers6[c % L](x)
+
+            def composed_t6():
+                for c in range(calls):
+                    w = layers[c % L].weight
+                    q, stats, cols = OPS.int8_vectorwise_quant.default(x, 6.0)
+                    OPS.int8_mixed_scaled_mm.default(x, q, w.CB, stats, w.SCB, cols, None)
+
+            composed_t6()
+            torch.cuda.synchronize()
+            legs = [capture(layer_t0), capture(layer_t6), Eager(composed_t6)]
+            reps = [max(2, int(10000.0 / (timed(g, calls, 1) * calls)) + 1) for g in legs]
+            samples = [[] for _ in legs]
+            for r in range(args.rounds):
+                for i in (range(len(legs)) if r % 2 == 0 else reversed(range(len(legs)))):
+                    samples[i].append(timed(legs[i], calls, reps[i]))
+            med = [statistics.median(s) for s in samples]
+            cols = [f"{m:9.2f} ({min(s):.2f}...{max(s):.2f})" for m, s in zip(med, samples)]
+            say(f"{f'{N} x {K}':>13s} {M:>5d} " + " ".join(f"{c:>28s}" for c in cols) + f" {med[1] / med[0]:6.2f}x {med[2] / med[1]:10.2f}x")
+            del legs
+        del layers, layers6
+        torch.cuda.empty_cache()
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--quick", action="store_true", help="first M of every shape only")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "int8_bench.txt"), help="the table is also written here ('' for none)")
+    ap.add_argument("--mixed", action="store_true", help="the threshold-6 table (mixed_table) instead, to profiles/int8_mixed_bench.txt")
+    ap.add_argument("--out", default=None, help="the table is also written here ('' for none; default profiles/int8_bench.txt)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "int8_mixed_bench.txt" if args.mixed else "int8_bench.txt")
     lines = []
 
     def say(s=""):
@@ -50,6 +124,12 @@ def main():
         lines.append(s)
 
     say(f"# {torch.cuda.get_device_name(0)}, {bnb.lib.bnb_mi355x_version().decode()}, torch {torch.__version__}")
+    if args.mixed:
+        mixed_table(args, say)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     say(f"# us per call: median (min ... max) of {args.rounds} rounds; x bf16; %HBM = N * K bytes / time / {HBM_PEAK_GBS:.0f} GB/s (M <= 16)")
     props = torch.cuda.get_device_properties(0)
     khz = ct.c_int(0)  # hipDeviceAttributeClockRate (5): the peak engine clock the runtime reports, kHz
